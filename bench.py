@@ -11,8 +11,16 @@ parallel model is the reference model reset per slice and codes 
 the reference's own 64-bit coder; the optional 32-bit P32 coder is measured on the same batch
 afterwards and reported as the labelled extra key `p32` (with its container-size delta).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
+
+A plain run does what the headline needs and no more: it generates the batch, warms up, times the K
+steps and prints the line (metric, value, ms_per_step, config, the roofline from the timed steps'
+own HIP events).  --dump-outputs DIR then writes what the last timed step left in the batch's output
+buffers as DIR/<name>.npy (dump_outputs): the generator is seeded, so two builds run with the same
+arguments can be compared array for array.  Everything below -- the oracle parity of the batch, the
+P32 coder, the CPU baselines, the whole-file, corpus and R-mode legs and the configs[3] stream leg
+(at N > 1 the sharded corpus and stream legs) -- runs only with --full, as extra keys of the same line.
 
 Weak scaling: every rank roundtrips its own 1024-slice batch (different seeds); slices are
 independent in the parallel model, so there is no collective in the timed region.  value = bytes of
@@ -710,6 +718,50 @@ def stream_cpu_baseline(data, ps, budget_s):
     return rec
 
 
+DUMP_SAMPLE = 1 << 21   # bytes sampled from each of the two byte outputs (8 MB each as float32)
+DUMP_SEED = 20240229    # the sample positions' seed: the same positions in every run
+
+
+def dump_outputs(batch, out_dir):
+    """--dump-outputs: what the last timed roundtrip step left in the batch's output buffers, the
+    arrays a caller of avr_roundtrip_slices reads back, as float .npy files (about 17 MB in all):
+      verdict             float32 [n]      the device's per-slice verdict (1 = regenerated bit-exactly)
+      compress_results    float64 [n, 10]  avr_slice_result of the compress: out_len, status, bins, mbs, bill[6]
+      decompress_results  float64 [n, 10]  the same of the decompress
+      recoded_sums        float64 [n, 2]   per slice, over all its re-coded bytes b[i]: sum b[i] and
+                                           sum b[i] * (i % 251 + 1) -- every byte counts
+      recoded_sample      float32 [m]      the slices' re-coded bytes laid end to end, at DUMP_SAMPLE
+                                           seeded positions (sorted; the same positions every run)
+      regenerated_sums / regenerated_sample  the same of the regenerated CABAC payloads."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    descs = batch.ps.descs
+    res = {"c": batch.results("c"), "d": batch.results("d")}
+    arrays = {"verdict": batch.verdicts().astype(np.float32)}
+    for tag, name in (("c", "compress_results"), ("d", "decompress_results")):
+        r = res[tag]
+        arrays[name] = np.column_stack([r["out_len"], r["status"], r["bins"], r["mbs"], r["bill"]]).astype(np.float64)
+    ok_c = (res["c"]["status"] == 0) & (descs["coded"] != 0)
+    outputs = (("recoded", batch.d_work, descs["out_offset"], np.where(ok_c, res["c"]["out_len"], 0)),
+               ("regenerated", batch.d_regen, descs["payload_offset"],
+                np.where(res["d"]["status"] == 0, res["d"]["out_len"], 0)))
+    for name, d_buf, offs, lens in outputs:
+        buf = d_buf.cpu().numpy()
+        segs = [buf[int(o):int(o) + int(ln)] for o, ln in zip(offs, lens)]
+        weight = (np.arange(max([len(s) for s in segs] + [1]), dtype=np.uint64) % 251 + 1)
+        arrays[f"{name}_sums"] = np.array(
+            [[s.sum(dtype=np.uint64), (s * weight[:len(s)]).sum(dtype=np.uint64)] for s in segs],
+            dtype=np.float64).reshape(len(segs), 2)
+        flat = np.concatenate(segs) if segs else np.zeros(0, dtype=np.uint8)
+        rng = np.random.default_rng(DUMP_SEED)
+        pos = np.sort(rng.integers(0, len(flat), size=min(len(flat), DUMP_SAMPLE))) if len(flat) else []
+        arrays[f"{name}_sample"] = flat[pos].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    progress(f"outputs written to {out}: " + ", ".join(f"{k}{list(a.shape)}" for k, a in arrays.items()))
+
+
 _JSON_OUT = sys.stdout
 
 
@@ -951,6 +1003,11 @@ def main():
     ap.add_argument("--mb-width", type=int, default=120)
     ap.add_argument("--mb-height", type=int, default=68)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (oracle parity, P32, CPU baselines, files, "
+                         "corpus, R-mode legs, the configs[3] stream leg) and report them in the same line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--round", default="r06")
@@ -962,7 +1019,7 @@ def main():
     ap.add_argument("--rfiles", type=int, default=256, help="files in the R-mode many-files leg (0: skip)")
     ap.add_argument("--rclips", type=int, default=512, help="copies of realshort.mp4 in the R-mode clips leg (0: skip)")
     ap.add_argument("--stream-leg-seconds", type=int, default=600,
-                    help="length of the configs[3] stream leg of the default run (0: skip)")
+                    help="length of the configs[3] stream leg of a --full run (0: skip)")
     ap.add_argument("--no-p32", action="store_true", help="skip the P32-coder extra measurement")
     ap.add_argument("--stream-steps", type=int, default=1)
     ap.add_argument("--stream-shard", action="store_true",
@@ -970,6 +1027,10 @@ def main():
     ap.add_argument("--stream-seconds", type=int, default=600)
     ap.add_argument("--stream-mb", type=int, nargs=2, default=(240, 135))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.stream_shard and args.dump_outputs:
+        ap.error("--dump-outputs writes the headline batch's outputs; it does not go with --stream-shard")
     if args.stream_shard:
         return main_stream_shard(args)
 
@@ -1024,14 +1085,16 @@ def main():
         elapsed = time.perf_counter() - t0
     # the timed steps recomputed the same outputs: re-check them, and against the oracle's answer
     bit_exact = bit_exact and bool((batch.verdicts() == 1).all())
-    gold = golden_check(batch, data, args) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, args.dump_outputs)
+    gold = golden_check(batch, data, args) if args.full and rank == 0 else None
     if gold is not None and gold.get("match") is False:
         bit_exact = False
     t_comp = sum(e[0].elapsed_time(e[1]) for e in evs) / args.steps / 1e3
     t_dec = sum(e[2].elapsed_time(e[3]) for e in evs) / args.steps / 1e3
     # labelled extra, outside the headline's timed region: the same batch through the P32 coder
     p32 = None
-    if world == 1 and not args.no_p32:
+    if args.full and world == 1 and not args.no_p32:
         p32 = p32_extra(batch, args, stream, mk, len(data), C)
 
     tot = torch.tensor([elapsed, len(data), 0.0 if bit_exact else 1.0], dtype=torch.float64, device=_coll(dev))
@@ -1094,25 +1157,25 @@ def main():
         if p32 is not None:
             line["p32"] = p32
         progress(f"batch: {line['value']:.1f} MB/s")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(ctx, args, len(data))
             progress("cpu baseline done")
-        if world == 1 and not args.no_files:
+        if args.full and world == 1 and not args.no_files:
             line["file_roundtrip"] = file_roundtrips(ctx, args)
-        if world == 1 and not args.no_corpus:
+        if args.full and world == 1 and not args.no_corpus:
             line["corpus"] = corpus_section(ctx, args)
-        if world == 1 and args.rfiles > 0 and not args.no_files:
+        if args.full and world == 1 and args.rfiles > 0 and not args.no_files:
             line["rmode_files"] = rmode_files_section(ctx, args)
-        if world == 1 and args.rclips > 0 and not args.no_files:
+        if args.full and world == 1 and args.rclips > 0 and not args.no_files:
             line["rmode_clips"] = rmode_clips_section(ctx, args)
-    if world > 1 and not args.no_corpus:
+    if args.full and world > 1 and not args.no_corpus:
         rec = corpus_sharded(ctx, args, world, rank, dev)
         if rank == 0:
             line["corpus"] = rec
     # BASELINE configs[3] at its full length (600 s of 4K, 18,000 slices) as a labelled extra key:
     # at N = 1 beside the headline, at N > 1 sharded over the ranks (strong scaling; the only
     # leg with a data-path collective: the gathers and the scatter over RCCL)
-    if args.stream_leg_seconds > 0 and not args.no_files:
+    if args.full and args.stream_leg_seconds > 0 and not args.no_files:
         _init_dist(world, dev)
         try:
             rec = stream_shard_leg(ctx, args, args.stream_leg_seconds, world, rank, dev,

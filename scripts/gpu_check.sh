@@ -2,6 +2,8 @@
 # One GPU session: smoke, GPU tests, a small bench (+ whole-file roundtrips).  Every GPU step has its
 # own time limit and the chain stops at the first failure.
 set -o pipefail
+# the small bench runs every leg (bench.py --full: CPU baselines, files, corpus, ...), not the headline alone
+BENCH_ARGS="--full ${BENCH_ARGS:---slices 96 --steps 1 --warmup 1 --cpu-seconds 5}"
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 echo "== smoke" && timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 \

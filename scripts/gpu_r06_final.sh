@@ -33,7 +33,7 @@ case ${PART:-a} in
     && python scripts/pmc_traffic.py gpurun_out/r06z_stream gpurun_out/r06_stream_pmc.json --leg stream_shard \
          --seconds 600 --mb 240 135 > $O/stream_pmc_traffic.log ;;
   d)
-    echo "== bench" && timeout -k 10 1100 python -u bench.py > $O/bench.json 2> $O/bench.err \
+    echo "== bench" && timeout -k 10 1100 python -u bench.py --full > $O/bench.json 2> $O/bench.err \
     && tail -c 600 $O/bench.json \
     && echo "== split kernel stats" \
     && PROBE_ONLY=4K_IBBP timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/split_prof -o run -- \

@@ -2,6 +2,8 @@
 # One GPU session: smoke, GPU parity tests, the default bench, and a rocprofv3 kernel-trace
 # summary of the bench.  Every GPU step has its own time limit; the chain stops at the first failure.
 set -o pipefail
+# the default bench of a round is the line with every leg (bench.py --full)
+BENCH_ARGS="--full ${BENCH_ARGS:---cpu-seconds 10}"
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out

@@ -52,3 +52,58 @@ def test_bench_golden_is_consistent():
     class A:
         slices, mb_width, mb_height, seed = 1024, 120, 68, 1
     assert bench.golden_check(None, b"", A) is None   # another seed: not this golden's batch
+
+
+def test_dump_outputs_arrays(tmp_path):
+    """bench.dump_outputs on a stand-in batch of host tensors: the arrays' names, dtypes and shapes,
+    the per-slice sums over exactly each slice's valid bytes (a failed or uncoded slice counts as
+    empty), a sample drawn from the slices' bytes laid end to end at the same positions every run."""
+    import numpy as np
+    import pytest
+    torch = pytest.importorskip("torch")
+    import avrecode_amd as avr
+
+    n = 3
+    descs = np.zeros(n, dtype=avr.SLICE_DESC)
+    descs["out_offset"] = [0, 16, 48]
+    descs["payload_offset"] = [0, 32, 64]
+    descs["coded"] = [1, 1, 0]
+    work = np.arange(1, 81, dtype=np.uint8)
+    regen = np.arange(101, 181, dtype=np.uint8)
+    res_c = np.zeros(n, dtype=avr.SLICE_RESULT)
+    res_c["out_len"], res_c["status"], res_c["bins"] = [5, 7, 9], [0, 0, 0], [50, 70, 90]
+    res_c["bill"][1] = [1, 2, 3, 4, 5, 6]
+    res_d = np.zeros(n, dtype=avr.SLICE_RESULT)
+    res_d["out_len"], res_d["status"] = [4, 6, 8], [0, -3, 0]
+
+    class PS:
+        pass
+
+    class Batch:
+        ps = PS()
+        d_work, d_regen = torch.from_numpy(work), torch.from_numpy(regen)
+        results = staticmethod(lambda which="c": res_c if which == "c" else res_d)
+        verdicts = staticmethod(lambda: np.array([1, 0, 1], dtype=np.int32))
+
+    Batch.ps.descs = descs
+    bench.dump_outputs(Batch, tmp_path / "a")
+    bench.dump_outputs(Batch, tmp_path / "b")
+    names = {"verdict", "compress_results", "decompress_results", "recoded_sums", "recoded_sample",
+             "regenerated_sums", "regenerated_sample"}
+    assert {p.stem for p in (tmp_path / "a").iterdir()} == names
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    for k in names:
+        assert a[k].dtype in (np.float32, np.float64)
+        assert np.array_equal(a[k], np.load(tmp_path / "b" / f"{k}.npy"))
+    assert a["verdict"].tolist() == [1, 0, 1]
+    assert a["compress_results"].shape == a["decompress_results"].shape == (n, 10)
+    assert a["compress_results"][1].tolist() == [7, 0, 70, 0, 1, 2, 3, 4, 5, 6]
+    assert a["decompress_results"][1, :2].tolist() == [6, -3]
+    w = lambda seg: [float(sum(seg)), float(sum(b * (i % 251 + 1) for i, b in enumerate(seg)))]  # noqa: E731
+    # slice 2 is not coded, slice 1's decompress failed: no bytes of theirs count
+    assert a["recoded_sums"].tolist() == [w(range(1, 6)), w(range(17, 24)), [0.0, 0.0]]
+    assert a["regenerated_sums"].tolist() == [w(range(101, 105)), [0.0, 0.0], w(range(165, 173))]
+    # 12 valid bytes each: every sample is one of them, in end-to-end order
+    assert len(a["recoded_sample"]) == len(a["regenerated_sample"]) == 12
+    assert set(a["recoded_sample"]) <= set(range(1, 6)) | set(range(17, 24))
+    assert list(a["recoded_sample"]) == sorted(a["recoded_sample"])

@@ -3,8 +3,8 @@
 `python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ...` exactly as the driver
 launches it, at tiny sizes, with the collectives on gloo (AVR_DIST_BACKEND=gloo: both ranks share
 this box's one GPU, and RCCL will not put two ranks on one device):
-* the default mode: every rank's weak-scaling batch (headline), the max-over-ranks reduction, the
-  corpus dealt over the ranks (corpus_sharded);
+* the default mode with --full: every rank's weak-scaling batch (headline), the max-over-ranks
+  reduction, the corpus dealt over the ranks (corpus_sharded) and the sharded stream leg;
 * --stream-shard (BASELINE configs[3]): the stream cut over the ranks, the gather to rank 0 and its
   container assembly, rank 0's plan of that container scattered over the ranks, every rank's
   decompress, the gather of the regenerated slices and rank 0's splice into the stream.
@@ -38,8 +38,8 @@ def _run_two_ranks(extra):
 
 
 def test_bench_default_mode_two_ranks():
-    line = _run_two_ranks(["--steps", "1", "--warmup", "1", "--slices", "8", "--mb-width", "40", "--mb-height", "24",
-                           "--corpus-scale", "0.05", "--stream-leg-seconds", "1", "--stream-mb", "20", "12"])
+    line = _run_two_ranks(["--full", "--steps", "1", "--warmup", "1", "--slices", "8", "--mb-width", "40",
+                           "--mb-height", "24", "--corpus-scale", "0.05", "--stream-leg-seconds", "1", "--stream-mb", "20", "12"])
     assert line["n_gpus"] == 2 and line["bit_exact"] is True
     assert line["scaling"] == "weak" and line["value"] > 0
     assert line["corpus"]["n_gpus"] == 2
