@@ -21,7 +21,7 @@ import numpy as np
 
 __all__ = [
     "AvrError", "Context", "MODEL_REFERENCE", "MODEL_PARALLEL", "MODEL_PARALLEL32", "MODEL_CHAINED", "MODEL_NAMES",
-    "SLICE_DESC",
+    "SLICE_DESC", "PIECE", "KEEP_ALL",
     "SLICE_RESULT", "SynthParams", "lib", "parse_stream", "assemble_container", "neighbor_tables",
     "plan_decompress", "splice_container", "container_model", "source_sha", "library_path", "EXPORTED_SYMBOLS",
     "seams_of_container",
@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "avr_hooks_end", "avr_hooks_destroy", "avr_neighbor_tables", "avr_last_phase_times",
     "avr_plan_decompress", "avr_splice_container", "avr_roundtrip_files", "avr_slice_kernel",
     "avr_compress_chain_range", "avr_decompress_chain_range", "avr_set_split_bytes", "avr_get_split_bytes",
+    "avr_dec_plan_load_pieces", "avr_dec_plan_units", "avr_dec_plan_recs", "avr_decompress_pieces", "avr_pack_pieces",
 )
 
 # avr_slice_desc / avr_slice_result (include/avrecode.h), C layout
@@ -78,7 +79,11 @@ SLICE_RESULT = np.dtype([("out_len", "<u4"), ("status", "<i4"), ("bins", "<u4"),
 # avr_pip_coding_type (CodingType, recode.cpp:616): the index of avr_file_stats.bill / cabac_bill
 CODING_TYPES = ("PIP_UNKNOWN", "PIP_UNREACHABLE", "PIP_SIGNIFICANCE_MAP", "PIP_SIGNIFICANCE_EOB",
                 "PIP_SIGNIFICANCE_NZ", "PIP_RESIDUALS")
-assert SLICE_DESC.itemsize == 96 and SLICE_RESULT.itemsize == 40
+# avr_piece (include/avrecode.h): what a unit of a piece plan is of its slice
+PIECE = np.dtype([("seam", "<i4"), ("n_mbs", "<u4"), ("slice", "<i4"), ("keep", "<u4")], align=True)
+KEEP_ALL = 0xFFFFFFFF    # avr_piece.keep of a last piece or a whole slice
+SLICE_NO_END = -9        # AVR_SLICE_NO_END
+assert SLICE_DESC.itemsize == 96 and SLICE_RESULT.itemsize == 40 and PIECE.itemsize == 16
 
 
 class AvrError(RuntimeError):
@@ -197,6 +202,11 @@ def lib() -> ctypes.CDLL:
     L.avr_dec_plan_descs.argtypes = [vp, vp]
     L.avr_dec_plan_arena.argtypes = [vp, vp, sz]
     L.avr_dec_plan_splice.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, psz]
+    L.avr_dec_plan_load_pieces.argtypes = [vp, vp, sz, pi, pi, psz, psz, pi, pi, pi, psz]
+    L.avr_dec_plan_units.argtypes = [vp, vp, vp]
+    L.avr_dec_plan_recs.argtypes = [vp, vp, sz]
+    L.avr_decompress_pieces.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, sz, vp, vp, vp, vp]
+    L.avr_pack_pieces.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.avr_container_model.argtypes = [vp, sz, pi]
     L.avr_synthesize_stream.argtypes = [vp, ctypes.POINTER(_SynthParams), i32, pp, psz]
     L.avr_container_describe.argtypes = [vp, sz, pp, pp, psz]
@@ -277,6 +287,11 @@ class ParsedStream:
     work_len: int            # bytes of compress output space the descs' out_offset/out_capacity index
     max_mb_width: int
     max_mb_height: int
+    # the units of a piece plan (DecompressPlan.parsed_units): what each desc is of its slice, and the
+    # seam records the pieces start from (rec_stride bytes each, the split kernels' device layout)
+    pieces: "np.ndarray | None" = None   # PIECE[n]
+    recs: "np.ndarray | None" = None     # uint8
+    rec_stride: int = 0
 
     @property
     def payload_bytes(self) -> int:
@@ -341,7 +356,14 @@ class DecompressPlan:
     batch (descs + the re-coded streams' arena, written into arena_out when given), splice(...) the
     file from the regenerated slices (into out when given: the view holding the file is returned).
     The handle keeps its scratch across loads; the container passed to load must stay alive and
-    unchanged until the next load.  Host only."""
+    unchanged until the next load.  Host only.
+
+    load(avrc, pieces=True) makes it a piece plan (avr_dec_plan_load_pieces), which also reads a
+    container whose long slices were cut (Context.split_bytes): n_slices / descs stay the coded
+    slices, the splice's indexing, and n_units / units / pieces list what one workgroup regenerates,
+    a whole slice or one piece of a split slice, with the seam records in recs (rec_stride bytes
+    each).  parsed_units(arena_out) gives that batch; shard.collapse_units turns its per-unit results
+    into splice()'s per-slice ones."""
 
     def __init__(self):
         self._h = ctypes.c_void_p()
@@ -350,15 +372,23 @@ class DecompressPlan:
             raise AvrError(r, "avr_dec_plan_new failed")
         self._keep = None
 
-    def load(self, avrc) -> "DecompressPlan":
+    def load(self, avrc, pieces: bool = False) -> "DecompressPlan":
         p, n, keep = _buf(avrc)
         ns, mw, mh = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         al, wl = ctypes.c_size_t(), ctypes.c_size_t()
-        r = lib().avr_dec_plan_load(self._h, p, n, ctypes.byref(ns), ctypes.byref(al), ctypes.byref(wl),
-                                    ctypes.byref(mw), ctypes.byref(mh))
+        nu, nr, rs = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+        self.n_units = self.units = self.pieces = self.recs = None
+        self.rec_stride = 0
+        if pieces:
+            r = lib().avr_dec_plan_load_pieces(self._h, p, n, ctypes.byref(ns), ctypes.byref(nu), ctypes.byref(al),
+                                               ctypes.byref(wl), ctypes.byref(mw), ctypes.byref(mh), ctypes.byref(nr),
+                                               ctypes.byref(rs))
+        else:
+            r = lib().avr_dec_plan_load(self._h, p, n, ctypes.byref(ns), ctypes.byref(al), ctypes.byref(wl),
+                                        ctypes.byref(mw), ctypes.byref(mh))
         if r != AVR_OK:
             self._keep = None
-            raise AvrError(r, "avr_dec_plan_load failed")
+            raise AvrError(r, "avr_dec_plan_load_pieces failed" if pieces else "avr_dec_plan_load failed")
         self._keep = (avrc, keep)
         self.n_slices, self.arena_len, self.work_len = ns.value, al.value, wl.value
         self.max_mb_width, self.max_mb_height = mw.value, mh.value
@@ -366,6 +396,15 @@ class DecompressPlan:
         if self.n_slices:
             lib().avr_dec_plan_descs(self._h, d.ctypes.data)
         self.descs = d
+        if pieces:
+            self.n_units, self.rec_stride = nu.value, rs.value
+            self.units = np.zeros(self.n_units, dtype=SLICE_DESC)
+            self.pieces = np.zeros(self.n_units, dtype=PIECE)
+            self.recs = np.zeros(nr.value * rs.value, dtype=np.uint8)
+            r = lib().avr_dec_plan_units(self._h, self.units.ctypes.data, self.pieces.ctypes.data)
+            r = r or lib().avr_dec_plan_recs(self._h, self.recs.ctypes.data, self.recs.nbytes)
+            if r != AVR_OK:
+                raise AvrError(r, "avr_dec_plan_units / avr_dec_plan_recs failed")
         return self
 
     def parsed(self, arena_out: "np.ndarray | None" = None) -> ParsedStream:
@@ -375,7 +414,22 @@ class DecompressPlan:
         r = lib().avr_dec_plan_arena(self._h, a.ctypes.data, a.nbytes)
         if r != AVR_OK:
             raise AvrError(r, "avr_dec_plan_arena failed")
+        if self.units is not None:
+            raise ValueError("DecompressPlan.parsed: a piece plan's batch is parsed_units()")
         return ParsedStream(self.descs.copy(), a, self.work_len, self.max_mb_width, self.max_mb_height)
+
+    def parsed_units(self, arena_out: "np.ndarray | None" = None) -> ParsedStream:
+        """A piece plan's batch: the units' descs and streams, with pieces / recs / rec_stride."""
+        if self.units is None:
+            raise ValueError("DecompressPlan.parsed_units: load(avrc, pieces=True) first")
+        a = np.empty(self.arena_len, dtype=np.uint8) if arena_out is None else arena_out[:self.arena_len]
+        if a.nbytes < self.arena_len:
+            raise ValueError("DecompressPlan.parsed_units: arena_out too small")
+        r = lib().avr_dec_plan_arena(self._h, a.ctypes.data, a.nbytes)
+        if r != AVR_OK:
+            raise AvrError(r, "avr_dec_plan_arena failed")
+        return ParsedStream(self.units.copy(), a, self.work_len, self.max_mb_width, self.max_mb_height,
+                            self.pieces.copy(), self.recs, self.rec_stride)
 
     def splice(self, status, regen, offsets, lens, out: "np.ndarray | None" = None):
         st = np.ascontiguousarray(status, dtype=np.int32)
@@ -739,6 +793,26 @@ class Context:
                     "slice_kernel")
         name = ("slices_parallel_kernel", "slices_queue_kernel")[k.value]
         return f"{name}<{1 if decompress else 0}, false, {'true' if p32 else 'false'}>"
+
+    def decompress_pieces(self, d_desc, pieces, n, max_w, max_h, d_recs, n_recs, rec_stride, d_in, d_out, d_res,
+                          stream=None):
+        """avr_decompress_pieces: a batch of pieces and whole progressive slices of MODEL_PARALLEL, one
+        workgroup per unit.  pieces: the units' PIECE array on the HOST (checked there before the
+        launch); d_recs: the n_recs seam records its seam fields index, on the device."""
+        pc = np.ascontiguousarray(pieces, dtype=PIECE)
+        if len(pc) != n:
+            raise ValueError("decompress_pieces: one PIECE per unit")
+        self._check(lib().avr_decompress_pieces(self._h, self._ptr(d_desc), pc.ctypes.data, n, max_w, max_h,
+                                                self._ptr(d_recs), n_recs, rec_stride, self._ptr(d_in),
+                                                self._ptr(d_out), self._ptr(d_res), self._stream(stream)),
+                    "decompress_pieces")
+
+    def pack_pieces(self, d_desc, d_pieces, d_res, n, d_out, d_packed, d_offsets, d_kept, d_status, stream=None):
+        """avr_pack_pieces: every unit's kept bytes packed at d_offsets[k] (n + 1 entries, the prefix
+        sum of d_kept); d_status[k] the unit's status, SLICE_NO_END when it came out short of keep."""
+        P = self._ptr
+        self._check(lib().avr_pack_pieces(self._h, P(d_desc), P(d_pieces), P(d_res), n, P(d_out), P(d_packed),
+                                          P(d_offsets), P(d_kept), P(d_status), self._stream(stream)), "pack_pieces")
 
     def pack_outputs(self, d_desc, d_res, n, d_out, d_packed, d_offsets, stream=None):
         P = self._ptr

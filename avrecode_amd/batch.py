@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import SLICE_DESC, SLICE_RESULT, MODEL_PARALLEL, Context, ParsedStream
+from . import KEEP_ALL, PIECE, SLICE_DESC, SLICE_RESULT, MODEL_PARALLEL, Context, ParsedStream
 
 
 def _dev_bytes(a: np.ndarray, device) -> torch.Tensor:
@@ -160,6 +160,72 @@ class DecompressRange:
 
     def results(self) -> np.ndarray:
         return self.d_res[:max(1, self.n) * SLICE_RESULT.itemsize].cpu().numpy().view(SLICE_RESULT)[: self.n]
+
+
+class UnitBatch:
+    """The units of a piece plan (DecompressPlan.parsed_units / shard.subset_units: whole slices and
+    the pieces of split slices) on the device.  Buffers in unit order: d_desc, d_in (the streams),
+    d_recs (the seam records), d_work (the regenerated bytes), d_res.
+    decompress(): the units that are pieces -- they start at a seam, stop after n_mbs macroblocks or
+    keep only their share -- through avr_decompress_pieces, the whole slices (field, MBAFF and
+    over-wide ones among them, which are never cut) through avr_decompress_slices, one launch after
+    the other on the stream; the descriptor rows of each launch are gathered, and its result rows
+    scattered back, by index with torch.  pack(): one avr_pack_pieces over all units."""
+
+    def __init__(self, ctx: Context, part: ParsedStream, device=None):
+        self.ctx, self.part = ctx, part
+        self.device = torch.device("cuda", ctx.device) if device is None else device
+        self.n = n = len(part.descs)
+        self.d_desc = _dev_bytes(part.descs, self.device).view(n, SLICE_DESC.itemsize)
+        self.d_in = _dev_bytes(part.arena, self.device)
+        self.d_work = torch.zeros(max(16, part.work_len + 16), dtype=torch.uint8, device=self.device)
+        self.d_res = torch.zeros(n, SLICE_RESULT.itemsize, dtype=torch.uint8, device=self.device)
+        self.n_recs = len(part.recs) // part.rec_stride if part.rec_stride else 0
+        self.d_recs = (_dev_bytes(part.recs, self.device) if self.n_recs
+                       else torch.zeros(16, dtype=torch.uint8, device=self.device))
+        pc = part.pieces
+        self.is_piece = (pc["seam"] >= 0) | (pc["n_mbs"] > 0) | (pc["keep"] != KEEP_ALL)
+
+    def decompress(self, model: int = MODEL_PARALLEL, stream=None):
+        part, n = self.part, self.n
+        idx_p, idx_r = np.flatnonzero(self.is_piece), np.flatnonzero(~self.is_piece)
+        if len(idx_p) and model != MODEL_PARALLEL:
+            raise ValueError("UnitBatch: pieces exist in MODEL_PARALLEL containers only")
+        with torch.cuda.stream(stream) if stream is not None else _null():
+            for idx, pieces in ((idx_p, True), (idx_r, False)):
+                if not len(idx):
+                    continue
+                whole = len(idx) == n
+                rows = None if whole else torch.from_numpy(idx).to(self.device)
+                dd = self.d_desc if whole else self.d_desc[rows].contiguous()
+                dr = self.d_res if whole else torch.zeros(len(idx), SLICE_RESULT.itemsize, dtype=torch.uint8,
+                                                          device=self.device)
+                if pieces:
+                    self.ctx.decompress_pieces(dd, part.pieces[idx], len(idx), int(part.descs["mb_width"][idx].max()),
+                                               part.max_mb_height, self.d_recs, self.n_recs, part.rec_stride,
+                                               self.d_in, self.d_work, dr, stream)
+                else:
+                    self.ctx.decompress_slices(dd, len(idx), part.max_mb_width, part.max_mb_height, self.d_in,
+                                               self.d_work, dr, model, stream)
+                if not whole:
+                    self.d_res[rows] = dr
+
+    def pack(self, pieces: "np.ndarray | None" = None, stream=None):
+        """(d_packed uint8, d_offsets int64[n + 1], d_kept int32[n] holding uint32, d_status int32[n]):
+        unit k's kept bytes at d_offsets[k].  pieces: another PIECE array than the batch's (tests)."""
+        n = self.n
+        d_pieces = _dev_bytes(np.ascontiguousarray(self.part.pieces if pieces is None else pieces, dtype=PIECE),
+                              self.device)
+        d_packed = torch.zeros(max(16, self.part.work_len + 16), dtype=torch.uint8, device=self.device)
+        d_offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        d_kept = torch.zeros(max(1, n), dtype=torch.int32, device=self.device)
+        d_status = torch.zeros(max(1, n), dtype=torch.int32, device=self.device)
+        self.ctx.pack_pieces(self.d_desc, d_pieces, self.d_res, n, self.d_work, d_packed, d_offsets, d_kept,
+                             d_status, stream)
+        return d_packed, d_offsets, d_kept, d_status
+
+    def results(self) -> np.ndarray:
+        return self.d_res.cpu().numpy().reshape(-1).view(SLICE_RESULT)[: self.n]
 
 
 class _null:

@@ -85,6 +85,9 @@ struct avr_ctx {
   hipStream_t split_stream = nullptr;
   DevBuf sp_in, sp_out, sp_descs, sp_res, sp_ctl, sp_recs, sp_snapn, sp_est, sp_in2, sp_out2;
   size_t split_bytes = 0;   // avr_set_split_bytes / AVR_SPLIT_BYTES (0: no split)
+  // avr_decompress_pieces: the batch's PieceCtl array, host (alive while its upload is in flight) and device
+  std::vector<avr::PieceCtl> pc_host;
+  DevBuf pc_ctl;
   // a batch holding both progressive and field slices runs its field kernel beside the progressive
   // one (avr::FieldLane); AVR_FIELD_LANE=0 keeps the two in one stream, one after the other
   hipStream_t fld_stream = nullptr;
@@ -2319,6 +2322,30 @@ struct avr_dec_plan {
   int max_h = 1;
   const uint8_t* avrc = nullptr;   // the caller's container (the blocks point into it)
   size_t n = 0;
+  // a piece plan (avr_dec_plan_load_pieces): plan.descs = the coded slices (a split slice once, the
+  // splice's indexing), units = what one workgroup regenerates, in container order; plan's arena
+  // layout is the units'
+  bool pieces = false;
+  std::vector<avr_slice_desc> units;
+  std::vector<avr_piece> unit_pieces;
+  Bytes recs;                      // the seam records, rec_stride apart
+  size_t rec_stride = 0;
+  void reset() {
+    avrc = nullptr;
+    pieces = false;
+    job.blocks.clear();
+    job.desc_of_block.clear();
+    job.splits.clear();
+    job.stream.clear();   // keeps its capacity: the next stream is written over mapped pages
+    plan.descs.clear();
+    plan.arena_copies.clear();
+    plan.arena_end = 0;
+    plan.max_w = 1;
+    plan.layout_only = true;
+    units.clear();
+    unit_pieces.clear();
+    recs.clear();
+  }
 };
 extern "C" {
 
@@ -2337,15 +2364,7 @@ int avr_dec_plan_load(avr_dec_plan* h, const uint8_t* avrc, size_t n, int* n_sli
   if (!h || !avrc || !n_slices || !arena_len || !work_len || !max_mb_width || !max_mb_height)
     return AVR_ERR_INVALID_ARGUMENT;
   return guarded(nullptr, [&]() -> int {
-    h->avrc = nullptr;
-    h->job.blocks.clear();
-    h->job.desc_of_block.clear();
-    h->job.stream.clear();   // keeps its capacity: the next stream is written over mapped pages
-    h->plan.descs.clear();
-    h->plan.arena_copies.clear();
-    h->plan.arena_end = 0;
-    h->plan.max_w = 1;
-    h->plan.layout_only = true;
+    h->reset();
     if (int r = decompress_setup(nullptr, avrc, n, &h->job, &h->plan)) return r;
     uint64_t w = 0;
     int mh = 1;
@@ -2365,6 +2384,109 @@ int avr_dec_plan_load(avr_dec_plan* h, const uint8_t* avrc, size_t n, int* n_sli
     *max_mb_height = mh;
     return AVR_OK;
   });
+}
+
+// A piece plan: decompress_setup with a split plan (every check of the whole-file decompress on a
+// seams field), then the units laid out in container order -- a whole slice as avr_dec_plan_load
+// lays it out, a split slice's pieces one after the other, each stream copied straight from its
+// span of Block.cabac -- and plan.descs rebuilt as the coded slices, split ones included, for the
+// splice.
+int avr_dec_plan_load_pieces(avr_dec_plan* h, const uint8_t* avrc, size_t n, int* n_slices, int* n_units,
+                             size_t* arena_len, size_t* work_len, int* max_mb_width, int* max_mb_height, int* n_recs,
+                             size_t* rec_stride) {
+  if (!h || !avrc || !n_slices || !n_units || !arena_len || !work_len || !max_mb_width || !max_mb_height || !n_recs ||
+      !rec_stride)
+    return AVR_ERR_INVALID_ARGUMENT;
+  return guarded(nullptr, [&]() -> int {
+    h->reset();
+    SplitPlan sp;
+    if (int r = decompress_setup(nullptr, avrc, n, &h->job, &h->plan, &sp)) return r;
+    // units for slice- and piece-range sharding: the parallel models only, as avr_plan_decompress
+    if (!h->job.parallel) return AVR_ERR_UNSUPPORTED;
+    DecJob& j = h->job;
+    std::vector<avr_slice_desc> slices;
+    std::vector<avr::PbCopy> copies;
+    uint64_t at = 0, work = 0, swork = 0;
+    int mw = std::max(h->plan.max_w, sp.plan.max_w), mh = 1;
+    auto unit = [&](avr_slice_desc d, const uint8_t* src, size_t len, const avr_piece& p) {
+      d.payload_offset = (at + 15) & ~(uint64_t)15;
+      copies.push_back({(size_t)d.payload_offset, src, len});
+      at = d.payload_offset + len + 16;
+      d.out_offset = work;
+      work += ((uint64_t)d.out_capacity + 15) & ~15ull;
+      mh = std::max(mh, d.mb_height);
+      h->units.push_back(d);
+      h->unit_pieces.push_back(p);
+    };
+    for (size_t i = 0; i < j.blocks.size(); i++) {
+      const avr::PbBlock& b = j.blocks[i];
+      const int k = j.desc_of_block[i];
+      if (!b.has_cabac || k == -1) continue;
+      const int s = (int)slices.size();
+      const size_t u0 = h->units.size();
+      avr_slice_desc sd;
+      if (k >= 0) {
+        sd = h->plan.descs[k];
+        unit(sd, b.cabac, b.cabac_len, avr_piece{-1, 0, s, UINT32_MAX});
+      } else {
+        const SplitBlock& x = j.splits[-2 - k];
+        sd = sp.plan.descs[x.first];
+        sd.payload_size = sd.read_limit = (uint32_t)b.cabac_len;
+        sd.out_capacity = (uint32_t)(b.size + 64);
+        size_t off = 0;
+        for (int p = 0; p < x.pieces; p++) {
+          const avr_slice_desc& pd = sp.plan.descs[x.first + p];
+          const avr::PieceCtl& pc = sp.ctl[x.first + p];
+          const uint32_t keep = p + 1 < x.pieces ? x.q[p] - (p ? x.q[p - 1] : 0u) : UINT32_MAX;
+          // the plan's records say where their piece's bytes start in the slice (the kernels do not read it)
+          if (pc.seam >= 0) ((avr::SeamRec*)(sp.recs.data() + (size_t)pc.seam * sp.stride))->q = x.q[p - 1];
+          unit(pd, b.cabac + off, pd.payload_size, avr_piece{pc.seam, pc.n_mbs, s, keep});
+          off += pd.payload_size;
+        }
+      }
+      sd.payload_offset = h->units[u0].payload_offset;
+      sd.out_offset = swork;
+      swork += ((uint64_t)sd.out_capacity + 15) & ~15ull;
+      j.desc_of_block[i] = s;
+      slices.push_back(sd);
+    }
+    j.splits.clear();
+    h->plan.descs = std::move(slices);
+    h->plan.arena_copies = std::move(copies);
+    h->plan.arena_end = at;
+    h->plan.max_w = mw;
+    h->recs = std::move(sp.recs);
+    h->rec_stride = sp.stride;
+    h->pieces = true;
+    h->avrc = avrc;
+    h->n = n;
+    h->work = work;
+    h->max_h = mh;
+    *n_slices = (int)h->plan.descs.size();
+    *n_units = (int)h->units.size();
+    *arena_len = h->plan.arena_end + 16;
+    *work_len = work;
+    *max_mb_width = mw;
+    *max_mb_height = mh;
+    *n_recs = (int)(h->recs.size() / h->rec_stride);
+    *rec_stride = h->rec_stride;
+    return AVR_OK;
+  });
+}
+
+int avr_dec_plan_units(const avr_dec_plan* h, avr_slice_desc* descs, avr_piece* pieces) {
+  if (!h || !h->avrc || !h->pieces || ((!descs || !pieces) && !h->units.empty())) return AVR_ERR_INVALID_ARGUMENT;
+  if (!h->units.empty()) {
+    memcpy(descs, h->units.data(), sizeof(avr_slice_desc) * h->units.size());
+    memcpy(pieces, h->unit_pieces.data(), sizeof(avr_piece) * h->unit_pieces.size());
+  }
+  return AVR_OK;
+}
+
+int avr_dec_plan_recs(const avr_dec_plan* h, uint8_t* out, size_t cap) {
+  if (!h || !h->avrc || !h->pieces || cap < h->recs.size() || (!out && !h->recs.empty())) return AVR_ERR_INVALID_ARGUMENT;
+  if (!h->recs.empty()) memcpy(out, h->recs.data(), h->recs.size());
+  return AVR_OK;
 }
 
 int avr_dec_plan_descs(const avr_dec_plan* h, avr_slice_desc* out) {
@@ -3024,6 +3146,52 @@ int avr_pack_outputs(avr_ctx* c, const avr_slice_desc* d_desc, const avr_slice_r
   if (!c || n < 0 || (n && (!d_desc || !d_res || !d_out || !d_packed || !d_offsets))) return AVR_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, avr::launch_pack(d_desc, d_res, n, d_out, d_packed, d_offsets, (hipStream_t)stream));
+  return AVR_OK;
+}
+
+// The units of a piece plan on the device: the split kernel (one workgroup per unit) on the caller's
+// stream, from the caller's device-resident descriptors, streams and seam records.  The piece array
+// is checked here, before anything is launched: a record index outside d_recs would be read.
+int avr_decompress_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* pieces, int n, int max_w,
+                          int max_h, const uint8_t* d_recs, int n_recs, size_t rec_stride, const uint8_t* d_in,
+                          uint8_t* d_out, avr_slice_result* d_res, void* stream) {
+  if (!c || n < 0 || n_recs < 0 || (n && (!d_desc || !pieces || !d_in || !d_out || !d_res)) || (n_recs && !d_recs) ||
+      max_w <= 0 || max_h <= 0)
+    return AVR_ERR_INVALID_ARGUMENT;
+  if (max_w > avr::kMringCols || rec_stride < avr::seam_rec_bytes(max_w) || rec_stride > UINT32_MAX)
+    return fail(c, AVR_ERR_INVALID_ARGUMENT, "avr_decompress_pieces: picture wider than a seam record");
+  for (int k = 0; k < n; k++)
+    if (pieces[k].seam < -1 || pieces[k].seam >= n_recs)
+      return fail(c, AVR_ERR_INVALID_ARGUMENT,
+                  "avr_decompress_pieces: unit " + std::to_string(k) + " starts at a seam record outside the batch's");
+  if (!n) return AVR_OK;
+  return guarded(c, [&]() -> int {
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    c->pc_host.resize(n);
+    for (int k = 0; k < n; k++) c->pc_host[k] = avr::PieceCtl{pieces[k].seam, pieces[k].n_mbs, -1, 0};
+    HIP_TRY(c, c->pc_ctl.reserve(sizeof(avr::PieceCtl) * n));
+    HIP_TRY(c, c->sp_est.reserve(sizeof(uint16_t) * (size_t)avr::kEstGlobal * std::max(1, avr::split_grid(n, max_w)), true));
+    if (!d_recs) HIP_TRY(c, c->sp_recs.reserve(64));   // a batch without cuts: no record is read
+    HIP_TRY(c, hipMemcpyAsync(c->pc_ctl.p, c->pc_host.data(), sizeof(avr::PieceCtl) * n, hipMemcpyHostToDevice, st));
+    avr::SplitArgs sa;
+    sa.ctl = c->pc_ctl.as<avr::PieceCtl>();
+    sa.recs = d_recs ? const_cast<uint8_t*>(d_recs) : c->sp_recs.as<uint8_t>();
+    sa.rec_stride = (uint32_t)rec_stride;
+    HIP_TRY(c, avr::launch_split(1, c->tables.as<avr::EngineTables>(), d_desc, n, max_w, d_in, d_out, d_res,
+                                 c->sp_est.as<uint16_t>(), sa, 0, st));
+    return AVR_OK;
+  });
+}
+
+int avr_pack_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* d_pieces, const avr_slice_result* d_res,
+                    int n, const uint8_t* d_out, uint8_t* d_packed, uint64_t* d_offsets, uint32_t* d_kept,
+                    int32_t* d_status, void* stream) {
+  if (!c || n < 0 || (n && (!d_desc || !d_pieces || !d_res || !d_out || !d_packed || !d_offsets || !d_kept || !d_status)))
+    return AVR_ERR_INVALID_ARGUMENT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, avr::launch_pack_pieces(d_desc, d_pieces, d_res, n, d_out, d_packed, d_offsets, d_kept, d_status,
+                                     (hipStream_t)stream));
   return AVR_OK;
 }
 

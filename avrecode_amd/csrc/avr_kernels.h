@@ -189,5 +189,9 @@ hipError_t launch_verify(const avr_slice_desc* descs, const avr_slice_result* rc
                          const uint8_t* in, const uint8_t* regen, int32_t* verdict, hipStream_t stream);
 hipError_t launch_pack(const avr_slice_desc* descs, const avr_slice_result* res, int n, const uint8_t* out,
                        uint8_t* packed, uint64_t* offsets, hipStream_t stream);
+// avr_pack_pieces (avr_k_pieces.hip): launch_pack for units, each keeping what its avr_piece says
+hipError_t launch_pack_pieces(const avr_slice_desc* descs, const avr_piece* pieces, const avr_slice_result* res, int n,
+                              const uint8_t* out, uint8_t* packed, uint64_t* offsets, uint32_t* kept, int32_t* status,
+                              hipStream_t stream);
 
 }  // namespace avr

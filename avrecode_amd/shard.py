@@ -8,7 +8,17 @@ rank 0 (point-to-point send/recv over xGMI with backend "nccl" = RCCL; CPU tenso
   sharded_compress    re-coded blocks -> rank 0 builds the Recoded container (avr_assemble_container)
   sharded_decompress  regenerated CABAC payloads -> rank 0 splices them with the container's
                       literals and applies the last-byte patch (avr_splice_container)
-Both are byte-identical to the single-GPU calls.
+sharded_decompress is byte-identical to the single-GPU call; sharded_compress is where no slice is
+long enough for the whole-file compress to cut it (see its docstring).
+
+A container whose long slices were cut into pieces (Context.split_bytes; Block field 16) is
+decompressed by units instead of slices: a unit is what one workgroup regenerates, a whole slice or
+one piece of a split slice (DecompressPlan.load(avrc, pieces=True)).  The units are partitioned by
+their re-coded bytes, so the pieces of one long slice land on several ranks; each rank regenerates
+its units from their streams and seam records (decompress_units_range: avr_decompress_pieces for the
+pieces, avr_decompress_slices for the rest, one avr_pack_pieces that keeps of every piece only its
+share of the slice), the gather concatenates them in rank order, and rank 0 folds the units back
+into slices (collapse_units) for the same splice.
 
 CHAINED model (the reference model restarted every AVR_CHAIN_SLICES coded slices), one file over
 the ranks, both directions: its chains are independent, so a file's chains are cut into contiguous
@@ -27,8 +37,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import (MODEL_CHAINED, MODEL_PARALLEL, DecompressPlan, ParsedStream, assemble_container, container_model,
-               parse_stream, plan_decompress, splice_container)
+from . import (MODEL_CHAINED, MODEL_PARALLEL, PIECE, SLICE_NO_END, DecompressPlan, ParsedStream, assemble_container,
+               container_model, parse_stream, plan_decompress, seams_of_container, splice_container)
 
 
 def partition(sizes, world: int) -> list[tuple[int, int]]:
@@ -171,6 +181,55 @@ def subset(ps: ParsedStream, lo: int, hi: int, copy_arena: bool = True) -> Parse
     return ParsedStream(d, arena.copy() if copy_arena else arena, w1 - w0, ps.max_mb_width, ps.max_mb_height)
 
 
+def subset_units(pu: ParsedStream, lo: int, hi: int, copy_arena: bool = True) -> ParsedStream:
+    """The units [lo, hi) of a piece plan's batch (DecompressPlan.parsed_units) as a self-contained
+    batch: subset(), plus the seam records the range's pieces start from, seam rebased to the first
+    of them."""
+    sub = subset(pu, lo, hi, copy_arena)
+    p = pu.pieces[lo:hi].copy()
+    cut = p["seam"] >= 0
+    recs = np.zeros(0, np.uint8)
+    if cut.any():
+        r0, r1 = int(p["seam"][cut].min()), int(p["seam"][cut].max()) + 1
+        p["seam"][cut] -= r0
+        recs = pu.recs[r0 * pu.rec_stride:r1 * pu.rec_stride]
+    sub.pieces, sub.recs, sub.rec_stride = p, recs, pu.rec_stride
+    return sub
+
+
+def collapse_units(pieces, status, offsets, lens):
+    """Per-unit results of a piece plan (all its units, in order: pieces = DecompressPlan.pieces; unit
+    k's kept bytes at offsets[k], lens[k] of the gathered blob) as DecompressPlan.splice's per-slice
+    (status int32, offsets uint64, lens uint32).  A slice's status is the first non-zero status of
+    its units, or SLICE_NO_END when a piece but the last did not keep exactly its share or the
+    slice's units do not follow each other in the blob without a gap; its bytes start at its first
+    unit's and are as long as its units' together."""
+    pieces = np.asarray(pieces, dtype=PIECE)
+    status = np.asarray(status, dtype=np.int64)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    n = len(pieces)
+    if not (len(status) == len(offsets) == len(lens) == n):
+        raise ValueError("collapse_units: one status / offset / length per unit")
+    if n == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.uint64), np.zeros(0, np.uint32)
+    sl = pieces["slice"]
+    first = np.flatnonzero(np.concatenate([[True], sl[1:] != sl[:-1]]))
+    count = np.diff(np.concatenate([first, [n]]))
+    st = status[first].copy()
+    off = offsets[first].copy()
+    ln = np.add.reduceat(lens, first)
+    for s in np.flatnonzero(count > 1):
+        a, b = int(first[s]), int(first[s] + count[s])
+        bad = status[a:b][status[a:b] != 0]
+        if len(bad):
+            st[s] = bad[0]
+        elif ((lens[a:b - 1] != pieces["keep"][a:b - 1]).any()
+              or (offsets[a:b - 1] + lens[a:b - 1] != offsets[a + 1:b]).any()):
+            st[s] = SLICE_NO_END
+    return st.astype(np.int32), off.astype(np.uint64), ln.astype(np.uint32)
+
+
 def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = None,
                      model: int = MODEL_PARALLEL) -> bytes | None:
     """PARALLEL-model compress of one file across all ranks; the container is returned on rank 0.
@@ -179,7 +238,10 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     GPU (compress + device roundtrip check: a slice is coded only if it regenerates its payload),
     packs the re-coded bytes on the device and sends them to rank 0 (gather_flat over RCCL), which
     assembles the Recoded container from its own parse (avr_assemble_container_parsed).
-    Byte-identical to ctx.compress(data, model); model = MODEL_PARALLEL or MODEL_PARALLEL32."""
+    model = MODEL_PARALLEL or MODEL_PARALLEL32.  Byte-identical to ctx.compress(data, model) where
+    no slice is a split candidate (a progressive slice of at least 1.5 ctx.split_bytes payload
+    bytes), or with ctx.split_bytes = 0: the whole-file compress cuts such a slice into pieces, this
+    one codes every slice whole (the seams are not carried through the gather and the assembly)."""
     import torch
     import torch.distributed as dist
 
@@ -240,6 +302,51 @@ def decompress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PA
     return flat, status, offs, lens
 
 
+def decompress_units_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL):
+    """This rank's unit range of a sharded decompress of a split container on its GPU
+    (batch.UnitBatch): (flat uint8 tensor, status, offsets, lens) per unit, unit k's kept bytes at
+    flat[offsets[k] : offsets[k] + lens[k]].  The pieces go through avr_decompress_pieces, the whole
+    slices through avr_decompress_slices, one launch after the other on the current stream, and one
+    avr_pack_pieces packs all units in unit order, each piece cut down to its share of its slice."""
+    import torch
+
+    from .batch import UnitBatch
+
+    b = UnitBatch(ctx, part, device=device)
+    b.decompress(model)
+    flat, d_off, d_kept, d_status = b.pack()
+    torch.cuda.synchronize()
+    n = len(part.descs)
+    offs = d_off.cpu().numpy()[:n].astype(np.int64)
+    lens = d_kept.cpu().numpy()[:n].view(np.uint32).astype(np.int64)
+    return flat, d_status.cpu().numpy()[:n].astype(np.int64), offs, lens
+
+
+def _sharded_decompress_units(ctx, avrc, device, run_range):
+    """sharded_decompress of a container with seams: units instead of slices."""
+    import torch
+    import torch.distributed as dist
+
+    rank, world = dist.get_rank(), dist.get_world_size()
+    plan = DecompressPlan().load(avrc, pieces=True)
+    pu = plan.parsed_units()
+    model = container_model(avrc)
+    lo, hi = partition(pu.descs["payload_size"], world)[rank]
+    part = subset_units(pu, lo, hi)
+    dev = _gather_device(ctx, device)
+    if hi > lo:
+        flat, status, offs, lens = (run_range or (lambda p: decompress_units_range(ctx, p, device, model)))(part)
+    else:
+        flat = torch.zeros(16, dtype=torch.uint8, device=dev)
+        offs = lens = status = np.zeros(0, np.int64)
+    g = gather_flat(flat, status, offs, lens, dst=0, device=dev)
+    if g is None:
+        return None
+    st, blob, offs, lens = g
+    st, offs, lens = collapse_units(plan.pieces, st, offs, lens)
+    return plan.splice(st, blob, offs, lens).tobytes()
+
+
 def sharded_decompress(ctx, avrc: bytes, device=None, run_range=None) -> bytes | None:
     """PARALLEL-model decompress of one container across all ranks; the file is returned on rank 0.
 
@@ -248,10 +355,16 @@ def sharded_decompress(ctx, avrc: bytes, device=None, run_range=None) -> bytes |
     (decompress_range: avr_decompress_slices + avr_pack_outputs), and sends the packed payloads to
     rank 0 (gather_flat over RCCL), which splices them with the literals and applies the last-byte
     patch (avr_splice_container, recode.cpp:1338-1357).  Byte-identical to ctx.decompress(avrc).
-    run_range(part) -> (flat, status, offsets, lens) replaces the device step (CPU tests)."""
+    run_range(part) -> (flat, status, offsets, lens) replaces the device step (CPU tests).
+    A container whose long slices were cut (Block field 16) goes by units instead: planned with
+    pieces, partitioned by the units' re-coded bytes, each rank's units through
+    decompress_units_range (run_range then gets the unit batch of subset_units and returns per-unit
+    outputs), and on rank 0 collapse_units before DecompressPlan.splice."""
     import torch
     import torch.distributed as dist
 
+    if seams_of_container(avrc):
+        return _sharded_decompress_units(ctx, avrc, device, run_range)
     rank, world = dist.get_rank(), dist.get_world_size()
     plan = plan_decompress(avrc)
     model = container_model(avrc)

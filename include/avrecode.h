@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define AVRECODE_ABI_VERSION 6  /* 6: the parallel model's long-slice split (avr_set_split_bytes, Block field 16);
+#define AVRECODE_ABI_VERSION 7  /* 7: piece plans (avr_dec_plan_load_pieces, avr_decompress_pieces, avr_pack_pieces);
+                                 * 6: the parallel model's long-slice split (avr_set_split_bytes, Block field 16);
                                  * 5: avr_slice_desc.file_offset (96 B), dec-plan handle, ranged parse */
 
 typedef enum {
@@ -89,8 +90,10 @@ void avr_free(void* p);
  * it (its first macroblock and output byte, the CABAC re-encoder's state, the context states, the
  * upper row's neighbour fields).  Such containers decompress through the whole-file calls
  * (avr_decompress_file(s), avr_roundtrip_file(s)) and the hooks sessions (which regenerate one
- * whole at begin, as a reference-model container); the per-slice plans (avr_plan_decompress,
- * avr_dec_plan_load) refuse them with AVR_ERR_UNSUPPORTED.  split_bytes = 0: no split.  Default: the environment's AVR_SPLIT_BYTES, else 98304.  Checked by the oracle's
+ * whole at begin, as a reference-model container) and, piece by piece on any number of ranks,
+ * through the piece plans (avr_dec_plan_load_pieces, avr_decompress_pieces, avr_pack_pieces); the
+ * per-slice plans (avr_plan_decompress, avr_dec_plan_load) refuse them with AVR_ERR_UNSUPPORTED.
+ * split_bytes = 0: no split.  Default: the environment's AVR_SPLIT_BYTES, else 98304.  Checked by the oracle's
  * restatement (oracle/oracle_seams.c). */
 int avr_set_split_bytes(avr_ctx* ctx, size_t split_bytes);
 size_t avr_get_split_bytes(const avr_ctx* ctx);
@@ -384,6 +387,57 @@ int avr_dec_plan_descs(const avr_dec_plan* plan, avr_slice_desc* out);
 int avr_dec_plan_arena(const avr_dec_plan* plan, uint8_t* out, size_t cap);
 int avr_dec_plan_splice(const avr_dec_plan* plan, const int32_t* status, const uint8_t* regen, size_t regen_len,
                         const uint64_t* offsets, const uint32_t* lens, uint8_t* out, size_t out_cap, size_t* out_len);
+
+/* Piece plans: the sharded decompress of a container whose long slices were cut (avr_set_split_bytes).
+ * The unit of work is what one workgroup regenerates: a whole coded slice, or one piece of a split
+ * slice.  No reference counterpart (the reference decodes a slice as one chain, recode.cpp:1411-1520).
+ * avr_dec_plan_load_pieces loads a parallel-model container, with or without seams, into a plan
+ * handle (AVR_ERR_UNSUPPORTED for a reference- or chained-model container; every check the
+ * whole-file decompress makes on a seams field, with AVR_ERR_FORMAT).  *n_slices = the coded slices,
+ * the indexing of avr_dec_plan_descs and avr_dec_plan_splice, a split slice counting once; *n_units
+ * = the units, in container order, a split slice's pieces consecutive; *n_recs seam records of
+ * *rec_stride bytes (the device layout of the split kernels, for pictures up to 288 macroblocks wide).
+ * avr_dec_plan_units: the units' descriptors -- payload_offset / payload_size index the arena
+ * avr_dec_plan_arena writes (*arena_len bytes; each unit's stream 16-byte aligned and followed by at
+ * least 16 zero bytes), out_offset / out_capacity a work buffer of *work_len bytes (a piece's capacity
+ * = its kept bytes + 4096) -- and what each unit is of its slice.  avr_dec_plan_recs: the records.
+ * On a container without seams the units are avr_dec_plan_load's slices, descriptor for descriptor.
+ * avr_dec_plan_splice takes one (status, offset, len) per coded slice as ever: for a split slice
+ * they describe the concatenation of its pieces' kept bytes. */
+typedef struct {
+  int32_t seam;    /* record index among the plan's seam records where this unit starts; -1: the slice's own start */
+  uint32_t n_mbs;  /* macroblocks in the unit; 0: to end_of_slice (a last piece, or a whole slice) */
+  int32_t slice;   /* which of the plan's coded slices (avr_dec_plan_splice's index) the unit belongs to */
+  uint32_t keep;   /* bytes of the unit's regenerated output that are the slice's: the next cut's first
+                    * byte - this one's; UINT32_MAX: all of them (a last piece, or a whole slice) */
+} avr_piece;
+int avr_dec_plan_load_pieces(avr_dec_plan* plan, const uint8_t* avrc, size_t n, int* n_slices, int* n_units,
+                             size_t* arena_len, size_t* work_len, int* max_mb_width, int* max_mb_height,
+                             int* n_recs, size_t* rec_stride);
+int avr_dec_plan_units(const avr_dec_plan* plan, avr_slice_desc* descs, avr_piece* pieces);
+int avr_dec_plan_recs(const avr_dec_plan* plan, uint8_t* out, size_t cap);
+
+/* A batch of units that are pieces or whole progressive-frame slices of AVR_MODEL_PARALLEL (the u64
+ * coder), regenerated one workgroup per unit by the split kernel (the one avr_decompress_file runs)
+ * on `stream`: d_desc / d_in / d_out / d_res as avr_decompress_slices, pieces = the units' HOST array
+ * (seam indexes d_recs: n_recs records of rec_stride bytes in device memory; slice and keep are not
+ * read).  The array is checked on the host before anything is launched: -1 <= seam < n_recs,
+ * max_mb_width <= 288 and rec_stride no less than a record of max_mb_width columns, otherwise
+ * AVR_ERR_INVALID_ARGUMENT.  Field, MBAFF and wider slices are never cut: they go through
+ * avr_decompress_slices.  Nothing is synchronised. */
+int avr_decompress_pieces(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_piece* pieces, int n,
+                          int max_mb_width, int max_mb_height, const uint8_t* d_recs, int n_recs, size_t rec_stride,
+                          const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res, void* stream);
+/* avr_pack_outputs for units: unit k's kept bytes -- all out_len of them when d_pieces[k].keep is
+ * UINT32_MAX, else the first keep -- packed at d_packed + d_offsets[k] (d_offsets: n + 1 entries, the
+ * exclusive prefix sum of d_kept).  d_status[k] = the unit's status, or AVR_SLICE_NO_END when it
+ * regenerated fewer than keep bytes; a unit with d_status != 0 keeps nothing.  Packed this way the
+ * consecutive units of a slice are the slice's regenerated bytes without gaps, on one rank and after
+ * a rank-order concatenation.  All pointers are device pointers (d_pieces: a device copy of the
+ * avr_piece array). */
+int avr_pack_pieces(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_piece* d_pieces,
+                    const avr_slice_result* d_res, int n, const uint8_t* d_out, uint8_t* d_packed,
+                    uint64_t* d_offsets, uint32_t* d_kept, int32_t* d_status, void* stream);
 
 /* Container codec check (host only): parse a Recoded protobuf (recode.proto:1-19) with the
  * library's own wire codec -- the one avr_decompress_file uses -- and return (a) its fields as JSON,
