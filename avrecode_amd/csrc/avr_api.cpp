@@ -1,158 +1,39 @@
-// C ABI of avrecode-amd (include/avrecode.h): host orchestration around the device kernels.
+// C ABI of avrecode-amd (include/avrecode.h), the device side: the context, and the orchestration
+// of every launch around the device kernels.
 //
 //   compress file   demux + headers (avr_front.cpp) -> payload arena in HBM -> slice kernel
 //                   (one wavefront per slice) -> segmentation + Recoded protobuf
-//                   (recode.cpp:1102-1132, 1275-1297)
-//   decompress file Recoded -> literal + surrogate stream (recode.cpp:1359-1409, 1527-1544) ->
-//                   headers -> slice kernel -> last-byte patch (recode.cpp:1345-1356)
+//                   (avr_assemble.cpp; recode.cpp:1102-1132, 1275-1297)
+//   decompress file Recoded -> literal + surrogate stream (avr_plan.cpp; recode.cpp:1359-1409,
+//                   1527-1544) -> headers -> slice kernel -> last-byte patch (recode.cpp:1345-1356)
 //
-// The hot path has no host implementation: without a GPU every entry point fails with
+// The host-only entry points (plans, assembly, stream parse) live in avr_plan.cpp and
+// avr_assemble.cpp, the seams codec in avr_seams.cpp, the libavcodec-hooks surface in avr_hooks.cpp.
+// The hot path has no host implementation: without a GPU every entry point here fails with
 // AVR_ERR_DEVICE.
 #include <hip/hip_runtime.h>
-#include <sys/mman.h>
 
 #include <algorithm>
 #include <array>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <memory>
-#include <mutex>
-#include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include <zlib.h>
-
 #include "../../include/avrecode.h"
+#include "avr_ctx.h"
 #include "avr_engine.h"
-#include "avr_front.h"
 #include "avr_synth.h"
-#include "avr_kernels.h"
 #include "h264_tables.h"
 
-namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  // zero: a fresh allocation starts zeroed (the estimator tables rely on it, see kEstLogN)
-  hipError_t reserve(size_t n, bool zero = false) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, n);
-    if (e == hipSuccess && zero) e = hipMemset(p, 0, n);
-    if (e == hipSuccess && zero) e = hipDeviceSynchronize();
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  ~DevBuf() { release(); }
-  template <class T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-}  // namespace
-
-struct avr_ctx {
-  int device = 0;
-  std::string err;
-  hipStream_t stream = nullptr;
-  DevBuf tables, est, frames, frame_meta, in, out, descs, res, packed, offsets, order;
-  DevBuf queue;                                          // largest-first slice queue (launch_slices)
-  DevBuf rm_goff, rm_counts, rm_stop, rm_off, rm_ops;   // parallel reference-model compress
-  DevBuf regen, dec_descs, res_d, verdict;               // compress-side roundtrip check
-  DevBuf file_first, file_op_off;                        // reference model over several files
-  // the parallel model's long-slice split (split_compress / split_decompress): its own stream, so the
-  // long slices' first pass overlaps the rest of the batch, and its own estimator scratch
-  hipStream_t split_stream = nullptr;
-  DevBuf sp_in, sp_out, sp_descs, sp_res, sp_ctl, sp_recs, sp_snapn, sp_est, sp_in2, sp_out2;
-  size_t split_bytes = 0;   // avr_set_split_bytes / AVR_SPLIT_BYTES (0: no split)
-  // avr_decompress_pieces: the batch's PieceCtl array, host (alive while its upload is in flight) and device
-  std::vector<avr::PieceCtl> pc_host;
-  DevBuf pc_ctl;
-  // a batch holding both progressive and field slices runs its field kernel beside the progressive
-  // one (avr::FieldLane); AVR_FIELD_LANE=0 keeps the two in one stream, one after the other
-  hipStream_t fld_stream = nullptr;
-  hipEvent_t fld_ev[2] = {nullptr, nullptr};
-  avr::FieldLane field_lane() const {
-    avr::FieldLane l;
-    if (fld_stream) l.stream = fld_stream, l.fork = fld_ev[0], l.join = fld_ev[1];
-    return l;
-  }
-  bool round_robin = false;   // placement probe passed: the CU schedule (order) may be used
-  int* order_or_null() { return round_robin ? order.as<int>() : nullptr; }
-  // phase breakdown of the current / last whole-file call (avr_phase_times): run_plan adds the
-  // device phases (HIP events ev[0..3] around its uploads, kernels and downloads) and its own wall
-  // time (plan_wall); the file paths add the host phases
-  avr_phase_times phase{};
-  double plan_wall = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~avr_ctx() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (split_stream) (void)hipStreamDestroy(split_stream);
-    for (auto& e : fld_ev)
-      if (e) (void)hipEventDestroy(e);
-    if (fld_stream) (void)hipStreamDestroy(fld_stream);
-  }
-};
+using namespace avr_host;
 
 namespace {
 
-// Model modes (include/avrecode.h): the reference model, and the parallel model on the reference's
-// arithmetic_code<uint64_t, uint8_t> (PARALLEL) or on the optional 32-bit P32 coder (PARALLEL32).
-bool valid_model(int m) {
-  return m == AVR_MODEL_REFERENCE || m == AVR_MODEL_PARALLEL || m == AVR_MODEL_PARALLEL32 || m == AVR_MODEL_CHAINED;
-}
-bool parallel_model(int m) { return m == AVR_MODEL_PARALLEL || m == AVR_MODEL_PARALLEL32; }
-// the reference model over a whole file, or in chains of AVR_CHAIN_SLICES coded slices
-bool reference_model(int m) { return m == AVR_MODEL_REFERENCE || m == AVR_MODEL_CHAINED; }
-// models whose per-slice outputs come from several ranks and are assembled on one: the parallel
-// models (slice ranges) and the chained model (chain ranges); the reference model is one unit
-bool assemblable(int m) { return parallel_model(m) || m == AVR_MODEL_CHAINED; }
-uint32_t coder_flag(int m) { return m == AVR_MODEL_PARALLEL32 ? avr::kFlagP32 : 0u; }
-constexpr size_t kLdsBudget = 160 * 1024;   // LDS per workgroup (one slice) on gfx950
 constexpr uint64_t kMaxSynthBytes = (uint64_t)1 << 35;   // avr_synthesize_stream's output cap (32 GiB)
-
-int fail(avr_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  return code;
-}
-// No C++ exception crosses the C ABI: the entry points that build host containers run their body
-// through guarded(), which turns an allocation failure into AVR_ERR_OUT_OF_MEMORY.
-template <class F>
-int guarded(avr_ctx* c, F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return fail(c, AVR_ERR_OUT_OF_MEMORY, "host allocation failed");
-  } catch (const std::exception& e) {
-    return fail(c, AVR_ERR_DEVICE, std::string("internal error: ") + e.what());
-  }
-}
-#define HIP_TRY(c, expr)                                                                              \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess) return fail(c, AVR_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(_e)); \
-  } while (0)
 
 // Engine tables: FFmpeg-layout CABAC tables, (m,n) init, exact reciprocals for the recoded
 // coder's (range/(pos+neg)) and the model's neighbour geometry.
@@ -275,92 +156,6 @@ bool check_reciprocals(const avr::EngineTables& t) {
     }
   }
   return true;
-}
-
-// A byte vector whose resize() leaves new bytes uninitialised (multi-GB buffers that are written
-// right after: no memset pass first).
-template <class T>
-struct DefaultInit : std::allocator<T> {
-  template <class U>
-  struct rebind {
-    using other = DefaultInit<U>;
-  };
-  DefaultInit() = default;
-  template <class U>
-  DefaultInit(const DefaultInit<U>&) {}
-  template <class U>
-  void construct(U* p) {
-    ::new ((void*)p) U;
-  }
-  template <class U, class... A>
-  void construct(U* p, A&&... a) {
-    ::new ((void*)p) U(std::forward<A>(a)...);
-  }
-};
-typedef std::vector<uint8_t, DefaultInit<uint8_t>> Bytes;
-
-struct Plan {
-  std::vector<avr_slice_desc> descs;
-  Bytes arena;   // payloads (compress) or recoded streams (decompress)
-  // decompress_setup with layout_only: the arena is not built; its byte copies are listed in
-  // arena_copies (dst in the arena, source in the container) and its length in arena_end
-  bool layout_only = false;
-  std::vector<avr::PbCopy> arena_copies;
-  uint64_t arena_end = 0;
-  int max_w = 1;
-  // sequential (reference-model) plans over several files: file f is descs[file_first[f] ..
-  // file_first[f + 1]); empty = one file
-  std::vector<int> file_first;
-  int n_files() const { return file_first.empty() ? 1 : (int)file_first.size() - 1; }
-  int file_begin(int f) const { return file_first.empty() ? 0 : file_first[f]; }
-  int file_end(int f) const { return file_first.empty() ? (int)descs.size() : file_first[f + 1]; }
-  // field pictures / MBAFF frames present: launches add the field-capable kernels (kFlagFields)
-  bool fields() const {
-    for (const auto& d : descs)
-      if (d.structure != AVR_STRUCT_FRAME) return true;
-    return false;
-  }
-  // both kinds of slice: the field kernel has work beside the progressive one (avr::FieldLane)
-  bool mixed() const {
-    bool f = false, p = false;
-    for (const auto& d : descs) (d.structure != AVR_STRUCT_FRAME ? f : p) = true;
-    return f && p;
-  }
-};
-
-template <class V>
-void append_aligned(V* arena, const uint8_t* p, size_t n, size_t extra, uint64_t* off) {
-  size_t o = (arena->size() + 15) & ~(size_t)15;
-  arena->resize(o + n + extra, 0);
-  if (n) memcpy(arena->data() + o, p, n);
-  *off = o;
-}
-
-// EdgeRec slots of the LDS ring a slice needs (launch max_mb_width): an MBAFF slice keeps its pair
-// edges and records there too (Walker::pair_edge)
-int ring_cols(const avr_slice_desc& d) { return d.structure == AVR_STRUCT_MBAFF ? 3 * d.mb_width + 7 : d.mb_width; }
-
-avr_slice_desc desc_from_header(const avr::SliceInfo& s) {
-  avr_slice_desc d;
-  memset(&d, 0, sizeof(d));
-  d.slice_type = s.h.slice_type == 3 ? 0 : s.h.slice_type == 4 ? 2 : s.h.slice_type;
-  d.slice_qp = s.h.slice_qp;
-  d.cabac_init_idc = s.h.cabac_init_idc;
-  d.first_mb = s.h.first_mb;
-  d.mb_width = s.h.mb_width;
-  d.mb_height = s.h.mb_height;
-  d.num_ref_idx_l0 = s.h.num_ref_idx[0];
-  d.num_ref_idx_l1 = s.h.num_ref_idx[1];
-  d.chroma_array_type = s.h.chroma_array_type;
-  d.transform_8x8_mode = s.h.transform_8x8_mode;
-  d.direct_8x8_inference = s.h.direct_8x8_inference;
-  d.x264_build = s.h.x264_build;
-  d.picture_id = s.picture_id;
-  d.coded = 1;
-  d.file_offset = ~(uint64_t)0;
-  d.structure = s.h.field_pic ? (s.h.bottom_field ? AVR_STRUCT_BOTTOM_FIELD : AVR_STRUCT_TOP_FIELD)
-              : s.h.mbaff ? AVR_STRUCT_MBAFF : AVR_STRUCT_FRAME;
-  return d;
 }
 
 constexpr int kRModeFallback = 1;
@@ -517,110 +312,8 @@ hipError_t reserve_parallel(avr_ctx* c, int n, int max_w, bool field_lane = fals
   return e;
 }
 
-// Upload plan, run the slice kernel over it (one launch, see launch_slices), download results and outputs.
-// verify (parallel compress only): also decompress every slice's output on the device, apply the
-// last-byte rule and compare with the payload (avr_roundtrip_slices); a slice whose output does not
-// regenerate its payload gets status kStatusNoRoundtrip, so no container ever holds a block that
-// cannot be decompressed.
+// a slice whose compress output does not regenerate its payload (run_plan's verify)
 constexpr int32_t kStatusNoRoundtrip = AVR_SLICE_NO_ROUNDTRIP;
-// out_host: a std::vector<uint8_t> or a Bytes (not zero-filled first: the download overwrites it)
-template <class HostBuf>
-int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_slice_result>* res,
-             HostBuf* out_host, bool verify = false, uint32_t flags = 0) {
-  const int n = (int)plan.descs.size();
-  if (plan.fields()) flags |= avr::kFlagFields;
-  // a parallel batch of progressive and field slices: the two kernels side by side
-  const avr::FieldLane lane = !sequential && plan.mixed() ? c->field_lane() : avr::FieldLane();
-  res->assign(n, avr_slice_result{0, 0, 0, 0, {0, 0, 0, 0, 0, 0}});
-  uint64_t out_total = 0;
-  for (auto& d : plan.descs) {
-    d.out_offset = out_total;
-    out_total += ((uint64_t)d.out_capacity + 15) & ~15ull;
-  }
-  out_host->resize(out_total);
-  if (!n) return AVR_OK;
-  const double t_wall = now_s();
-  HIP_TRY(c, c->in.reserve(plan.arena.size() + 4096));
-  HIP_TRY(c, c->out.reserve(out_total + 4096));
-  HIP_TRY(c, c->descs.reserve(sizeof(avr_slice_desc) * n));
-  HIP_TRY(c, c->res.reserve(sizeof(avr_slice_result) * n));
-  for (auto& e : c->ev)
-    if (!e) HIP_TRY(c, hipEventCreate(&e));
-  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->in.p, plan.arena.data(), plan.arena.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->descs.p, plan.descs.data(), sizeof(avr_slice_desc) * n, hipMemcpyHostToDevice,
-                            c->stream));
-  HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
-  int rm = kRModeFallback;
-  if (sequential && mode == 0 && !getenv("AVR_RMODE_SEQUENTIAL") && rmode_parallel_pays(plan)) {
-    rm = run_rmode_compress(c, plan, out_total, flags);
-    if (rm < 0) return rm;
-  }
-  if (sequential && rm == AVR_OK) {
-    // done: the parallel reference-model compress
-  } else if (sequential) {
-    // one workgroup per file (the reference model is sequential within a file only)
-    const int nf = plan.n_files();
-    avr::SeqFiles sf;
-    sf.n_files = nf;
-    size_t fbytes = 0;
-    for (auto& d : plan.descs) fbytes = std::max(fbytes, (size_t)2 * d.mb_width * d.mb_height * 52);
-    sf.frame_stride = (fbytes + 255) & ~(size_t)255;
-    HIP_TRY(c, c->est.reserve(sizeof(uint16_t) * avr::kEstGlobal * (size_t)nf, true));
-    HIP_TRY(c, c->frames.reserve(sf.frame_stride * nf + 64));
-    HIP_TRY(c, c->frame_meta.reserve(sizeof(int) * (size_t)nf + 64));
-    if (!plan.file_first.empty()) {
-      HIP_TRY(c, c->file_first.reserve(sizeof(int) * plan.file_first.size()));
-      HIP_TRY(c, hipMemcpyAsync(c->file_first.p, plan.file_first.data(), sizeof(int) * plan.file_first.size(),
-                                hipMemcpyHostToDevice, c->stream));
-      sf.file_first = c->file_first.as<int>();
-    }
-    HIP_TRY(c, avr::launch_slices(mode, true, c->tables.as<avr::EngineTables>(), c->descs.as<avr_slice_desc>(), n,
-                                  plan.max_w, c->in.as<uint8_t>(), c->out.as<uint8_t>(), c->res.as<avr_slice_result>(),
-                                  c->est.as<uint16_t>(), c->frames.as<uint8_t>(), c->frame_meta.as<int>(), nullptr,
-                                  c->stream, sf, flags));
-  } else {
-    HIP_TRY(c, reserve_parallel(c, n, plan.max_w, lane.stream != nullptr));
-    HIP_TRY(c, avr::launch_slices(mode, false, c->tables.as<avr::EngineTables>(), c->descs.as<avr_slice_desc>(), n,
-                                  plan.max_w, c->in.as<uint8_t>(), c->out.as<uint8_t>(), c->res.as<avr_slice_result>(),
-                                  c->est.as<uint16_t>(), nullptr, nullptr, c->order_or_null(), c->stream,
-                                  avr::SeqFiles(), flags, c->queue.p, &lane));
-  }
-  std::vector<int32_t> verdict;
-  if (verify && mode == 0 && !sequential) {
-    HIP_TRY(c, c->regen.reserve(plan.arena.size() + 4096));
-    HIP_TRY(c, c->dec_descs.reserve(sizeof(avr_slice_desc) * n));
-    HIP_TRY(c, c->res_d.reserve(sizeof(avr_slice_result) * n));
-    HIP_TRY(c, c->verdict.reserve(sizeof(int32_t) * n));
-    avr_slice_desc* dd = c->dec_descs.as<avr_slice_desc>();
-    avr_slice_result* rd = c->res_d.as<avr_slice_result>();
-    HIP_TRY(c, avr::launch_derive_decompress(c->descs.as<avr_slice_desc>(), c->res.as<avr_slice_result>(), n, dd,
-                                             c->stream));
-    HIP_TRY(c, avr::launch_slices(1, false, c->tables.as<avr::EngineTables>(), dd, n, plan.max_w, c->out.as<uint8_t>(),
-                                  c->regen.as<uint8_t>(), rd, c->est.as<uint16_t>(), nullptr, nullptr,
-                                  c->order_or_null(), c->stream, avr::SeqFiles(),
-                                  (plan.fields() ? avr::kFlagFields : 0u) | (flags & avr::kFlagP32), c->queue.p,
-                                  &lane));
-    HIP_TRY(c, avr::launch_verify(c->descs.as<avr_slice_desc>(), c->res.as<avr_slice_result>(), rd, n,
-                                  c->in.as<uint8_t>(), c->regen.as<uint8_t>(), c->verdict.as<int32_t>(), c->stream));
-    verdict.resize(n);
-    HIP_TRY(c, hipMemcpyAsync(verdict.data(), c->verdict.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
-  HIP_TRY(c, hipMemcpyAsync(res->data(), c->res.p, sizeof(avr_slice_result) * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(out_host->data(), c->out.p, out_total, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  float ms[3] = {0, 0, 0};
-  for (int i = 0; i < 3; i++) HIP_TRY(c, hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
-  c->phase.upload_s += 1e-3 * ms[0];
-  c->phase.kernel_s += 1e-3 * ms[1];
-  c->phase.download_s += 1e-3 * ms[2];
-  c->plan_wall += now_s() - t_wall;
-  for (int k = 0; k < (int)verdict.size(); k++)
-    if ((*res)[k].status == 0 && verdict[k] != 1) (*res)[k].status = kStatusNoRoundtrip;
-  return AVR_OK;
-}
 
 // ------------------------------------------------------------------------ the long-slice split
 // The parallel model (on arithmetic_code<uint64_t, uint8_t>) cuts a long progressive slice at
@@ -636,9 +329,9 @@ int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_
 //   - Block field 16 ("seams", zlib) carries, per cut, what the piece after it needs: its first
 //     macroblock, its first output byte q, the re-encoder state, the CABAC contexts, last_dqp_nz
 //     and the upper row's edges (the parse's neighbour fields).
-// Compress takes the long slices through the split kernels twice (avr_k_split.hip): the cut scan --
-// the CABAC parse of each whole slice alone (a trace walk without output: no model, one wave),
-// recording the candidates, on its own stream beside the rest of the batch -- then the pieces (a
+// Compress takes the long slices through the split kernel once (avr_k_split.hip, mode 0), on its
+// own stream beside the rest of the batch: each whole slice is cut as it is walked -- the cut
+// records, the pieces' streams one after the other and their ends come out of that single walk (a
 // slice without a cut: one piece).  Decompress runs the pieces side by side and splices them: piece
 // i's bytes up to cut i's q.
 constexpr size_t kSplitBytesDefault = 98304;
@@ -648,148 +341,18 @@ bool split_candidate(const avr_slice_desc& d, size_t split_bytes) {
          d.mb_width <= avr::kMringCols && 2 * (uint64_t)d.payload_size >= 3 * (uint64_t)split_bytes;
 }
 
-struct SeamCe {
-  uint32_t q, low, outstanding, cache, range;
-  int32_t queue;
+// The two timing events around a split launch, owned by the job they time: destroyed with it on
+// every path out, the failed ones included.
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
 };
-// The re-encoder where the decoder stands after bitpos bits with codIOffset `offset` (the oracle's
-// avr_seam_encoder): m = (bitpos - 10) / 8 whole bytes have left the window; the last byte of L
-// below m that is not 0xFF (q) is the cache, the 0xFF bytes after it outstanding, the rest in low.
-bool seam_encoder(const uint8_t* pay, size_t n, uint64_t bitpos, uint32_t offset, uint32_t range, SeamCe* s) {
-  if (bitpos < 26) return false;
-  const uint64_t m = (bitpos - 10) / 8, sb = m > 12 ? m - 12 : 0, e = (bitpos + 7) / 8;
-  unsigned __int128 x = 0;
-  for (uint64_t j = sb; j < e; j++) x = x << 8 | (j < n ? pay[j] : 0);
-  x >>= 8 * e - bitpos;
-  if (x < offset) return false;
-  const unsigned __int128 y = x - offset;
-  for (uint64_t j = m; j-- > sb;) {
-    const uint32_t b = (uint32_t)(y >> (bitpos - 8 * j - 8)) & 0xff;
-    if (b == 0xff) continue;
-    const unsigned lowbits = (unsigned)(bitpos - 8 * m);
-    s->q = (uint32_t)j;
-    s->cache = b;
-    s->outstanding = (uint32_t)(m - 1 - j);
-    s->low = (uint32_t)(y & (((unsigned __int128)1 << lowbits) - 1));
-    s->queue = (int32_t)lowbits - 18;
-    s->range = range;
-    return true;
-  }
-  return false;
-}
-
-void put_le32(std::vector<uint8_t>* o, uint32_t v) {
-  for (int k = 0; k < 4; k++) o->push_back((uint8_t)(v >> (8 * k)));
-}
-uint32_t get_le32(const uint8_t* p) {
-  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
-
-// The slice's initial context states (9.3.1.1), as init_slice_state sets them on the device.
-void cabac_init_states(const avr_slice_desc& d, uint8_t out[1024]) {
-  const int qp = d.slice_qp < 0 ? 0 : d.slice_qp > 51 ? 51 : d.slice_qp;
-  for (int c = 0; c < 1024; c++) {
-    int m, n;
-    avr::mn_for_ctx(d.slice_type == 2 ? -1 : d.cabac_init_idc, c, &m, &n);
-    int pre = ((m * qp) >> 4) + n;
-    pre = pre < 1 ? 1 : pre > 126 ? 126 : pre;
-    out[c] = pre <= 63 ? (uint8_t)((63 - pre) << 1) : (uint8_t)(((pre - 64) << 1) | 1);
-  }
-}
-// an upper-row edge byte as the seams field keeps it: what the parse of the row below reads of it --
-// nnz only as nonzero (coded_block_flag's context), |mvd| only up to 33 (absMvdComp's sum against
-// 3 and 32)
-uint8_t edge_norm(int j, uint8_t b) {
-  if (j >= 4 && j < 16) return b != 0;
-  if (j >= 16 && j < 32) return b > 33 ? 33 : b;
-  return b;
-}
-
-// Block field 16: u32 raw length, then zlib (level 9) of { u32 2, u32 cuts, u32 mb_width,
-// u32 piece_len[cuts + 1], per cut { u32 first_mb, q, last_dqp_nz, ce_low, ce_queue,
-// ce_outstanding, ce_cache, ce_range, u8 state[1024] XOR the slice's initial states, u8 edges
-// byte-major (byte j of every column, j = 0..39; edge_norm) } } (little-endian)
-bool seams_encode(const std::vector<const avr::SeamRec*>& recs, const std::vector<SeamCe>& ce, const avr_slice_desc& d,
-                  const std::vector<uint32_t>& piece_len, std::vector<uint8_t>* out) {
-  const int mb_width = d.mb_width;
-  uint8_t init[1024];
-  cabac_init_states(d, init);
-  std::vector<uint8_t> raw;
-  put_le32(&raw, 2);
-  put_le32(&raw, (uint32_t)recs.size());
-  put_le32(&raw, (uint32_t)mb_width);
-  for (uint32_t l : piece_len) put_le32(&raw, l);
-  for (size_t i = 0; i < recs.size(); i++) {
-    put_le32(&raw, recs[i]->first_mb);
-    put_le32(&raw, ce[i].q);
-    put_le32(&raw, recs[i]->last_dqp_nz);
-    put_le32(&raw, ce[i].low);
-    put_le32(&raw, (uint32_t)ce[i].queue);
-    put_le32(&raw, ce[i].outstanding);
-    put_le32(&raw, ce[i].cache);
-    put_le32(&raw, ce[i].range);
-    for (int c = 0; c < 1024; c++) raw.push_back((uint8_t)(recs[i]->state[c] ^ init[c]));
-    const uint8_t* e = (const uint8_t*)(recs[i] + 1);
-    for (int j = 0; j < avr::kEdgeBytes; j++)
-      for (int c = 0; c < mb_width; c++) raw.push_back(edge_norm(j, e[(size_t)avr::kEdgeBytes * c + j]));
-  }
-  uLongf zl = compressBound(raw.size());
-  out->assign(4 + zl, 0);
-  if (compress2(out->data() + 4, &zl, raw.data(), raw.size(), 9) != Z_OK) return false;
-  out->resize(4 + zl);
-  for (int k = 0; k < 4; k++) (*out)[k] = (uint8_t)(raw.size() >> (8 * k));
-  return true;
-}
-
-// the pieces of a split block: per cut a device record (decompress fields), the pieces' streams
-struct SeamsDecoded {
-  int cuts = 0;
-  std::vector<uint32_t> piece_len, first_mb, q;
-  std::vector<uint8_t> recs;   // cuts records of rec_stride bytes
-};
-bool seams_decode(const uint8_t* p, size_t n, const avr_slice_desc& d, size_t rec_stride, SeamsDecoded* sd) {
-  const int mb_width = d.mb_width;
-  uint8_t init[1024];
-  cabac_init_states(d, init);
-  if (n < 4) return false;
-  const uint32_t rl = get_le32(p);
-  if (rl < 12 || rl > (1u << 30)) return false;
-  std::vector<uint8_t> raw(rl);
-  uLongf got = rl;
-  if (uncompress(raw.data(), &got, p + 4, n - 4) != Z_OK || got != rl || get_le32(raw.data()) != 2) return false;
-  const uint32_t k = get_le32(raw.data() + 4), w = get_le32(raw.data() + 8);
-  const size_t per = 32 + 1024 + (size_t)avr::kEdgeBytes * w;
-  if ((int)w != mb_width || k == 0 || k > 65536 || 12 + 4 * ((size_t)k + 1) + per * k != rl) return false;
-  sd->cuts = (int)k;
-  const uint8_t* q = raw.data() + 12;
-  sd->piece_len.resize(k + 1);
-  for (uint32_t i = 0; i <= k; i++, q += 4) sd->piece_len[i] = get_le32(q);
-  sd->recs.assign((size_t)k * rec_stride, 0);
-  sd->first_mb.resize(k);
-  sd->q.resize(k);
-  for (uint32_t i = 0; i < k; i++, q += per) {
-    avr::SeamRec* r = (avr::SeamRec*)(sd->recs.data() + (size_t)i * rec_stride);
-    r->first_mb = sd->first_mb[i] = get_le32(q);
-    sd->q[i] = get_le32(q + 4);
-    r->last_dqp_nz = get_le32(q + 8);
-    r->ce_low = get_le32(q + 12);
-    r->ce_queue = (int32_t)get_le32(q + 16);
-    r->ce_outstanding = get_le32(q + 20);
-    r->ce_cache = get_le32(q + 24);
-    r->ce_range = get_le32(q + 28);
-    // a cut's state is what seam_encoder can produce: the window 12 bytes deep at most
-    if (r->ce_queue < -8 || r->ce_queue > -1 || r->ce_cache > 0xff || r->ce_range < 256 || r->ce_range > 510 ||
-        r->ce_low >= (1u << (r->ce_queue + 18)) || r->ce_outstanding > 12 || (i && sd->q[i] <= sd->q[i - 1]) ||
-        (i && sd->first_mb[i] <= sd->first_mb[i - 1]) || sd->first_mb[i] % w ||
-        sd->first_mb[i] >= (uint32_t)w * (uint32_t)std::max(1, d.mb_height))
-      return false;
-    for (int c = 0; c < 1024; c++) r->state[c] = (uint8_t)(q[32 + c] ^ init[c]);
-    uint8_t* e = (uint8_t*)(r + 1);
-    for (int j = 0; j < avr::kEdgeBytes; j++)
-      for (uint32_t c = 0; c < w; c++) e[(size_t)avr::kEdgeBytes * c + j] = q[32 + 1024 + (size_t)j * w + c];
-  }
-  return true;
-}
 
 // Compress of the long slices, in two calls around the rest of the batch: begin uploads them and
 // launches the split compress on the split stream (each slice cut as it is walked: the records,
@@ -810,7 +373,7 @@ struct SplitJob {
   size_t stride = 0;
   int max_w = 1;
   uint32_t flags = 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EventPair ev;   // around the split compress kernel
 };
 
 int split_begin(avr_ctx* c, SplitJob* j, size_t split_bytes, uint32_t flags) {
@@ -829,8 +392,7 @@ int split_begin(avr_ctx* c, SplitJob* j, size_t split_bytes, uint32_t flags) {
     d.read_limit = (uint32_t)s.read_limit;
     const uint32_t cap = (uint32_t)(8ull * s.size / j->split_bits) + 1;
     d.out_capacity = (uint32_t)(s.size * 2 + 256 + 64 * (size_t)cap);
-    d.out_offset = j->out_total;
-    j->out_total += ((uint64_t)d.out_capacity + 15) & ~15ull;
+    place_output(&d, &j->out_total);
     j->max_w = std::max(j->max_w, d.mb_width);
     j->ctl[k] = avr::PieceCtl{-1, 0, (int32_t)j->nrec, cap};
     j->nrec += cap;
@@ -845,8 +407,8 @@ int split_begin(avr_ctx* c, SplitJob* j, size_t split_bytes, uint32_t flags) {
   HIP_TRY(c, c->sp_recs.reserve(j->stride * j->nrec + 64));
   HIP_TRY(c, c->sp_snapn.reserve(sizeof(uint32_t) * ((size_t)n + j->nrec)));
   HIP_TRY(c, c->sp_est.reserve(sizeof(uint16_t) * (size_t)avr::kEstGlobal * std::max(1, grid), true));
-  HIP_TRY(c, hipEventCreate(&j->e0));
-  HIP_TRY(c, hipEventCreate(&j->e1));
+  HIP_TRY(c, hipEventCreate(&j->ev.e0));
+  HIP_TRY(c, hipEventCreate(&j->ev.e1));
   hipStream_t st = c->split_stream;
   HIP_TRY(c, hipMemcpyAsync(c->sp_in.p, j->arena.data(), j->arena.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(c->sp_descs.p, j->d.data(), sizeof(avr_slice_desc) * n, hipMemcpyHostToDevice, st));
@@ -859,11 +421,11 @@ int split_begin(avr_ctx* c, SplitJob* j, size_t split_bytes, uint32_t flags) {
   sa.split_bits = j->split_bits;
   sa.snap_n = c->sp_snapn.as<uint32_t>();
   sa.piece_end = sa.snap_n + n;
-  HIP_TRY(c, hipEventRecord(j->e0, st));
+  HIP_TRY(c, hipEventRecord(j->ev.e0, st));
   HIP_TRY(c, avr::launch_split(0, c->tables.as<avr::EngineTables>(), c->sp_descs.as<avr_slice_desc>(), n, j->max_w,
                                c->sp_in.as<uint8_t>(), c->sp_out.as<uint8_t>(), c->sp_res.as<avr_slice_result>(),
                                c->sp_est.as<uint16_t>(), sa, j->flags, st));
-  HIP_TRY(c, hipEventRecord(j->e1, st));
+  HIP_TRY(c, hipEventRecord(j->ev.e1, st));
   return AVR_OK;
 }
 
@@ -873,7 +435,7 @@ int split_begin(avr_ctx* c, SplitJob* j, size_t split_bytes, uint32_t flags) {
 // (The downloads wait for split_wait: a copy into pageable host memory would block the host until
 // the kernel before it is done, and with it the launches meant to run beside it.)
 struct SplitPending {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EventPair ev;   // around the pieces kernel; e0 set: a launch is in flight
   void* res = nullptr;
   void* out = nullptr;
   const void* res_dev = nullptr;
@@ -882,17 +444,14 @@ struct SplitPending {
 };
 bool split_timing() { return getenv("AVR_SPLIT_TIMING") != nullptr; }
 int split_wait(avr_ctx* c, SplitPending* pend) {
-  if (!pend->e0) return AVR_OK;
+  if (!pend->ev.e0) return AVR_OK;
   HIP_TRY(c, hipStreamSynchronize(c->split_stream));
   HIP_TRY(c, hipMemcpy(pend->res, pend->res_dev, pend->res_bytes, hipMemcpyDeviceToHost));
   HIP_TRY(c, hipMemcpy(pend->out, pend->out_dev, pend->out_bytes, hipMemcpyDeviceToHost));
   float ms = 0;
-  HIP_TRY(c, hipEventElapsedTime(&ms, pend->e0, pend->e1));
+  HIP_TRY(c, hipEventElapsedTime(&ms, pend->ev.e0, pend->ev.e1));
   if (split_timing()) fprintf(stderr, "split: pieces kernel %.3f s\n", 1e-3 * ms);
   c->phase.kernel_s += 1e-3 * ms;
-  (void)hipEventDestroy(pend->e0);
-  (void)hipEventDestroy(pend->e1);
-  pend->e0 = pend->e1 = nullptr;
   return AVR_OK;
 }
 int split_launch(avr_ctx* c, int mode, std::vector<avr_slice_desc>& d, const std::vector<avr::PieceCtl>& ctl,
@@ -900,10 +459,7 @@ int split_launch(avr_ctx* c, int mode, std::vector<avr_slice_desc>& d, const std
                  Bytes* out, DevBuf* out_dev, SplitPending* pending = nullptr) {
   const int n = (int)d.size();
   uint64_t total = 0;
-  for (auto& x : d) {
-    x.out_offset = total;
-    total += ((uint64_t)x.out_capacity + 15) & ~15ull;
-  }
+  for (auto& x : d) place_output(&x, &total);
   res->assign(n, avr_slice_result{});
   out->resize(total);
   if (!n) return AVR_OK;
@@ -921,13 +477,13 @@ int split_launch(avr_ctx* c, int mode, std::vector<avr_slice_desc>& d, const std
   sa.rec_stride = (uint32_t)stride;
   SplitPending local;
   SplitPending* pend = pending ? pending : &local;
-  HIP_TRY(c, hipEventCreate(&pend->e0));
-  HIP_TRY(c, hipEventCreate(&pend->e1));
-  HIP_TRY(c, hipEventRecord(pend->e0, st));
+  HIP_TRY(c, hipEventCreate(&pend->ev.e0));
+  HIP_TRY(c, hipEventCreate(&pend->ev.e1));
+  HIP_TRY(c, hipEventRecord(pend->ev.e0, st));
   HIP_TRY(c, avr::launch_split(mode, c->tables.as<avr::EngineTables>(), c->sp_descs.as<avr_slice_desc>(), n, max_w,
                                in_dev, out_dev->as<uint8_t>(), c->sp_res.as<avr_slice_result>(), c->sp_est.as<uint16_t>(),
                                sa, flags, st));
-  HIP_TRY(c, hipEventRecord(pend->e1, st));
+  HIP_TRY(c, hipEventRecord(pend->ev.e1, st));
   pend->res = res->data();
   pend->res_dev = c->sp_res.p;
   pend->res_bytes = sizeof(avr_slice_result) * n;
@@ -935,31 +491,6 @@ int split_launch(avr_ctx* c, int mode, std::vector<avr_slice_desc>& d, const std
   pend->out_dev = out_dev->p;
   pend->out_bytes = total;
   return pending ? AVR_OK : split_wait(c, pend);
-}
-
-// the regenerated bytes of a split slice: piece i's bytes up to cut i's q (the cut's first byte),
-// the last piece whole; false if a piece failed or came out short
-bool splice_pieces(const std::vector<const uint8_t*>& p, const std::vector<uint32_t>& len,
-                   const std::vector<int32_t>& status, const std::vector<uint32_t>& q, std::vector<uint8_t>* o) {
-  o->clear();
-  for (size_t i = 0; i < p.size(); i++) {
-    if (status[i]) return false;
-    const size_t start = i ? q[i - 1] : 0;
-    if (o->size() != start) return false;
-    size_t keep = len[i];
-    if (i < q.size()) {
-      if (q[i] < start || q[i] - start > len[i]) return false;
-      keep = q[i] - start;
-    }
-    o->insert(o->end(), p[i], p[i] + keep);
-  }
-  return true;
-}
-// recode.cpp:1345-1356 on a regenerated slice (before it: the trailing 0x80 already dropped)
-void last_byte_patch(std::vector<uint8_t>* o, const uint8_t* payload, size_t size) {
-  if (size <= 1) return;
-  if ((int)(size & 1) != (int)(o->size() & 1)) o->push_back(payload[size - 1]);
-  else if (!o->empty()) o->back() = payload[size - 1];
 }
 
 int split_finish(avr_ctx* c, SplitJob* j, bool verify, std::vector<SplitOut>* out) {
@@ -977,12 +508,9 @@ int split_finish(avr_ctx* c, SplitJob* j, bool verify, std::vector<SplitOut>* ou
   HIP_TRY(c, hipMemcpyAsync(recs.data(), c->sp_recs.p, recs.size(), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   float ms = 0;
-  HIP_TRY(c, hipEventElapsedTime(&ms, j->e0, j->e1));
+  HIP_TRY(c, hipEventElapsedTime(&ms, j->ev.e0, j->ev.e1));
   if (split_timing()) fprintf(stderr, "split: compress kernel %.3f s (%d slices)\n", 1e-3 * ms, n);
   c->phase.kernel_s += 1e-3 * ms;
-  (void)hipEventDestroy(j->e0);
-  (void)hipEventDestroy(j->e1);
-  j->e0 = j->e1 = nullptr;
   const uint32_t* piece_end = cnt.data() + n;
   // 2) every cut checked against the host's restatement (seam_encoder), the pieces' lengths
   std::vector<std::vector<const avr::SeamRec*>> cuts(n);
@@ -1075,383 +603,6 @@ int split_finish(avr_ctx* c, SplitJob* j, bool verify, std::vector<SplitOut>* ou
     if (so.status || cuts[k].empty()) continue;
     if (!seams_encode(cuts[k], ces[k], j->d[k], plen[k], &so.seams)) return fail(c, AVR_ERR_DEVICE, "zlib failed");
   }
-  return AVR_OK;
-}
-
-struct ParsedFile {
-  std::vector<avr::SliceInfo> slices;
-};
-
-// views: slices without emulation-prevention bytes point into `in` instead of holding a copy (the
-// caller keeps `in` alive while it uses pf)
-int parse_file(avr_ctx* c, const uint8_t* in, size_t n, ParsedFile* pf, bool views = false,
-               const avr::SkipRanges* skips = nullptr) {
-  std::vector<avr::NalRef> nals;
-  if (!avr::demux(in, n, &nals, skips)) return fail(c, AVR_ERR_FORMAT, "not an MP4/avcC or Annex-B H.264 stream");
-  avr::StreamParser sp;
-  sp.set_skips(in, skips);
-  for (auto& nr : nals) {
-    avr::SliceInfo s;
-    if (sp.next(in + nr.offset, nr.size, &s, views)) {
-      s.nal_offset = nr.offset;
-      s.nal_size = nr.size;
-      pf->slices.push_back(std::move(s));
-    }
-  }
-  return AVR_OK;
-}
-
-// A slice the device can take: supported syntax, at least a surrogate marker long, and an LDS ring
-// (ring_cols: 3 W + 7 records for an MBAFF slice) that fits a workgroup's LDS -- a very wide MBAFF
-// picture is stored skip_coded instead of failing the whole file's launch.
-bool recodable_candidate(const avr::SliceInfo& s) {
-  const int cols = s.h.mbaff && !s.h.field_pic ? 3 * s.h.mb_width + 7 : s.h.mb_width;
-  return s.h.supported && s.size >= (size_t)avr::kSurrogateMarkerBytes && avr::shared_bytes(cols) <= kLdsBudget;
-}
-
-// A slice as the container writer sees it: its payload (init_decoder's buf, size) and whether the
-// device may re-code it (recodable_candidate).
-struct SliceView {
-  const uint8_t* payload;
-  size_t size;
-  bool candidate;
-  uint64_t file_pos;   // where the payload stands verbatim in the file (the parse knows), or ~0
-};
-std::vector<SliceView> views_of(const ParsedFile& pf) {
-  std::vector<SliceView> v(pf.slices.size());
-  for (size_t i = 0; i < v.size(); i++)
-    v[i] = {pf.slices[i].payload(), pf.slices[i].size, recodable_candidate(pf.slices[i]),
-            pf.slices[i].file_payload_offset()};
-  return v;
-}
-
-// Host threads for one file's bulk steps (trigram index, container copies): up to 16, or 1 inside a
-// parallel_files worker, which already spreads the files over the thread budget (a corpus of large
-// files would otherwise start ~16 x 16 threads at once).
-thread_local bool tl_in_file_pool = false;
-unsigned bulk_threads() {
-  return tl_in_file_pool ? 1u : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-}
-
-// Every 00 00 0y trigram (y <= 3) of a file, keyed by y and the four bytes after it, then by
-// position.  In an escaped H.264 stream these occur only at start codes, emulation-prevention bytes
-// (00 00 03) and container bytes (MP4 lengths and boxes), so the index is small.
-struct TrigramIndex {
-  bool built = false;
-  struct Entry {
-    uint64_t key;   // y << 32 | the next four bytes (big-endian, zeros past the end)
-    uint64_t pos;
-    bool operator<(const Entry& o) const { return key != o.key ? key < o.key : pos < o.pos; }
-  };
-  std::vector<Entry> e;
-  // per y, every trigram position in ascending order: the lookups whose payload holds no four bytes
-  // after its trigram (built at the first such lookup)
-  bool pos_built = false;
-  std::vector<uint64_t> pos[4];
-  void build_pos() {
-    pos_built = true;
-    for (const Entry& x : e) pos[x.key >> 32].push_back(x.pos);
-    for (auto& v : pos) std::sort(v.begin(), v.end());
-  }
-  static uint64_t key_at(const uint8_t* f, size_t n, size_t p) {   // trigram at p (p + 2 < n)
-    uint32_t nx = 0;
-    for (int k = 0; k < 4; k++) nx = nx << 8 | (p + 3 + k < n ? f[p + 3 + k] : 0u);
-    return (uint64_t)f[p + 2] << 32 | nx;
-  }
-  // the trigrams starting in [lo, hi)
-  static void scan(const uint8_t* f, size_t n, size_t lo, size_t hi, std::vector<Entry>* out) {
-    const uint8_t* end = f + std::min(hi, n >= 2 ? n - 2 : 0);
-    for (const uint8_t* p = f + lo; p < end;) {
-      p = (const uint8_t*)memchr(p, 0, (size_t)(end - p));
-      if (!p) break;
-      if (p[1] == 0 && p[2] <= 3) out->push_back({key_at(f, n, (size_t)(p - f)), (uint64_t)(p - f)});
-      p++;
-    }
-  }
-  void build(const uint8_t* f, size_t n) {
-    built = true;
-    // a multi-GB file is scanned in chunks on host threads
-    const unsigned T = n < ((size_t)256 << 20) ? 1u : bulk_threads();
-    std::vector<std::vector<Entry>> part(T);
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < T; t++) th.emplace_back(scan, f, n, n * t / T, n * (t + 1) / T, &part[t]);
-    scan(f, n, 0, n / T, &part[0]);
-    for (auto& x : th) x.join();
-    for (auto& v : part) e.insert(e.end(), v.begin(), v.end());
-    std::sort(e.begin(), e.end());
-  }
-};
-
-// memmem(in + from, n - from, P, m) (the reference's search, recode.cpp:1285) without its cost on a
-// miss.  A payload P holding a 00 00 0y trigram (y <= 3) at offset j -- an unescaped payload whose
-// NAL had emulation-prevention bytes -- can only occur at q with a trigram of the file at q + j
-// followed by the same four bytes as in P (when P has them), so the index's entries with that key
-// from position from + j on, in ascending order, are the only candidates and the first that matches
-// is memmem's answer.  Such payloads are exactly the ones that usually occur nowhere, where memmem
-// would scan to the end of the file for each of them (O(misses x file): minutes for a 10-minute 4K
-// stream); with the key a miss costs a binary search.  A payload without one is found in its own
-// NAL (its bytes are verbatim there), so memmem stops at most one NAL past `from`.
-const uint8_t* find_payload(const uint8_t* in, size_t n, size_t from, const uint8_t* P, size_t m, TrigramIndex* ix) {
-  size_t j = 0;
-  bool anchor = false;
-  for (const uint8_t* q = P; m >= 3 && q + 2 < P + m;) {
-    q = (const uint8_t*)memchr(q, 0, (size_t)(P + m - 2 - q));
-    if (!q) break;
-    if (q[1] == 0 && q[2] <= 3) {
-      j = (size_t)(q - P);
-      anchor = true;
-      break;
-    }
-    q++;
-  }
-  if (!anchor) return (const uint8_t*)memmem(in + from, n - from, P, m);
-  if (!ix->built) {
-    const double tb = now_s();
-    ix->build(in, n);
-    if (getenv("AVR_ASM_TIMING")) fprintf(stderr, "index build %.3f s, %zu entries\n", now_s() - tb, ix->e.size());
-  }
-  using E = TrigramIndex::Entry;
-  if (j + 7 > m) {
-    // the trigram lies in P's last six bytes: no key beyond y; y's positions from from + j on, in
-    // ascending order -- the first that matches is memmem's answer
-    if (!ix->pos_built) ix->build_pos();
-    const std::vector<uint64_t>& ps = ix->pos[P[j + 2]];
-    for (auto it = std::lower_bound(ps.begin(), ps.end(), (uint64_t)(from + j)); it != ps.end(); ++it) {
-      const size_t q = (size_t)*it - j;
-      if (q + m > n) break;
-      if (memcmp(in + q, P, m) == 0) return in + q;
-    }
-    return nullptr;
-  }
-  const uint64_t key = TrigramIndex::key_at(P, m, j);   // P holds the four bytes after its trigram
-  for (auto it = std::lower_bound(ix->e.begin(), ix->e.end(), E{key, (uint64_t)(from + j)}); it != ix->e.end(); ++it) {
-    if (it->key != key) break;
-    const size_t q = (size_t)it->pos - j;
-    if (q + m > n) break;
-    if (memcmp(in + q, P, m) == 0) return in + q;
-  }
-  return nullptr;
-}
-
-// memmem(in + from, n - from, P, m) for a payload that stands verbatim at `own` >= from (segment
-// checks it): memmem's
-// answer is the first occurrence at or after `from` and `own` is one, so only [from, own) -- the
-// literal gap before the slice: start code or length, NAL and slice header, skipped NAL units --
-// needs a search.  Candidates are the gap's bytes equal to P[0] (memchr), each checked on its first
-// 64 bytes and, if those agree, in full; a gap with more than a few such deep candidates (only a
-// degenerate payload has them) goes to memmem over [from, own + m - 1).  O(gap) per slice instead
-// of memmem's O(m) needle preparation plus its scan: the segmentation of a 4 GB stream no longer
-// reads the stream once more.
-const uint8_t* find_before(const uint8_t* in, size_t from, size_t own, const uint8_t* P, size_t m) {
-  const size_t head = std::min<size_t>(m, 64);
-  int deep = 0;
-  for (size_t q = from; q < own;) {
-    const uint8_t* h = (const uint8_t*)memchr(in + q, P[0], own - q);
-    if (!h) break;
-    if (memcmp(h, P, head) == 0) {
-      if (++deep > 4) {
-        const uint8_t* r = (const uint8_t*)memmem(in + from, own - from + m - 1, P, m);
-        return r ? r : in + own;
-      }
-      if (memcmp(h + head, P + head, m - head) == 0) return h;
-    }
-    q = (size_t)(h - in) + 1;
-  }
-  return in + own;
-}
-
-// find_next_coded_block_and_emit_literal (recode.cpp:1275-1297): slice i becomes a cabac block when
-// it is recodable (ok[i]), at least a surrogate marker long, and its payload occurs verbatim after
-// the previous coded block.  Returns the payload's position in the file per slice (null = skip).
-std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const std::vector<SliceView>& sv,
-                                    const std::vector<char>& ok) {
-  std::vector<const uint8_t*> found(sv.size(), nullptr);
-  TrigramIndex ix;
-  // a recorded position is trusted only where the payload's bytes stand there (a payload that is a
-  // view of the file at that position trivially; a copy -- rank 0's parse arena, another revision
-  // of the file -- compared in full, on host threads); else the plain search
-  std::vector<char> own_ok(sv.size(), 0);
-  {
-    std::vector<size_t> chk;
-    for (size_t i = 0; i < sv.size(); i++) {
-      const uint64_t own = sv[i].file_pos;
-      if (!ok[i] || sv[i].size < (size_t)avr::kSurrogateMarkerBytes || own == ~(uint64_t)0 || own + sv[i].size > n) continue;
-      if (sv[i].payload == in + own) own_ok[i] = 1;
-      else chk.push_back(i);
-    }
-    uint64_t bytes = 0;
-    for (size_t i : chk) bytes += sv[i].size;
-    const unsigned T = bytes < ((uint64_t)64 << 20) ? 1u : bulk_threads();
-    auto work = [&](unsigned t) {
-      for (size_t k = t; k < chk.size(); k += T) {
-        const size_t i = chk[k];
-        own_ok[i] = memcmp(in + sv[i].file_pos, sv[i].payload, sv[i].size) == 0;
-      }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < T; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto& x : th) x.join();
-  }
-  size_t prev_end = 0;
-  for (size_t i = 0; i < sv.size(); i++) {
-    if (!ok[i] || sv[i].size < (size_t)avr::kSurrogateMarkerBytes) continue;
-    const uint64_t own = sv[i].file_pos;
-    const uint8_t* f = own_ok[i] && own >= prev_end
-                           ? find_before(in, prev_end, (size_t)own, sv[i].payload, sv[i].size)
-                           : find_payload(in, n, prev_end, sv[i].payload, sv[i].size, &ix);
-    if (f) {
-      found[i] = f;
-      prev_end = (size_t)(f - in) + sv[i].size;
-    }
-  }
-  return found;
-}
-std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const ParsedFile& pf, const std::vector<char>& ok) {
-  return segment(in, n, views_of(pf), ok);
-}
-
-// A large host output buffer handed to the caller (freed by avr_free = free): 2 MiB aligned and
-// advised to transparent huge pages, so its first touch costs one fault per 2 MiB instead of per
-// 4 KiB page (a 4.4 GB container or payload arena: ~1 s of page faults otherwise).
-uint8_t* host_alloc(size_t n) {
-  constexpr size_t kHuge = (size_t)2 << 20;
-  if (n < 16 * kHuge) return (uint8_t*)malloc(n ? n : 1);
-  void* p = nullptr;
-  if (posix_memalign(&p, kHuge, n)) return nullptr;
-  (void)madvise(p, n & ~(kHuge - 1), MADV_HUGEPAGE);
-  return (uint8_t*)p;
-}
-
-// Byte copies of a container's literals and re-coded blocks, spread over host threads when they are
-// large (a 10-minute 4K stream's container is 4.4 GB).  A job without a source fills its bytes
-// with `fill` (the decompressor's surrogate blocks).
-void copy_part(uint8_t* dst, const uint8_t* src, size_t len, uint8_t fill) {
-  if (src) memcpy(dst, src, len);
-  else memset(dst, fill, len);
-}
-void parallel_copies(const std::vector<avr::PbCopy>& jobs, uint8_t* base, uint8_t fill = 0) {
-  uint64_t total = 0;
-  for (const auto& j : jobs) total += j.len;
-  const unsigned T = total < ((uint64_t)64 << 20) ? 1u : bulk_threads();
-  if (T == 1) {
-    for (const auto& j : jobs) copy_part(base + j.dst, j.src, j.len, fill);
-    return;
-  }
-  // thread t copies the bytes [t total / T, (t + 1) total / T) of the concatenated jobs
-  auto work = [&](unsigned t) {
-    const uint64_t lo = total * t / T, hi = total * (t + 1) / T;
-    uint64_t at = 0;
-    for (const auto& j : jobs) {
-      const uint64_t a = std::max(at, lo), b = std::min(at + j.len, hi);
-      if (a < b) copy_part(base + j.dst + (a - at), j.src ? j.src + (a - at) : nullptr, (size_t)(b - a), fill);
-      at += j.len;
-      if (at >= hi) break;
-    }
-  };
-  std::vector<std::thread> th;
-  for (unsigned t = 1; t < T; t++) th.emplace_back(work, t);
-  work(0);
-  for (auto& x : th) x.join();
-}
-
-// fn(f) for f in [0, nf) on up to 16 host threads (independent files: segmentation, containers).
-// An exception in a worker (allocation failure) is rethrown here, on the caller's thread, so that
-// guarded() still turns it into a status.
-template <class F>
-void parallel_files(int nf, F&& fn) {
-  const unsigned T = (unsigned)std::min<int>(nf, (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
-  if (T <= 1) {
-    for (int f = 0; f < nf; f++) fn(f);
-    return;
-  }
-  std::atomic<int> next{0};
-  std::exception_ptr err;
-  std::mutex mu;
-  auto work = [&]() {
-    const bool was = tl_in_file_pool;
-    tl_in_file_pool = true;   // each file's own bulk steps stay on this thread
-    try {
-      for (int f; (f = next.fetch_add(1)) < nf;) fn(f);
-    } catch (...) {
-      std::lock_guard<std::mutex> g(mu);
-      if (!err) err = std::current_exception();
-      next = nf;
-    }
-    tl_in_file_pool = was;
-  };
-  std::vector<std::thread> th;
-  for (unsigned t = 1; t < T; t++) th.emplace_back(work);
-  work();
-  for (auto& x : th) x.join();
-  if (err) std::rethrow_exception(err);
-}
-
-// compressor::run's block stream (recode.cpp:1115-1125, 1275-1297) as a Recoded protobuf, written
-// once: the blocks' headers in order, their bytes by parallel_copies, into the caller's buffer dst
-// (cap bytes; too small: AVR_ERR_INVALID_ARGUMENT with *out_len = the size needed) or, without one,
-// into one exactly sized buffer allocated here (*out).
-int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv, const std::vector<const uint8_t*>& found,
-                   const std::vector<std::pair<const uint8_t*, size_t>>& recoded, int model, uint8_t** out,
-                   size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0,
-                   const std::vector<std::pair<const uint8_t*, size_t>>* seams = nullptr) {
-  std::vector<avr::PbBlock> blocks;
-  blocks.reserve(2 * sv.size() + 1);
-  size_t prev_end = 0;
-  for (size_t i = 0; i < sv.size(); i++) {
-    const SliceView& s = sv[i];
-    avr::PbBlock b;
-    if (found[i]) {
-      avr::PbBlock lit;
-      lit.has_literal = true;
-      lit.literal = in + prev_end;
-      lit.literal_len = (size_t)(found[i] - (in + prev_end));
-      blocks.push_back(lit);
-      prev_end = (size_t)(found[i] - in) + s.size;
-      b.has_size = true;
-      b.size = (int64_t)s.size;
-      b.has_parity = true;
-      b.length_parity = s.size & 1;
-      if (s.size > 1) b.has_last_byte = true, b.last_byte.assign(1, (char)s.payload[s.size - 1]);
-      b.has_cabac = true;
-      b.cabac = recoded[i].first;
-      b.cabac_len = recoded[i].second;
-      if (seams && (*seams)[i].second) b.has_seams = true, b.seams = (*seams)[i].first, b.seams_len = (*seams)[i].second;
-    } else {
-      b.has_skip = true;
-      b.skip_coded = true;
-      b.has_size = true;
-      b.size = (int64_t)s.size;
-    }
-    blocks.push_back(std::move(b));
-  }
-  avr::PbBlock lit;
-  lit.has_literal = true;
-  lit.literal = in + prev_end;
-  lit.literal_len = n - prev_end;
-  blocks.push_back(lit);
-  std::vector<uint8_t> md;
-  if (const char* tag = avr::version_of_model(model)) avr::pb_put_metadata_version(&md, tag);
-  size_t total = md.size();
-  for (const auto& b : blocks) total += avr::pb_block_size(b);
-  if (dst && total > cap) {
-    *out_len = total;
-    return AVR_ERR_INVALID_ARGUMENT;
-  }
-  uint8_t* o = dst ? dst : host_alloc(total);
-  if (!o) return AVR_ERR_OUT_OF_MEMORY;
-  if (!md.empty()) memcpy(o, md.data(), md.size());
-  size_t at = md.size();
-  std::vector<avr::PbCopy> copies;
-  copies.reserve(2 * blocks.size());
-  for (const auto& b : blocks) at = avr::pb_write_block(o, at, b, &copies);
-  if (at != total) {
-    if (!dst) free(o);
-    return fail(nullptr, AVR_ERR_DEVICE, "internal error: container size");
-  }
-  parallel_copies(copies, o);
-  if (out) *out = dst ? nullptr : o;
-  *out_len = total;
   return AVR_OK;
 }
 
@@ -1670,234 +821,6 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
 // decompressor::run (recode.cpp:1312-1357) for several files at once: the slices of every
 // parallel-model file go to one parallel launch, every reference-model file to one workgroup of a
 // sequential launch.
-// A split block (the parallel model's long-slice split): its pieces in the split plan, the cuts' q
-// (piece i's bytes end at q[i]), the spliced regenerated bytes after the run
-struct SplitBlock {
-  int block = -1, first = 0, pieces = 0;
-  std::vector<uint32_t> q;
-  std::vector<uint8_t> regen;
-  int32_t status = 0;
-  avr_slice_result bill{};
-};
-struct SplitPlan {
-  Plan plan;                        // the pieces (descs, their re-coded streams in the arena)
-  std::vector<avr::PieceCtl> ctl;
-  Bytes recs;                       // the cut records, rec_stride apart
-  size_t stride = avr::seam_rec_bytes(kMringCols);
-  static constexpr int kMringCols = avr::kMringCols;   // widest picture a record holds
-};
-struct DecJob {
-  std::vector<avr::PbBlock> blocks;
-  Bytes stream;                      // read_packet's stream: literals + surrogate blocks
-  bool parallel = false;
-  int model = AVR_MODEL_REFERENCE;   // from Recoded.Metadata.version
-  std::vector<int> desc_of_block;    // plan index per coded block (-1: none; <= -2: split block -2 - k)
-  std::vector<SplitBlock> splits;
-};
-
-// sp: where the pieces of split blocks go (nullptr: such a container is refused -- the sharded and
-// hooks paths decompress slices, not pieces)
-int decompress_setup(avr_ctx* c, const uint8_t* in, size_t n, DecJob* j, Plan* plan, SplitPlan* sp = nullptr) {
-  const bool tm = getenv("AVR_ASM_TIMING") != nullptr;
-  double t0 = now_s();
-  std::string version;
-  if (!avr::pb_parse(in, n, &j->blocks, &version)) return fail(c, AVR_ERR_FORMAT, "not a Recoded protobuf");
-  j->model = avr::model_of_version(version);
-  // another avrecode-amd container format (the round-2 "avrecode-amd:P", ...) would be read as a
-  // reference-model container and fail late: refuse it here
-  if (j->model < 0)
-    return fail(c, AVR_ERR_FORMAT, "unsupported container version " + version + " (expected " + avr::kParallelModelTag +
-                                       " or " + avr::kParallel32ModelTag + ")");
-  j->parallel = parallel_model(j->model);
-  // read_packet (recode.cpp:1359-1409): literals and surrogate blocks form the stream -- its layout
-  // first, then one allocation, the markers, and the literal copies and 'X' fills on host threads
-  uint64_t seq = 1;
-  size_t total = 0;
-  for (auto& b : j->blocks) {
-    if ((int)b.has_literal + (int)b.has_cabac + (int)b.has_skip != 1)
-      return fail(c, AVR_ERR_FORMAT, "Invalid input block: must have exactly one type");
-    if (b.has_literal) {
-      total += b.literal_len;
-    } else if (b.has_cabac) {
-      if (!b.has_size) return fail(c, AVR_ERR_FORMAT, "CABAC block requires size field.");
-      if (b.size < avr::kSurrogateMarkerBytes || b.size > ((int64_t)1 << 31))
-        return fail(c, AVR_ERR_FORMAT, "Invalid coded block size for surrogate: " + std::to_string(b.size));
-      total += (size_t)b.size;
-    } else if (!b.skip_coded) {
-      return fail(c, AVR_ERR_FORMAT, "Unknown input block type");
-    }
-  }
-  j->stream.resize(total);
-  // the surrogate fills: no 0x00 / 0x03 byte in them ('X'), so the parse steps over them
-  avr::SkipRanges skips;
-  {
-    std::vector<avr::PbCopy> fills;
-    fills.reserve(j->blocks.size());
-    size_t at = 0;
-    for (auto& b : j->blocks) {
-      if (b.has_literal) {
-        if (b.literal_len) fills.push_back({at, b.literal, b.literal_len});
-        at += b.literal_len;
-      } else if (b.has_cabac) {
-        avr::surrogate_marker(seq++, j->stream.data() + at);
-        fills.push_back({at + 8, nullptr, (size_t)b.size - 8});
-        if (b.size > 8) skips.push_back({at + 8, at + (size_t)b.size});
-        at += (size_t)b.size;
-      }
-    }
-    parallel_copies(fills, j->stream.data(), (uint8_t)'X');
-  }
-  static_assert('X' != 0 && 'X' != 3, "surrogate fill: no start-code or emulation-prevention byte");
-  if (tm) fprintf(stderr, "setup: pb+stream %.3f s\n", now_s() - t0), t0 = now_s();
-  ParsedFile pf;
-  if (int r = parse_file(c, j->stream.data(), j->stream.size(), &pf, /*views=*/true, &skips)) return r;
-  if (tm) fprintf(stderr, "setup: parse %.3f s\n", now_s() - t0), t0 = now_s();
-  // recognize_coded_block (recode.cpp:1546-1573): slices claim coded blocks in order
-  j->desc_of_block.assign(j->blocks.size(), -1);
-  size_t next_coded = 0;
-  uint64_t seq_check = 1;
-  std::vector<avr_slice_desc> descs;
-  std::vector<int> block_of;
-  Plan local;
-  for (auto& s : pf.slices) {
-    while (next_coded < j->blocks.size() && !j->blocks[next_coded].has_cabac && !j->blocks[next_coded].has_skip)
-      next_coded++;
-    if (next_coded >= j->blocks.size())
-      return fail(c, AVR_ERR_FORMAT, "Coded block expected, but not recorded in the compressed data.");
-    const avr::PbBlock& b = j->blocks[next_coded];
-    if ((size_t)b.size != s.size) return fail(c, AVR_ERR_FORMAT, "Invalid surrogate block size.");
-    avr_slice_desc d = desc_from_header(s);
-    if (b.has_cabac) {
-      uint8_t mk[8];
-      avr::surrogate_marker(seq_check++, mk);
-      if (memcmp(s.payload(), mk, 8) != 0) return fail(c, AVR_ERR_FORMAT, "Invalid surrogate marker in coded block.");
-      d.payload_size = (uint32_t)b.cabac_len;
-      d.read_limit = (uint32_t)b.cabac_len;
-      d.out_capacity = (uint32_t)(b.size + 64);
-    } else {
-      d.coded = 0;
-    }
-    if (b.has_cabac && b.has_seams) {   // a split block: its pieces go to the split plan
-      if (!sp) return fail(c, AVR_ERR_UNSUPPORTED, "split slices (block field 16) decompress through the whole-file calls only");
-      if (j->model != AVR_MODEL_PARALLEL || d.structure != AVR_STRUCT_FRAME || d.mb_width > SplitPlan::kMringCols)
-        return fail(c, AVR_ERR_FORMAT, "seams on a block that cannot be split");
-      SeamsDecoded sd;
-      if (!seams_decode(b.seams, b.seams_len, d, sp->stride, &sd))
-        return fail(c, AVR_ERR_FORMAT, "Invalid seams field in coded block.");
-      uint64_t tot = 0;
-      for (uint32_t l : sd.piece_len) tot += l;
-      if (tot != b.cabac_len || sd.q.back() >= (uint64_t)b.size || sd.first_mb[0] <= (uint32_t)d.first_mb)
-        return fail(c, AVR_ERR_FORMAT, "Invalid seams field in coded block.");
-      SplitBlock x;
-      x.block = (int)next_coded;
-      x.first = (int)sp->plan.descs.size();
-      x.pieces = sd.cuts + 1;
-      x.q = sd.q;
-      const uint32_t rec0 = (uint32_t)(sp->recs.size() / sp->stride);
-      sp->recs.insert(sp->recs.end(), sd.recs.begin(), sd.recs.end());
-      uint64_t off = 0;
-      for (int i = 0; i <= sd.cuts; i++) {
-        avr_slice_desc pd = d;
-        if (i) pd.first_mb = (int32_t)sd.first_mb[i - 1];
-        append_aligned(&sp->plan.arena, b.cabac + off, sd.piece_len[i], 16, &pd.payload_offset);
-        off += sd.piece_len[i];
-        pd.payload_size = pd.read_limit = sd.piece_len[i];
-        pd.out_capacity = (uint32_t)((i < sd.cuts ? sd.q[i] : (uint32_t)b.size) - (i ? sd.q[i - 1] : 0u) + 4096);
-        sp->plan.max_w = std::max(sp->plan.max_w, pd.mb_width);
-        sp->plan.descs.push_back(pd);
-        sp->ctl.push_back(avr::PieceCtl{i ? (int32_t)(rec0 + i - 1) : -1,
-                                        i < sd.cuts ? sd.first_mb[i] - (uint32_t)pd.first_mb : 0u, -1, 0});
-      }
-      j->desc_of_block[next_coded] = -2 - (int)j->splits.size();
-      j->splits.push_back(std::move(x));
-      next_coded++;
-      continue;
-    }
-    if (j->parallel && !d.coded) {   // the parallel model has no cross-slice state: skip it
-      next_coded++;
-      continue;
-    }
-    block_of.push_back((int)next_coded);
-    descs.push_back(d);
-    next_coded++;
-  }
-  // all checks passed: append to the shared plan (append_aligned's layout: 16-byte aligned streams,
-  // each followed by >= 16 zero bytes), the re-coded streams copied on host threads
-  if (!plan) {
-    for (size_t k = 0; k < descs.size(); k++) j->desc_of_block[block_of[k]] = (int)k;
-    return AVR_OK;
-  }
-  std::vector<avr::PbCopy> copies;
-  copies.reserve(descs.size());
-  uint64_t at = plan->layout_only ? plan->arena_end : plan->arena.size();
-  for (size_t k = 0; k < descs.size(); k++) {
-    avr_slice_desc& d = descs[k];
-    const avr::PbBlock& b = j->blocks[block_of[k]];
-    if (d.coded) {
-      d.payload_offset = (at + 15) & ~(uint64_t)15;
-      copies.push_back({(size_t)d.payload_offset, b.cabac, b.cabac_len});
-      at = d.payload_offset + b.cabac_len + 16;
-      plan->max_w = std::max(plan->max_w, ring_cols(d));
-    }
-  }
-  if (plan->layout_only) {
-    plan->arena_copies.insert(plan->arena_copies.end(), copies.begin(), copies.end());
-    plan->arena_end = at;
-    for (size_t k = 0; k < descs.size(); k++) {
-      j->desc_of_block[block_of[k]] = (int)plan->descs.size();
-      plan->descs.push_back(descs[k]);
-    }
-    return AVR_OK;
-  }
-  const size_t a0 = plan->arena.size();
-  plan->arena.resize(at);
-  {
-    uint64_t z = a0;   // the zero bytes between the streams
-    for (const auto& cp : copies) {
-      memset(plan->arena.data() + z, 0, cp.dst - z);
-      z = cp.dst + cp.len;
-    }
-    memset(plan->arena.data() + z, 0, at - z);
-  }
-  parallel_copies(copies, plan->arena.data());
-  for (size_t k = 0; k < descs.size(); k++) {
-    j->desc_of_block[block_of[k]] = (int)plan->descs.size();
-    plan->descs.push_back(descs[k]);
-  }
-  if (tm) fprintf(stderr, "setup: match+arena %.3f s\n", now_s() - t0);
-  return AVR_OK;
-}
-
-// decompressor::run's output (recode.cpp:1338-1357): the literals and the regenerated slices in
-// block order, each slice patched by the last-byte rule (x264 padding correction, 1345-1356).
-// slice(k, &p, &len) gives plan slice k's regenerated bytes and returns its status.
-template <class Slice>
-int splice_job(avr_ctx* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>* o) {
-  o->reserve(j.stream.size());
-  for (size_t i = 0; i < j.blocks.size(); i++) {
-    const avr::PbBlock& b = j.blocks[i];
-    if (b.has_literal) {
-      o->insert(o->end(), b.literal, b.literal + b.literal_len);
-      continue;
-    }
-    if (!b.has_cabac) continue;
-    const int k = j.desc_of_block[i];
-    if (k == -1) return fail(c, AVR_ERR_FORMAT, "Not all blocks were decoded.");
-    const uint8_t* p = nullptr;
-    size_t len = 0;
-    if (int stt = slice(k, &p, &len))
-      return fail(c, AVR_ERR_FORMAT, "slice " + std::to_string(k) + " failed to decode (" + std::to_string(stt) + ")");
-    const size_t o0 = o->size();
-    o->insert(o->end(), p, p + len);
-    if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {
-      const size_t n = o->size() - o0;
-      if ((int)b.length_parity != (int)(n & 1)) o->push_back((uint8_t)b.last_byte[0]);
-      else if (n) o->back() = (uint8_t)b.last_byte[0];
-    }
-  }
-  return AVR_OK;
-}
-
 int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* in_len, uint8_t** out,
                      size_t* out_len, int32_t* status, std::vector<Bill>* bills = nullptr) {
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2255,6 +1178,110 @@ int export_range(const ChainRangeOut& o, int* lo, int* hi, int32_t** status, uin
 
 }  // namespace
 
+namespace avr_host {
+
+// run_plan (avr_ctx.h; the hooks surface calls it too): defined after its callers above, and
+// instantiated below for the two host buffers it is used with
+template <class HostBuf>
+int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_slice_result>* res,
+             HostBuf* out_host, bool verify, uint32_t flags) {
+  const int n = (int)plan.descs.size();
+  if (plan.fields()) flags |= avr::kFlagFields;
+  // a parallel batch of progressive and field slices: the two kernels side by side
+  const avr::FieldLane lane = !sequential && plan.mixed() ? c->field_lane() : avr::FieldLane();
+  res->assign(n, avr_slice_result{0, 0, 0, 0, {0, 0, 0, 0, 0, 0}});
+  uint64_t out_total = 0;
+  for (auto& d : plan.descs) place_output(&d, &out_total);
+  out_host->resize(out_total);
+  if (!n) return AVR_OK;
+  const double t_wall = now_s();
+  HIP_TRY(c, c->in.reserve(plan.arena.size() + 4096));
+  HIP_TRY(c, c->out.reserve(out_total + 4096));
+  HIP_TRY(c, c->descs.reserve(sizeof(avr_slice_desc) * n));
+  HIP_TRY(c, c->res.reserve(sizeof(avr_slice_result) * n));
+  for (auto& e : c->ev)
+    if (!e) HIP_TRY(c, hipEventCreate(&e));
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->in.p, plan.arena.data(), plan.arena.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->descs.p, plan.descs.data(), sizeof(avr_slice_desc) * n, hipMemcpyHostToDevice,
+                            c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+  int rm = kRModeFallback;
+  if (sequential && mode == 0 && !getenv("AVR_RMODE_SEQUENTIAL") && rmode_parallel_pays(plan)) {
+    rm = run_rmode_compress(c, plan, out_total, flags);
+    if (rm < 0) return rm;
+  }
+  if (sequential && rm == AVR_OK) {
+    // done: the parallel reference-model compress
+  } else if (sequential) {
+    // one workgroup per file (the reference model is sequential within a file only)
+    const int nf = plan.n_files();
+    avr::SeqFiles sf;
+    sf.n_files = nf;
+    size_t fbytes = 0;
+    for (auto& d : plan.descs) fbytes = std::max(fbytes, (size_t)2 * d.mb_width * d.mb_height * 52);
+    sf.frame_stride = (fbytes + 255) & ~(size_t)255;
+    HIP_TRY(c, c->est.reserve(sizeof(uint16_t) * avr::kEstGlobal * (size_t)nf, true));
+    HIP_TRY(c, c->frames.reserve(sf.frame_stride * nf + 64));
+    HIP_TRY(c, c->frame_meta.reserve(sizeof(int) * (size_t)nf + 64));
+    if (!plan.file_first.empty()) {
+      HIP_TRY(c, c->file_first.reserve(sizeof(int) * plan.file_first.size()));
+      HIP_TRY(c, hipMemcpyAsync(c->file_first.p, plan.file_first.data(), sizeof(int) * plan.file_first.size(),
+                                hipMemcpyHostToDevice, c->stream));
+      sf.file_first = c->file_first.as<int>();
+    }
+    HIP_TRY(c, avr::launch_slices(mode, true, c->tables.as<avr::EngineTables>(), c->descs.as<avr_slice_desc>(), n,
+                                  plan.max_w, c->in.as<uint8_t>(), c->out.as<uint8_t>(), c->res.as<avr_slice_result>(),
+                                  c->est.as<uint16_t>(), c->frames.as<uint8_t>(), c->frame_meta.as<int>(), nullptr,
+                                  c->stream, sf, flags));
+  } else {
+    HIP_TRY(c, reserve_parallel(c, n, plan.max_w, lane.stream != nullptr));
+    HIP_TRY(c, avr::launch_slices(mode, false, c->tables.as<avr::EngineTables>(), c->descs.as<avr_slice_desc>(), n,
+                                  plan.max_w, c->in.as<uint8_t>(), c->out.as<uint8_t>(), c->res.as<avr_slice_result>(),
+                                  c->est.as<uint16_t>(), nullptr, nullptr, c->order_or_null(), c->stream,
+                                  avr::SeqFiles(), flags, c->queue.p, &lane));
+  }
+  std::vector<int32_t> verdict;
+  if (verify && mode == 0 && !sequential) {
+    HIP_TRY(c, c->regen.reserve(plan.arena.size() + 4096));
+    HIP_TRY(c, c->dec_descs.reserve(sizeof(avr_slice_desc) * n));
+    HIP_TRY(c, c->res_d.reserve(sizeof(avr_slice_result) * n));
+    HIP_TRY(c, c->verdict.reserve(sizeof(int32_t) * n));
+    avr_slice_desc* dd = c->dec_descs.as<avr_slice_desc>();
+    avr_slice_result* rd = c->res_d.as<avr_slice_result>();
+    HIP_TRY(c, avr::launch_derive_decompress(c->descs.as<avr_slice_desc>(), c->res.as<avr_slice_result>(), n, dd,
+                                             c->stream));
+    HIP_TRY(c, avr::launch_slices(1, false, c->tables.as<avr::EngineTables>(), dd, n, plan.max_w, c->out.as<uint8_t>(),
+                                  c->regen.as<uint8_t>(), rd, c->est.as<uint16_t>(), nullptr, nullptr,
+                                  c->order_or_null(), c->stream, avr::SeqFiles(),
+                                  (plan.fields() ? avr::kFlagFields : 0u) | (flags & avr::kFlagP32), c->queue.p,
+                                  &lane));
+    HIP_TRY(c, avr::launch_verify(c->descs.as<avr_slice_desc>(), c->res.as<avr_slice_result>(), rd, n,
+                                  c->in.as<uint8_t>(), c->regen.as<uint8_t>(), c->verdict.as<int32_t>(), c->stream));
+    verdict.resize(n);
+    HIP_TRY(c, hipMemcpyAsync(verdict.data(), c->verdict.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipMemcpyAsync(res->data(), c->res.p, sizeof(avr_slice_result) * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out_host->data(), c->out.p, out_total, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  float ms[3] = {0, 0, 0};
+  for (int i = 0; i < 3; i++) HIP_TRY(c, hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+  c->phase.upload_s += 1e-3 * ms[0];
+  c->phase.kernel_s += 1e-3 * ms[1];
+  c->phase.download_s += 1e-3 * ms[2];
+  c->plan_wall += now_s() - t_wall;
+  for (int k = 0; k < (int)verdict.size(); k++)
+    if ((*res)[k].status == 0 && verdict[k] != 1) (*res)[k].status = kStatusNoRoundtrip;
+  return AVR_OK;
+}
+
+template int run_plan(avr_ctx*, int, bool, Plan&, std::vector<avr_slice_result>*, Bytes*, bool, uint32_t);
+template int run_plan(avr_ctx*, int, bool, Plan&, std::vector<avr_slice_result>*, std::vector<uint8_t>*, bool, uint32_t);
+
+}  // namespace avr_host
+
 // ================================================================================ C ABI
 extern "C" {
 
@@ -2308,326 +1335,6 @@ size_t avr_get_split_bytes(const avr_ctx* c) { return c ? c->split_bytes : 0; }
 
 void avr_free(void* p) { free(p); }
 
-// ------------------------------------------------------------------ sharded decompress plans
-// decompressor::run (recode.cpp:1338-1409) cut in two around the device work: load = read_packet's
-// surrogate stream parsed and matched to the container's coded blocks (decompress_setup in layout
-// mode: descs and the arena layout, no bytes copied), then the arena written where the caller wants
-// it, and the splice of the regenerated slices with the literals and the last-byte patch
-// (recode.cpp:1345-1356).  A handle keeps its scratch (the surrogate stream) for the next load.
-}  // extern "C"
-struct avr_dec_plan {
-  DecJob job;
-  Plan plan;
-  uint64_t work = 0;
-  int max_h = 1;
-  const uint8_t* avrc = nullptr;   // the caller's container (the blocks point into it)
-  size_t n = 0;
-  // a piece plan (avr_dec_plan_load_pieces): plan.descs = the coded slices (a split slice once, the
-  // splice's indexing), units = what one workgroup regenerates, in container order; plan's arena
-  // layout is the units'
-  bool pieces = false;
-  std::vector<avr_slice_desc> units;
-  std::vector<avr_piece> unit_pieces;
-  Bytes recs;                      // the seam records, rec_stride apart
-  size_t rec_stride = 0;
-  void reset() {
-    avrc = nullptr;
-    pieces = false;
-    job.blocks.clear();
-    job.desc_of_block.clear();
-    job.splits.clear();
-    job.stream.clear();   // keeps its capacity: the next stream is written over mapped pages
-    plan.descs.clear();
-    plan.arena_copies.clear();
-    plan.arena_end = 0;
-    plan.max_w = 1;
-    plan.layout_only = true;
-    units.clear();
-    unit_pieces.clear();
-    recs.clear();
-  }
-};
-extern "C" {
-
-int avr_dec_plan_new(avr_dec_plan** out) {
-  if (!out) return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    *out = new avr_dec_plan();
-    return AVR_OK;
-  });
-}
-
-void avr_dec_plan_free(avr_dec_plan* h) { delete h; }
-
-int avr_dec_plan_load(avr_dec_plan* h, const uint8_t* avrc, size_t n, int* n_slices, size_t* arena_len,
-                      size_t* work_len, int* max_mb_width, int* max_mb_height) {
-  if (!h || !avrc || !n_slices || !arena_len || !work_len || !max_mb_width || !max_mb_height)
-    return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    h->reset();
-    if (int r = decompress_setup(nullptr, avrc, n, &h->job, &h->plan)) return r;
-    uint64_t w = 0;
-    int mh = 1;
-    for (auto& d : h->plan.descs) {
-      d.out_offset = w;
-      w += ((uint64_t)d.out_capacity + 15) & ~15ull;
-      mh = std::max(mh, d.mb_height);
-    }
-    h->avrc = avrc;
-    h->n = n;
-    h->work = w;
-    h->max_h = mh;
-    *n_slices = (int)h->plan.descs.size();
-    *arena_len = h->plan.arena_end + 16;
-    *work_len = w;
-    *max_mb_width = h->plan.max_w;
-    *max_mb_height = mh;
-    return AVR_OK;
-  });
-}
-
-// A piece plan: decompress_setup with a split plan (every check of the whole-file decompress on a
-// seams field), then the units laid out in container order -- a whole slice as avr_dec_plan_load
-// lays it out, a split slice's pieces one after the other, each stream copied straight from its
-// span of Block.cabac -- and plan.descs rebuilt as the coded slices, split ones included, for the
-// splice.
-int avr_dec_plan_load_pieces(avr_dec_plan* h, const uint8_t* avrc, size_t n, int* n_slices, int* n_units,
-                             size_t* arena_len, size_t* work_len, int* max_mb_width, int* max_mb_height, int* n_recs,
-                             size_t* rec_stride) {
-  if (!h || !avrc || !n_slices || !n_units || !arena_len || !work_len || !max_mb_width || !max_mb_height || !n_recs ||
-      !rec_stride)
-    return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    h->reset();
-    SplitPlan sp;
-    if (int r = decompress_setup(nullptr, avrc, n, &h->job, &h->plan, &sp)) return r;
-    // units for slice- and piece-range sharding: the parallel models only, as avr_plan_decompress
-    if (!h->job.parallel) return AVR_ERR_UNSUPPORTED;
-    DecJob& j = h->job;
-    std::vector<avr_slice_desc> slices;
-    std::vector<avr::PbCopy> copies;
-    uint64_t at = 0, work = 0, swork = 0;
-    int mw = std::max(h->plan.max_w, sp.plan.max_w), mh = 1;
-    auto unit = [&](avr_slice_desc d, const uint8_t* src, size_t len, const avr_piece& p) {
-      d.payload_offset = (at + 15) & ~(uint64_t)15;
-      copies.push_back({(size_t)d.payload_offset, src, len});
-      at = d.payload_offset + len + 16;
-      d.out_offset = work;
-      work += ((uint64_t)d.out_capacity + 15) & ~15ull;
-      mh = std::max(mh, d.mb_height);
-      h->units.push_back(d);
-      h->unit_pieces.push_back(p);
-    };
-    for (size_t i = 0; i < j.blocks.size(); i++) {
-      const avr::PbBlock& b = j.blocks[i];
-      const int k = j.desc_of_block[i];
-      if (!b.has_cabac || k == -1) continue;
-      const int s = (int)slices.size();
-      const size_t u0 = h->units.size();
-      avr_slice_desc sd;
-      if (k >= 0) {
-        sd = h->plan.descs[k];
-        unit(sd, b.cabac, b.cabac_len, avr_piece{-1, 0, s, UINT32_MAX});
-      } else {
-        const SplitBlock& x = j.splits[-2 - k];
-        sd = sp.plan.descs[x.first];
-        sd.payload_size = sd.read_limit = (uint32_t)b.cabac_len;
-        sd.out_capacity = (uint32_t)(b.size + 64);
-        size_t off = 0;
-        for (int p = 0; p < x.pieces; p++) {
-          const avr_slice_desc& pd = sp.plan.descs[x.first + p];
-          const avr::PieceCtl& pc = sp.ctl[x.first + p];
-          const uint32_t keep = p + 1 < x.pieces ? x.q[p] - (p ? x.q[p - 1] : 0u) : UINT32_MAX;
-          // the plan's records say where their piece's bytes start in the slice (the kernels do not read it)
-          if (pc.seam >= 0) ((avr::SeamRec*)(sp.recs.data() + (size_t)pc.seam * sp.stride))->q = x.q[p - 1];
-          unit(pd, b.cabac + off, pd.payload_size, avr_piece{pc.seam, pc.n_mbs, s, keep});
-          off += pd.payload_size;
-        }
-      }
-      sd.payload_offset = h->units[u0].payload_offset;
-      sd.out_offset = swork;
-      swork += ((uint64_t)sd.out_capacity + 15) & ~15ull;
-      j.desc_of_block[i] = s;
-      slices.push_back(sd);
-    }
-    j.splits.clear();
-    h->plan.descs = std::move(slices);
-    h->plan.arena_copies = std::move(copies);
-    h->plan.arena_end = at;
-    h->plan.max_w = mw;
-    h->recs = std::move(sp.recs);
-    h->rec_stride = sp.stride;
-    h->pieces = true;
-    h->avrc = avrc;
-    h->n = n;
-    h->work = work;
-    h->max_h = mh;
-    *n_slices = (int)h->plan.descs.size();
-    *n_units = (int)h->units.size();
-    *arena_len = h->plan.arena_end + 16;
-    *work_len = work;
-    *max_mb_width = mw;
-    *max_mb_height = mh;
-    *n_recs = (int)(h->recs.size() / h->rec_stride);
-    *rec_stride = h->rec_stride;
-    return AVR_OK;
-  });
-}
-
-int avr_dec_plan_units(const avr_dec_plan* h, avr_slice_desc* descs, avr_piece* pieces) {
-  if (!h || !h->avrc || !h->pieces || ((!descs || !pieces) && !h->units.empty())) return AVR_ERR_INVALID_ARGUMENT;
-  if (!h->units.empty()) {
-    memcpy(descs, h->units.data(), sizeof(avr_slice_desc) * h->units.size());
-    memcpy(pieces, h->unit_pieces.data(), sizeof(avr_piece) * h->unit_pieces.size());
-  }
-  return AVR_OK;
-}
-
-int avr_dec_plan_recs(const avr_dec_plan* h, uint8_t* out, size_t cap) {
-  if (!h || !h->avrc || !h->pieces || cap < h->recs.size() || (!out && !h->recs.empty())) return AVR_ERR_INVALID_ARGUMENT;
-  if (!h->recs.empty()) memcpy(out, h->recs.data(), h->recs.size());
-  return AVR_OK;
-}
-
-int avr_dec_plan_descs(const avr_dec_plan* h, avr_slice_desc* out) {
-  if (!h || !h->avrc || (!out && !h->plan.descs.empty())) return AVR_ERR_INVALID_ARGUMENT;
-  if (!h->plan.descs.empty()) memcpy(out, h->plan.descs.data(), sizeof(avr_slice_desc) * h->plan.descs.size());
-  return AVR_OK;
-}
-
-int avr_dec_plan_arena(const avr_dec_plan* h, uint8_t* out, size_t cap) {
-  if (!h || !h->avrc || !out || cap < h->plan.arena_end + 16) return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    const auto& cp = h->plan.arena_copies;
-    const uint64_t end = h->plan.arena_end + 16;
-    uint64_t z = 0;   // the zero bytes between and after the streams
-    for (const auto& c : cp) {
-      memset(out + z, 0, c.dst - z);
-      z = c.dst + c.len;
-    }
-    memset(out + z, 0, end - z);
-    parallel_copies(cp, out);
-    return AVR_OK;
-  });
-}
-
-}  // extern "C"
-namespace {
-// splice_job's output laid out: the literal and regenerated-slice copies, the last-byte patches
-// (position, byte) and the total length.
-int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* regen, size_t regen_len,
-                  const uint64_t* offsets, const uint32_t* lens, std::vector<avr::PbCopy>* copies,
-                  std::vector<std::pair<size_t, uint8_t>>* patches, size_t* total) {
-  const DecJob& j = h->job;
-  const int ns = (int)h->plan.descs.size();
-  // every slice's regenerated bytes inside regen and within its own output capacity
-  for (int k = 0; k < ns; k++)
-    if (status[k] == 0 && (offsets[k] > regen_len || lens[k] > regen_len - offsets[k] ||
-                           lens[k] > h->plan.descs[k].out_capacity))
-      return AVR_ERR_INVALID_ARGUMENT;
-  copies->reserve(j.blocks.size());
-  size_t at = 0;
-  for (size_t i = 0; i < j.blocks.size(); i++) {
-    const avr::PbBlock& b = j.blocks[i];
-    if (b.has_literal) {
-      if (b.literal_len) copies->push_back({at, b.literal, b.literal_len});
-      at += b.literal_len;
-      continue;
-    }
-    if (!b.has_cabac) continue;
-    const int k = j.desc_of_block[i];
-    if (k < 0) return AVR_ERR_FORMAT;          // "Not all blocks were decoded." (recode.cpp:1354)
-    if (status[k]) return AVR_ERR_FORMAT;      // the slice failed to decode
-    const size_t len = lens[k];
-    if (len) copies->push_back({at, regen + offsets[k], len});
-    size_t m = len;
-    if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {   // recode.cpp:1345-1356
-      if ((int)b.length_parity != (int)(m & 1)) patches->push_back({at + m, (uint8_t)b.last_byte[0]}), m++;
-      else if (m) patches->push_back({at + m - 1, (uint8_t)b.last_byte[0]});
-    }
-    at += m;
-  }
-  *total = at;
-  return AVR_OK;
-}
-}  // namespace
-extern "C" {
-
-int avr_dec_plan_splice(const avr_dec_plan* h, const int32_t* status, const uint8_t* regen, size_t regen_len,
-                        const uint64_t* offsets, const uint32_t* lens, uint8_t* out, size_t out_cap, size_t* out_len) {
-  const int ns = h ? (int)h->plan.descs.size() : 0;
-  if (!h || !h->avrc || !out_len || (ns && (!status || !regen || !offsets || !lens))) return AVR_ERR_INVALID_ARGUMENT;
-  *out_len = 0;
-  return guarded(nullptr, [&]() -> int {
-    std::vector<avr::PbCopy> copies;
-    std::vector<std::pair<size_t, uint8_t>> patches;
-    size_t total = 0;
-    if (int r = splice_layout(h, status, regen, regen_len, offsets, lens, &copies, &patches, &total)) return r;
-    *out_len = total;
-    if (total > out_cap || (total && !out)) return AVR_ERR_INVALID_ARGUMENT;
-    parallel_copies(copies, out);
-    for (const auto& pt : patches) out[pt.first] = pt.second;
-    return AVR_OK;
-  });
-}
-
-int avr_plan_decompress(const uint8_t* avrc, size_t n, avr_slice_desc** descs, int* n_slices, uint8_t** arena,
-                        size_t* arena_len, size_t* work_len, int* max_mb_width, int* max_mb_height) {
-  if (!avrc || !descs || !n_slices || !arena || !arena_len || !work_len || !max_mb_width || !max_mb_height)
-    return AVR_ERR_INVALID_ARGUMENT;
-  *descs = nullptr;
-  *arena = nullptr;
-  return guarded(nullptr, [&]() -> int {
-    avr_dec_plan h;
-    int ns = 0;
-    size_t al = 0;
-    if (int r = avr_dec_plan_load(&h, avrc, n, &ns, &al, work_len, max_mb_width, max_mb_height)) return r;
-    // a slice batch for slice-range sharding: the parallel models only (the reference model's
-    // slices chain; the chained model shards by chains, avr_decompress_chain_range)
-    if (!h.job.parallel) return AVR_ERR_UNSUPPORTED;
-    *descs = (avr_slice_desc*)malloc(sizeof(avr_slice_desc) * std::max(1, ns));
-    *arena = host_alloc(al);
-    if (!*descs || !*arena) {
-      free(*descs);
-      free(*arena);
-      *descs = nullptr;
-      *arena = nullptr;
-      return AVR_ERR_OUT_OF_MEMORY;
-    }
-    avr_dec_plan_descs(&h, *descs);
-    if (int r = avr_dec_plan_arena(&h, *arena, al)) return r;
-    *n_slices = ns;
-    *arena_len = al;
-    return AVR_OK;
-  });
-}
-
-int avr_splice_container(const uint8_t* avrc, size_t n, int n_slices, const int32_t* status, const uint8_t* regen,
-                         size_t regen_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out,
-                         size_t* out_len) {
-  if (!avrc || n_slices < 0 || (n_slices && (!status || !regen || !offsets || !lens)) || !out || !out_len)
-    return AVR_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  return guarded(nullptr, [&]() -> int {
-    avr_dec_plan h;
-    int ns = 0, mw = 0, mh = 0;
-    size_t al = 0, wl = 0;
-    if (int r = avr_dec_plan_load(&h, avrc, n, &ns, &al, &wl, &mw, &mh)) return r;
-    if (ns != n_slices) return AVR_ERR_INVALID_ARGUMENT;
-    std::vector<avr::PbCopy> copies;
-    std::vector<std::pair<size_t, uint8_t>> patches;
-    size_t total = 0;
-    if (int r = splice_layout(&h, status, regen, regen_len, offsets, lens, &copies, &patches, &total)) return r;
-    uint8_t* o = host_alloc(total);
-    if (!o) return AVR_ERR_OUT_OF_MEMORY;
-    parallel_copies(copies, o);
-    for (const auto& pt : patches) o[pt.first] = pt.second;
-    *out = o;
-    *out_len = total;
-    return AVR_OK;
-  });
-}
-
 int avr_last_phase_times(const avr_ctx* c, avr_phase_times* out) {
   if (!c || !out) return AVR_ERR_INVALID_ARGUMENT;
   *out = c->phase;
@@ -2665,107 +1372,6 @@ int avr_compress_files(avr_ctx* c, int n_files, const uint8_t* const* in, const 
   return guarded(c, [&] { return compress_files(c, n_files, in, in_len, model, out, out_len, status); });
 }
 
-namespace {
-// Rank 0's container from gathered per-slice outputs (both avr_assemble_container entry points).
-int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceView>& sv, const int32_t* status,
-             const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out,
-             size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0) {
-  std::vector<char> ok(sv.size(), 0);
-  std::vector<std::pair<const uint8_t*, size_t>> blobs(sv.size(), {nullptr, 0});
-  for (size_t i = 0; i < sv.size(); i++) {
-    ok[i] = sv[i].candidate && status[i] == 0;
-    if (ok[i]) {
-      if (!recoded || offsets[i] > recoded_len || lens[i] > recoded_len - offsets[i]) return AVR_ERR_INVALID_ARGUMENT;
-      blobs[i] = {recoded + offsets[i], lens[i]};
-    }
-  }
-  const double t0 = now_s();
-  const std::vector<const uint8_t*> found = segment(file, n, sv, ok);
-  const double t1 = now_s();
-  const int r = emit_container(file, n, sv, found, blobs, model, out, out_len, dst, cap);
-  if (getenv("AVR_ASM_TIMING")) fprintf(stderr, "assemble: segment %.3f s, emit %.3f s\n", t1 - t0, now_s() - t1);
-  return r;
-}
-}  // namespace
-
-int avr_assemble_container(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
-                           const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens,
-                           uint8_t** out, size_t* out_len) {
-  if (!file || !out || !out_len || n_slices < 0 || (n_slices && (!status || !offsets || !lens)) || !assemblable(model))
-    return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    ParsedFile pf;
-    if (int r = parse_file(nullptr, file, n, &pf, /*views=*/true)) return r;
-    if ((size_t)n_slices != pf.slices.size()) return AVR_ERR_INVALID_ARGUMENT;
-    return assemble(file, n, model, views_of(pf), status, recoded, recoded_len, offsets, lens, out, out_len);
-  });
-}
-
-namespace {
-int assemble_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
-                    const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
-                    size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out, size_t* out_len,
-                    uint8_t* dst, size_t cap) {
-  if (!file || !out_len || n_slices < 0 || (n_slices && (!descs || !arena || !status || !offsets || !lens)) ||
-      !assemblable(model))
-    return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    std::vector<SliceView> sv((size_t)n_slices);
-    for (int i = 0; i < n_slices; i++) {
-      const avr_slice_desc& d = descs[i];
-      if (d.payload_offset > arena_len || d.payload_size > arena_len - d.payload_offset) return AVR_ERR_INVALID_ARGUMENT;
-      // only avr_parse_stream's own descriptors of this file: a coded slice is one recodable_candidate
-      // accepted (a surrogate marker long, its LDS ring within a workgroup), and a payload the parse
-      // found verbatim stands at file_offset (its first and last bytes checked: O(1) per slice)
-      if (d.coded && (d.payload_size < (uint32_t)avr::kSurrogateMarkerBytes ||
-                      avr::shared_bytes(ring_cols(d)) > kLdsBudget))
-        return AVR_ERR_INVALID_ARGUMENT;
-      const uint8_t* P = arena + d.payload_offset;
-      const size_t m = d.payload_size;
-      if (d.file_offset != ~(uint64_t)0) {
-        const size_t k = std::min<size_t>(m, 16);
-        if (d.file_offset > n || m > n - d.file_offset || memcmp(file + d.file_offset, P, k) != 0 ||
-            memcmp(file + d.file_offset + m - k, P + m - k, k) != 0)
-          return AVR_ERR_INVALID_ARGUMENT;
-      }
-      sv[i] = {P, m, d.coded != 0, d.file_offset};
-    }
-    return assemble(file, n, model, sv, status, recoded, recoded_len, offsets, lens, out, out_len, dst, cap);
-  });
-}
-}  // namespace
-
-int avr_assemble_container_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
-                                  const uint8_t* arena, size_t arena_len, const int32_t* status,
-                                  const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets,
-                                  const uint32_t* lens, uint8_t** out, size_t* out_len) {
-  if (!out) return AVR_ERR_INVALID_ARGUMENT;
-  return assemble_parsed(file, n, model, descs, n_slices, arena, arena_len, status, recoded, recoded_len, offsets, lens,
-                         out, out_len, nullptr, 0);
-}
-
-int avr_assemble_container_into(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
-                                const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
-                                size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t* out,
-                                size_t out_cap, size_t* out_len) {
-  if (!out) return AVR_ERR_INVALID_ARGUMENT;
-  return assemble_parsed(file, n, model, descs, n_slices, arena, arena_len, status, recoded, recoded_len, offsets, lens,
-                         nullptr, out_len, out, out_cap);
-}
-
-int avr_container_model(const uint8_t* avrc, size_t n, int* model) {
-  if (!avrc || !model) return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    std::vector<avr::PbBlock> blocks;
-    std::string version;
-    if (!avr::pb_parse(avrc, n, &blocks, &version)) return AVR_ERR_FORMAT;
-    const int m = avr::model_of_version(version);
-    if (m < 0) return AVR_ERR_FORMAT;
-    *model = m;
-    return AVR_OK;
-  });
-}
-
 int avr_decompress_file(avr_ctx* c, const uint8_t* in, size_t n, uint8_t** out, size_t* out_len) {
   if (!c || !in || !out || !out_len) return AVR_ERR_INVALID_ARGUMENT;
   int32_t st = 0;
@@ -2781,12 +1387,6 @@ int avr_decompress_files(avr_ctx* c, int n_files, const uint8_t* const* in, cons
   return guarded(c, [&] { return decompress_files(c, n_files, in, in_len, out, out_len, status); });
 }
 
-static int roundtrip_file(avr_ctx* c, const uint8_t* in, size_t n, int model, uint8_t** compressed,
-                          size_t* compressed_len, avr_file_stats* stats);
-int avr_roundtrip_file(avr_ctx* c, const uint8_t* in, size_t n, int model, uint8_t** compressed,
-                       size_t* compressed_len, avr_file_stats* stats) {
-  return guarded(c, [&] { return roundtrip_file(c, in, n, model, compressed, compressed_len, stats); });
-}
 static int roundtrip_file(avr_ctx* c, const uint8_t* in, size_t n, int model, uint8_t** compressed,
                           size_t* compressed_len, avr_file_stats* stats) {
   if (!c || !in) return AVR_ERR_INVALID_ARGUMENT;
@@ -2868,6 +1468,10 @@ static int roundtrip_file(avr_ctx* c, const uint8_t* in, size_t n, int model, ui
   }
   if (!same) return fail(c, AVR_ERR_ROUNDTRIP, "Compress-decompress roundtrip failed.");
   return AVR_OK;
+}
+int avr_roundtrip_file(avr_ctx* c, const uint8_t* in, size_t n, int model, uint8_t** compressed,
+                       size_t* compressed_len, avr_file_stats* stats) {
+  return guarded(c, [&] { return roundtrip_file(c, in, n, model, compressed, compressed_len, stats); });
 }
 
 // roundtrip_file's two attempts over a corpus: each attempt is one batched compress_files and one
@@ -3058,89 +1662,6 @@ int avr_slice_kernel(avr_ctx* c, int decompress, int n, int max_mb_width, int* k
   return AVR_OK;
 }
 
-int avr_parse_stream_range(const uint8_t* file, size_t n, int lo, int hi, avr_slice_desc** descs, int* n_slices,
-                           uint8_t** arena, size_t* arena_len, size_t* work_len, int* max_w, int* max_h) {
-  if (!file || !descs || !n_slices || !arena || !arena_len || !work_len || !max_w || !max_h || lo < 0)
-    return AVR_ERR_INVALID_ARGUMENT;
-  *descs = nullptr;
-  *arena = nullptr;
-  return guarded(nullptr, [&]() -> int {
-    ParsedFile pf;
-    if (int r = parse_file(nullptr, file, n, &pf, /*views=*/true)) return r;
-    const int total = (int)pf.slices.size();
-    const int b = std::min(lo, total), e = hi < 0 ? total : std::max(b, std::min(hi, total));
-    // the arena's layout first (append_aligned's: 16-byte aligned payloads, each followed by >= 16
-    // zero bytes), then one allocation and the payload copies on host threads
-    const size_t ns = (size_t)(e - b);
-    std::vector<avr_slice_desc> dv(ns);
-    std::vector<avr::PbCopy> copies(ns);
-    uint64_t work = 0, at = 0;
-    int mw = 1, mh = 1;
-    for (size_t i = 0; i < ns; i++) {
-      const avr::SliceInfo& s = pf.slices[b + i];
-      avr_slice_desc& d = dv[i];
-      d = desc_from_header(s);
-      d.payload_offset = (at + 15) & ~(uint64_t)15;
-      at = d.payload_offset + s.read_limit + 16;
-      copies[i] = {(size_t)d.payload_offset, s.payload(), s.read_limit};
-      d.payload_size = (uint32_t)s.size;
-      d.read_limit = (uint32_t)s.read_limit;
-      d.coded = recodable_candidate(s);
-      d.file_offset = s.file_payload_offset();
-      d.out_offset = work;
-      d.out_capacity = (uint32_t)(s.size * 2 + 256);
-      work += ((uint64_t)d.out_capacity + 15) & ~15ull;
-      if (d.coded) mw = std::max(mw, ring_cols(d));   // uncoded slices are never walked
-      mh = std::max(mh, d.mb_height);
-    }
-    const size_t alen = at + 16;
-    const size_t dn = sizeof(avr_slice_desc) * ns;
-    *descs = (avr_slice_desc*)malloc(dn ? dn : 1);
-    *arena = host_alloc(alen);
-    if (!*descs || !*arena) {
-      free(*descs);
-      free(*arena);
-      *descs = nullptr;
-      *arena = nullptr;
-      return AVR_ERR_OUT_OF_MEMORY;
-    }
-    if (dn) memcpy(*descs, dv.data(), dn);
-    parallel_copies(copies, *arena);
-    // the zero bytes between and after the payloads
-    uint64_t z = 0;
-    for (const auto& cp : copies) {
-      memset(*arena + z, 0, cp.dst - z);
-      z = cp.dst + cp.len;
-    }
-    memset(*arena + z, 0, alen - z);
-    *n_slices = (int)ns;
-    *arena_len = alen;
-    *work_len = work;
-    *max_w = mw;
-    *max_h = mh;
-    return AVR_OK;
-  });
-}
-
-int avr_parse_stream(const uint8_t* file, size_t n, avr_slice_desc** descs, int* n_slices, uint8_t** arena,
-                     size_t* arena_len, size_t* work_len, int* max_w, int* max_h) {
-  return avr_parse_stream_range(file, n, 0, -1, descs, n_slices, arena, arena_len, work_len, max_w, max_h);
-}
-
-int avr_slice_payload_sizes(const uint8_t* file, size_t n, uint32_t** sizes, int* n_slices) {
-  if (!file || !sizes || !n_slices) return AVR_ERR_INVALID_ARGUMENT;
-  *sizes = nullptr;
-  return guarded(nullptr, [&]() -> int {
-    ParsedFile pf;
-    if (int r = parse_file(nullptr, file, n, &pf, /*views=*/true)) return r;
-    *sizes = (uint32_t*)malloc(sizeof(uint32_t) * std::max<size_t>(1, pf.slices.size()));
-    if (!*sizes) return AVR_ERR_OUT_OF_MEMORY;
-    for (size_t i = 0; i < pf.slices.size(); i++) (*sizes)[i] = (uint32_t)pf.slices[i].size;
-    *n_slices = (int)pf.slices.size();
-    return AVR_OK;
-  });
-}
-
 int avr_pack_outputs(avr_ctx* c, const avr_slice_desc* d_desc, const avr_slice_result* d_res, int n,
                      const uint8_t* d_out, uint8_t* d_packed, uint64_t* d_offsets, void* stream) {
   if (!c || n < 0 || (n && (!d_desc || !d_res || !d_out || !d_packed || !d_offsets))) return AVR_ERR_INVALID_ARGUMENT;
@@ -3195,60 +1716,6 @@ int avr_pack_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* d
   return AVR_OK;
 }
 
-int avr_container_describe(const uint8_t* in, size_t n, char** json, uint8_t** reserialized, size_t* len) {
-  if (!in || !json || !reserialized || !len) return AVR_ERR_INVALID_ARGUMENT;
-  *json = nullptr;
-  *reserialized = nullptr;
-  std::vector<avr::PbBlock> blocks;
-  std::string version;
-  bool has_md = false;
-  if (!avr::pb_parse(in, n, &blocks, &version, &has_md)) return AVR_ERR_FORMAT;
-  static const char* hexd = "0123456789abcdef";
-  auto hex = [&](const uint8_t* p, size_t k) {
-    std::string h;
-    h.reserve(2 * k);
-    for (size_t i = 0; i < k; i++) h += hexd[p[i] >> 4], h += hexd[p[i] & 15];
-    return h;
-  };
-  std::string j = "{\"version\": ";
-  j += has_md ? "\"" + hex((const uint8_t*)version.data(), version.size()) + "\"" : std::string("null");
-  j += ", \"blocks\": [";
-  std::vector<uint8_t> o;
-  if (has_md) avr::pb_put_metadata_version(&o, version);
-  for (size_t i = 0; i < blocks.size(); i++) {
-    const avr::PbBlock& b = blocks[i];
-    std::string e;
-    auto add = [&](const std::string& kv) { e += (e.empty() ? "" : ", ") + kv; };
-    if (b.has_size) add("\"size\": " + std::to_string(b.size));
-    if (b.has_literal) add("\"literal\": \"" + hex(b.literal, b.literal_len) + "\"");
-    if (b.has_skip) add(std::string("\"skip_coded\": ") + (b.skip_coded ? "true" : "false"));
-    if (b.has_cabac) add("\"cabac\": \"" + hex(b.cabac, b.cabac_len) + "\"");
-    if (b.has_parity) add(std::string("\"length_parity\": ") + (b.length_parity ? "true" : "false"));
-    if (b.has_last_byte) add("\"last_byte\": \"" + hex((const uint8_t*)b.last_byte.data(), b.last_byte.size()) + "\"");
-    if (b.has_seams) add("\"seams\": \"" + hex(b.seams, b.seams_len) + "\"");
-    j += (i ? ", {" : "{") + e + "}";
-    avr::pb_put_block(&o, b);
-  }
-  j += "]}";
-  *json = (char*)malloc(j.size() + 1);
-  *reserialized = (uint8_t*)malloc(o.size() ? o.size() : 1);
-  if (!*json || !*reserialized) {
-    free(*json);
-    free(*reserialized);
-    *json = nullptr;
-    *reserialized = nullptr;
-    return AVR_ERR_OUT_OF_MEMORY;
-  }
-  memcpy(*json, j.c_str(), j.size() + 1);
-  if (!o.empty()) memcpy(*reserialized, o.data(), o.size());
-  *len = o.size();
-  return AVR_OK;
-}
-
-static int synthesize_stream(avr_ctx* c, const avr_synth_params* p, int n, uint8_t** out, size_t* out_len);
-int avr_synthesize_stream(avr_ctx* c, const avr_synth_params* p, int n, uint8_t** out, size_t* out_len) {
-  return guarded(c, [&] { return synthesize_stream(c, p, n, out, out_len); });
-}
 static int synthesize_stream(avr_ctx* c, const avr_synth_params* p, int n, uint8_t** out, size_t* out_len) {
   if (!c || !p || n <= 0 || !out || !out_len || p->mb_width <= 0 || p->mb_height <= 0 || p->slice_type < 0 ||
       p->slice_type > 2 || p->chroma_format_idc < 1 || p->chroma_format_idc > 3 || p->gop_length < 0 ||
@@ -3337,6 +1804,9 @@ static int synthesize_stream(avr_ctx* c, const avr_synth_params* p, int n, uint8
   *out_len = at;
   return AVR_OK;
 }
+int avr_synthesize_stream(avr_ctx* c, const avr_synth_params* p, int n, uint8_t** out, size_t* out_len) {
+  return guarded(c, [&] { return synthesize_stream(c, p, n, out, out_len); });
+}
 
 }  // extern "C"
 
@@ -3356,889 +1826,4 @@ extern "C" int avr_debug_profile(int mode, unsigned long long* out16) {
                : mode == 4 ? avr::profile_sequential_decompress(out16)
                            : avr::profile_parallel_generate(out16);
   return e == hipSuccess ? AVR_OK : AVR_ERR_DEVICE;
-}
-
-// ==================================================================== libavcodec-hooks surface
-// The reference's hook objects (compressor::cabac_decoder recode.cpp:1134-1268,
-// decompressor::cabac_decoder 1411-1520) answer each bin request by running the model inline.
-// Here the device has already done the whole file; the session replays the device's decode-order
-// bin trace (MODE_TRACE kernel) to the caller and cross-checks the caller's parse against it.
-struct avr_hooks_session;
-
-// A significance map of the device's parse (MODE_TRACE event records): the bins [begin, end) it
-// spans and the model state it starts under -- mb_xy and begin_sub_mb's arguments.
-struct HookMap {
-  uint32_t begin = 0, end = 0;
-  int x = 0, y = 0;
-  int sub[5] = {0, 0, 0, 0, 0};   // cat, scan8 index, max_coeff, is_dc, chroma422
-};
-
-struct avr_hooks_slice {
-  avr_hooks_session* sess = nullptr;
-  int index = 0;                 // slice index (decode order)
-  const uint8_t* trace = nullptr;   // 2 bytes per bin: bin | kind << 1, state byte before it
-  size_t nbins = 0, cur = 0;
-  const HookMap* maps = nullptr;
-  size_t nmaps = 0, map_cur = 0;
-  bool sub_open = false;
-  int sub_args[5] = {0, 0, 0, 0, 0};
-  int coding_type = 0;
-};
-
-// Streaming compress session: incremental demux + parse of the bytes fed so far.  Only what is new
-// is parsed: an Annex-B NAL unit once the next start code (00 00 00 / 00 00 01, demux_annexb's rule)
-// has been fed -- the unit in progress provisionally when a decoder already asks for its slice (a
-// later feed that extends it fails the session) -- and an MP4 sample once the moov box and the
-// whole sample are in.  Slices come out in decode order exactly as parse_file gives them.
-struct StreamIngest {
-  avr::StreamParser sp;
-  int kind = 0;                 // 0 undecided (< 8 bytes), 1 Annex-B, 2 MP4
-  // Annex-B
-  size_t scan = 0;              // where the search for the next boundary / start code resumes
-  bool in_nal = false;          // a NAL unit started at nal_begin (after its start code)
-  size_t nal_begin = 0;
-  size_t prov_end = 0;          // the unit in progress was parsed provisionally through here (0: not)
-  // MP4
-  bool have_layout = false;
-  avr::Mp4Layout layout;
-  size_t next_sample = 0;
-};
-
-struct avr_hooks_session {
-  avr_ctx* c = nullptr;
-  bool decompress = false;
-  std::vector<uint8_t> original;   // the H.264 file
-  std::vector<uint8_t> result;     // compress: the container; decompress: the original file
-  std::vector<uint8_t> stream;     // decompress: read_packet's stream
-  ParsedFile pf;
-  std::vector<char> coded;
-  std::vector<std::vector<uint8_t>> bins;   // per slice: the device's bins (2 bytes each)
-  std::vector<std::vector<HookMap>> maps;    // per slice: its significance maps
-  std::vector<avr_hooks_slice> slices;
-  size_t next_slice = 0;
-  uint64_t next_marker = 1;
-  avr_hooks_slice* live = nullptr;  // the slice model hooks refer to (one live CABAC context, recode.cpp:199)
-  uint64_t mb_calls = 0;
-  int mb_x = -1, mb_y = -1;         // the caller's last mb_xy (h264_model::mb_coord)
-  // frame_spec (update_frame_spec, recode.cpp:824-843): the caller's last call and the slice it
-  // belonged to; a call made between slices waits for the next init_decoder
-  bool fs_have = false, fs_pending = false;
-  int fs_num = 0, fs_w = 0, fs_h = 0, fs_slice = -1;
-  int pend_num = 0, pend_w = 0, pend_h = 0;
-  // streaming compress (avr_hooks_compress_stream_begin): `original` grows by avr_hooks_feed; pf holds
-  // the slices parsed from it so far (ing: incremental), traced[i] = slice i's device work is done --
-  // its bin trace and, for the parallel model, its final re-coded block (blocks / block_status: the
-  // container is assembled from them at avr_hooks_end without another device pass)
-  bool streaming = false;
-  StreamIngest ing;
-  std::vector<char> traced;
-  std::vector<std::vector<uint8_t>> blocks;
-  std::vector<int32_t> block_status;
-  int model = 0;
-  // decompress of a parallel-model container, on demand: the container's plan (every coded slice's
-  // re-coded block) is made at begin, and a slice is regenerated on the device -- with the coded
-  // slices after it that are not yet, up to kLazyBatch -- when init_decoder reaches it; its bins
-  // are traced from the regenerated payload (recode.cpp:1435-1449 decodes each bin as FFmpeg asks)
-  bool lazy = false;
-  DecJob job;
-  Plan dplan;
-  std::vector<int> plan_of;          // per slice: its dplan index (-1: not coded)
-  std::vector<int> block_of;         // per slice: its container block
-  std::vector<char> regen_done;
-  std::vector<std::vector<uint8_t>> regen;   // per slice: its regenerated payload (last-byte patched)
-  std::string err;
-  void fail_once(const std::string& m) {
-    if (err.empty()) err = m;
-  }
-};
-
-namespace {
-
-// FFmpeg's state transition for one decoded bin (ff_h264_mlps_state, cabac_code.h:46-48)
-uint8_t next_state(uint8_t s, int bin) {
-  const int p = s >> 1, mps = s & 1;
-  if (bin == mps) return (uint8_t)(2 * (p < 62 ? p + 1 : p) + mps);
-  return (uint8_t)(p == 0 ? (s ^ 1) : 2 * avr::kTransIdxLPS[p] + mps);
-}
-
-// Device trace (MODE_TRACE kernel) of the slices `which` of hs->pf into hs->bins / hs->maps.
-int trace_slices(avr_hooks_session* hs, const std::vector<int>& which) {
-  avr_ctx* c = hs->c;
-  Plan plan;
-  std::vector<int> slice_of;
-  for (const int i : which) {
-    const avr::SliceInfo& s = hs->pf.slices[i];
-    avr_slice_desc d = desc_from_header(s);
-    append_aligned(&plan.arena, s.payload(), s.read_limit, 16, &d.payload_offset);
-    d.payload_size = (uint32_t)s.size;
-    d.read_limit = (uint32_t)s.read_limit;
-    // 2 bytes per bin (H.264 bounds a slice's bins by ~32/3 per payload byte plus a per-macroblock
-    // allowance, 7.4.2.2) and 12 bytes of map events per residual block (<= 51 per macroblock)
-    d.out_capacity = (uint32_t)std::min<uint64_t>(
-        0xfffffff0ull, 32ull * s.size + 1280ull * d.mb_width * d.mb_height + 8192);
-    plan.max_w = std::max(plan.max_w, ring_cols(d));
-    slice_of.push_back(i);
-    plan.descs.push_back(d);
-  }
-  if (plan.descs.empty()) return AVR_OK;
-  std::vector<avr_slice_result> res;
-  std::vector<uint8_t> traces;
-  if (int r = run_plan(c, 3, false, plan, &res, &traces)) return r;
-  for (size_t k = 0; k < plan.descs.size(); k++) {
-    const int i = slice_of[k];
-    if (res[k].status != 0)
-      return fail(c, AVR_ERR_FORMAT, "hooks: device trace of slice " + std::to_string(i) + " failed (" +
-                                         std::to_string(res[k].status) + ")");
-    // split the records: bins (kinds 0-2) and map events (kind 3, avr_walker.h TRACE_EV_*)
-    const uint8_t* t = traces.data() + plan.descs[k].out_offset;
-    const size_t len = res[k].out_len;
-    std::vector<uint8_t>& b = hs->bins[i];
-    std::vector<HookMap>& m = hs->maps[i];
-    b.clear();
-    m.clear();
-    b.reserve(len);
-    bool open = false;
-    for (size_t at = 0; at + 2 <= len;) {
-      if (((t[at] >> 1) & 3) != 3) {
-        b.push_back(t[at]);
-        b.push_back(t[at + 1]);
-        at += 2;
-        continue;
-      }
-      const uint32_t bin_index = (uint32_t)(b.size() / 2);
-      if (t[at + 1] == 1 && at + 10 <= len && !open) {
-        HookMap h;
-        h.begin = bin_index;
-        h.x = t[at + 2] | t[at + 3] << 8;
-        h.y = t[at + 4] | t[at + 5] << 8;
-        h.sub[0] = t[at + 6], h.sub[1] = t[at + 7], h.sub[2] = t[at + 8];
-        h.sub[3] = t[at + 9] & 1, h.sub[4] = t[at + 9] >> 1;
-        m.push_back(h);
-        open = true;
-        at += 10;
-      } else if (t[at + 1] == 2 && open) {
-        m.back().end = bin_index;
-        open = false;
-        at += 2;
-      } else {
-        return fail(c, AVR_ERR_DEVICE, "hooks: malformed device trace of slice " + std::to_string(i));
-      }
-    }
-    if (open) return fail(c, AVR_ERR_DEVICE, "hooks: device trace of slice " + std::to_string(i) + " ends in a map");
-  }
-  return AVR_OK;
-}
-
-// Device trace of every coded slice of hs->pf (decode order).
-int run_traces(avr_hooks_session* hs) {
-  std::vector<int> which;
-  for (size_t i = 0; i < hs->pf.slices.size(); i++)
-    if (hs->coded[i]) which.push_back((int)i);
-  hs->bins.assign(hs->pf.slices.size(), {});
-  hs->maps.assign(hs->pf.slices.size(), {});
-  return trace_slices(hs, which);
-}
-
-// Streaming session: one NAL unit of the fed bytes through the stream parser (a slice joins pf).
-void ingest_nal(avr_hooks_session* hs, size_t off, size_t size) {
-  avr::SliceInfo si;
-  if (!hs->ing.sp.next(hs->original.data() + off, size, &si)) return;
-  si.nal_offset = off;
-  si.nal_size = size;
-  hs->pf.slices.push_back(std::move(si));
-}
-
-// Parse what the fed bytes newly complete.  final: the stream has ended (avr_hooks_end: the unit in
-// progress ends with it).  want: the number of slices a decoder needs now -- when the complete units
-// do not reach it, the Annex-B unit in progress is taken provisionally.
-int ingest(avr_hooks_session* hs, bool final, size_t want) {
-  StreamIngest& g = hs->ing;
-  const uint8_t* f = hs->original.data();
-  const size_t n = hs->original.size();
-  if (!g.kind) {
-    if (n < 8 && !final) return AVR_OK;
-    g.kind = avr::is_mp4(f, n) ? 2 : 1;
-  }
-  if (g.kind == 2) {
-    if (!g.have_layout) {
-      const int r = avr::mp4_layout(f, n, &g.layout);
-      if (r < 0 || (r == 0 && final)) return fail(hs->c, AVR_ERR_FORMAT, "hooks: not an MP4/avcC H.264 stream");
-      if (r == 0) return AVR_OK;   // the moov box is not in yet (a moov-last file: not before the end)
-      g.have_layout = true;
-      for (const avr::NalRef& nr : g.layout.param_sets) ingest_nal(hs, nr.offset, nr.size);
-    }
-    std::vector<avr::NalRef> nals;
-    for (; g.next_sample < g.layout.samples.size(); g.next_sample++) {
-      const avr::NalRef& smp = g.layout.samples[g.next_sample];
-      if (smp.offset > n || smp.size > n - smp.offset) {
-        if (final) return fail(hs->c, AVR_ERR_FORMAT, "hooks: an MP4 sample lies past the end of the stream");
-        break;   // not complete yet
-      }
-      nals.clear();
-      avr::mp4_sample_nals(f, smp, g.layout.len_size, &nals);
-      for (const avr::NalRef& nr : nals) ingest_nal(hs, nr.offset, nr.size);
-    }
-    return AVR_OK;
-  }
-  // Annex-B (demux_annexb's rules, resumed where the last call stopped)
-  auto is_sc = [&](size_t j) { return j + 3 <= n && f[j] == 0 && f[j + 1] == 0 && f[j + 2] == 1; };
-  auto unit_end = [&](size_t begin, size_t end) {   // trailing zero bytes belong to the next start code
-    while (end > begin && f[end - 1] == 0) end--;
-    return end;
-  };
-  for (;;) {
-    if (!g.in_nal) {
-      size_t i = g.scan;
-      while (i + 3 <= n && !is_sc(i)) i++;
-      if (i + 3 > n) {
-        g.scan = i;
-        break;
-      }
-      g.in_nal = true;
-      g.nal_begin = g.scan = i + 3;
-    }
-    size_t j = g.scan;
-    while (j + 3 <= n && !(f[j] == 0 && f[j + 1] == 0 && (f[j + 2] == 1 || f[j + 2] == 0))) j++;
-    if (j + 3 > n) {
-      g.scan = j;
-      break;
-    }
-    // the unit in progress is complete: [nal_begin, j) without trailing zeros
-    const size_t end = unit_end(g.nal_begin, j);
-    if (g.prov_end) {
-      if (end != g.prov_end)
-        return fail(hs->c, AVR_ERR_FORMAT, "hooks: a slice was decoded before its NAL unit was complete");
-      g.prov_end = 0;
-    } else if (end > g.nal_begin) {
-      ingest_nal(hs, g.nal_begin, end - g.nal_begin);
-    }
-    g.in_nal = false;
-    g.scan = j;
-  }
-  // the unit in progress: at the end of the stream it is complete; before it, it is parsed
-  // provisionally when the decoder needs a slice the complete units do not hold
-  if (g.in_nal && (final || hs->pf.slices.size() < want)) {
-    const size_t end = unit_end(g.nal_begin, n);
-    if (g.prov_end && end != g.prov_end)
-      return fail(hs->c, AVR_ERR_FORMAT, "hooks: a slice was decoded before its NAL unit was complete");
-    if (!g.prov_end && end > g.nal_begin) {
-      ingest_nal(hs, g.nal_begin, end - g.nal_begin);
-      g.prov_end = end;
-    }
-    if (final) g.in_nal = false, g.prov_end = 0;
-  }
-  return AVR_OK;
-}
-
-// Per-slice state for the slices parsed so far.
-void grow_session(avr_hooks_session* hs) {
-  const size_t n = hs->pf.slices.size();
-  hs->coded.resize(n, 0);
-  hs->bins.resize(n);
-  hs->maps.resize(n);
-  hs->slices.resize(n);   // no slice object is live here (init_decoder closed it first)
-  hs->traced.resize(n, 0);
-  hs->blocks.resize(n);
-  hs->block_status.resize(n, AVR_SLICE_NO_ROUNDTRIP);
-}
-
-// Streaming session: the device work of slice i and of every parsed slice after it not done yet
-// (trace-ahead: the slices a feed completed go to the device together) -- their decode-order bin
-// traces, and for the parallel model their final re-coded blocks (compress + the per-slice device
-// roundtrip check, as avr_compress_file runs it).
-int stream_device_work(avr_hooks_session* hs, size_t i) {
-  std::vector<int> which;
-  for (size_t k = i; k < hs->pf.slices.size(); k++)
-    if (!hs->traced[k]) {
-      hs->traced[k] = 1;
-      if (recodable_candidate(hs->pf.slices[k])) which.push_back((int)k);
-    }
-  if (which.empty()) return AVR_OK;
-  if (int r = trace_slices(hs, which)) return r;
-  if (!parallel_model(hs->model)) return AVR_OK;
-  Plan plan;
-  for (const int k : which) {
-    const avr::SliceInfo& s = hs->pf.slices[k];
-    avr_slice_desc d = desc_from_header(s);
-    append_aligned(&plan.arena, s.payload(), s.read_limit, 16, &d.payload_offset);
-    d.payload_size = (uint32_t)s.size;
-    d.read_limit = (uint32_t)s.read_limit;
-    d.out_capacity = (uint32_t)(s.size * 2 + 256);
-    plan.max_w = std::max(plan.max_w, ring_cols(d));
-    plan.descs.push_back(d);
-  }
-  std::vector<avr_slice_result> res;
-  std::vector<uint8_t> outb;
-  if (int r = run_plan(hs->c, 0, false, plan, &res, &outb, /*verify=*/true, coder_flag(hs->model))) return r;
-  for (size_t q = 0; q < which.size(); q++) {
-    const int k = which[q];
-    hs->block_status[k] = res[q].status;
-    if (res[q].status == 0)
-      hs->blocks[k].assign(outb.begin() + plan.descs[q].out_offset, outb.begin() + plan.descs[q].out_offset + res[q].out_len);
-  }
-  return AVR_OK;
-}
-
-// Lazy decompress session: regenerate the coded slices from i on that are not yet (at most
-// kLazyBatch, one device launch), patch each by the last-byte rule (recode.cpp:1345-1356) and put
-// the regenerated payload in place of the surrogate one; trace = also trace them (init_decoder).
-constexpr size_t kLazyBatch = 32;
-int lazy_device_work(avr_hooks_session* hs, size_t i, bool trace, size_t batch = kLazyBatch) {
-  std::vector<int> which;
-  for (size_t k = i; k < hs->pf.slices.size() && which.size() < batch; k++)
-    if (hs->coded[k] && !hs->regen_done[k]) which.push_back((int)k);
-  if (which.empty()) return AVR_OK;
-  Plan sub;
-  for (const int k : which) {
-    avr_slice_desc d = hs->dplan.descs[hs->plan_of[k]];
-    append_aligned(&sub.arena, hs->dplan.arena.data() + d.payload_offset, d.payload_size, 16, &d.payload_offset);
-    sub.max_w = std::max(sub.max_w, ring_cols(d));
-    sub.descs.push_back(d);
-  }
-  std::vector<avr_slice_result> res;
-  std::vector<uint8_t> outb;
-  if (int r = run_plan(hs->c, 1, false, sub, &res, &outb, false, coder_flag(hs->model))) return r;
-  for (size_t q = 0; q < which.size(); q++) {
-    const int k = which[q];
-    if (res[q].status != 0)
-      return fail(hs->c, AVR_ERR_FORMAT, "slice " + std::to_string(k) + " failed to decode (" +
-                                             std::to_string(res[q].status) + ")");
-    std::vector<uint8_t>& g = hs->regen[k];
-    g.assign(outb.begin() + sub.descs[q].out_offset, outb.begin() + sub.descs[q].out_offset + res[q].out_len);
-    const avr::PbBlock& b = hs->job.blocks[hs->block_of[k]];
-    if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {   // as splice_job
-      if ((int)b.length_parity != (int)(g.size() & 1)) g.push_back((uint8_t)b.last_byte[0]);
-      else if (!g.empty()) g.back() = (uint8_t)b.last_byte[0];
-    }
-    // the regenerated payload in place of the surrogate one; the NAL's bytes after the payload
-    // (from the literal that follows the block) stay, as does the parse's read limit
-    avr::SliceInfo& s = hs->pf.slices[k];
-    s.own();
-    if (g.size() != s.size || s.rbsp.size() < s.h.cabac_start + s.size)
-      return fail(hs->c, AVR_ERR_FORMAT, "slice " + std::to_string(k) + " regenerated " + std::to_string(g.size()) +
-                                             " bytes for a " + std::to_string(s.size) + "-byte payload");
-    std::copy(g.begin(), g.end(), s.rbsp.begin() + s.h.cabac_start);
-    hs->regen_done[k] = 1;
-  }
-  return trace ? trace_slices(hs, which) : AVR_OK;
-}
-
-// which slices of the file a container re-codes: the i-th non-literal block is slice i's
-bool coded_from_container(const std::vector<avr::PbBlock>& blocks, size_t n_slices, std::vector<char>* coded) {
-  coded->assign(n_slices, 0);
-  size_t i = 0;
-  for (auto& b : blocks) {
-    if (b.has_literal) continue;
-    if (i >= n_slices) return false;
-    (*coded)[i++] = b.has_cabac ? 1 : 0;
-  }
-  return i == n_slices;
-}
-
-// the live slice is done (the next init_decoder or avr_hooks_end): every bin and every map consumed
-void close_live(avr_hooks_session* hs) {
-  avr_hooks_slice* h = hs->live;
-  hs->live = nullptr;
-  if (!h) return;
-  if (h->cur != h->nbins)
-    hs->fail_once("hooks: slice " + std::to_string(h->index) + " ended after " + std::to_string(h->cur) + " of " +
-                  std::to_string(h->nbins) + " bins");
-  else if (h->map_cur != h->nmaps)
-    hs->fail_once("hooks: slice " + std::to_string(h->index) + " reported " + std::to_string(h->map_cur) + " of its " +
-                  std::to_string(h->nmaps) + " significance maps");
-  else if (!hs->fs_have || hs->pf.slices[hs->fs_slice].picture_id != hs->pf.slices[h->index].picture_id)
-    hs->fail_once("hooks: slice " + std::to_string(h->index) + " was decoded without a frame_spec for its picture");
-}
-
-// frame_spec of slice i: the model's frames (update_frame_spec, recode.cpp:824-843) turn over where
-// the device's pictures do (its decode-order picture counter, which the two fields of a frame
-// share, as they share frame_num), and the size must be the picture's.  A caller that starts a new
-// frame inside one of the device's pictures is refused.  A caller whose frame_num stays the same
-// while the device starts a new picture is accepted only where the two pictures' slice headers
-// carry the same frame_num: the fork passes that syntax element, and consecutive pictures share it
-// after a non-reference picture (e.g. B(frame_num 4, nal_ref_idc 0) then P(4)) -- the model keeps
-// its per-picture frames there (frame_spec takes a picture counter).  Any other
-// repeat is a caller whose frames differ from the pictures it decodes.
-void check_frame_spec(avr_hooks_session* hs, int i, int frame_num, int w, int h) {
-  const avr::SliceInfo& s = hs->pf.slices[i];
-  const std::string where = "hooks: slice " + std::to_string(i) + ": frame_spec(" + std::to_string(frame_num) + ", " +
-                            std::to_string(w) + ", " + std::to_string(h) + ")";
-  if (w != s.h.mb_width || h != s.h.mb_height) {
-    hs->fail_once(where + " size differs from the picture's " + std::to_string(s.h.mb_width) + " x " +
-                  std::to_string(s.h.mb_height));
-    return;
-  }
-  if (hs->fs_have) {
-    const avr::SliceInfo& p = hs->pf.slices[hs->fs_slice];
-    const bool caller_new = frame_num != hs->fs_num || w != hs->fs_w || h != hs->fs_h;
-    const bool device_new = s.picture_id != p.picture_id || w != hs->fs_w || h != hs->fs_h;
-    const bool syntax_repeat = !caller_new && device_new && s.h.frame_num == p.h.frame_num;
-    if (caller_new != device_new && !syntax_repeat)
-      hs->fail_once(where + (device_new ? " keeps the frame of slice " : " starts a new frame after slice ") +
-                    std::to_string(hs->fs_slice) + ", the device's parse " +
-                    (device_new ? "starts a new picture" : "stays in the same picture"));
-  }
-  hs->fs_have = true;
-  hs->fs_num = frame_num, hs->fs_w = w, hs->fs_h = h, hs->fs_slice = i;
-}
-
-int hooks_finish_setup(avr_hooks_session* hs, const std::vector<avr::PbBlock>& blocks) {
-  if (int r = parse_file(hs->c, hs->original.data(), hs->original.size(), &hs->pf)) return r;
-  if (!coded_from_container(blocks, hs->pf.slices.size(), &hs->coded))
-    return fail(hs->c, AVR_ERR_FORMAT, "hooks: container blocks do not match the file's slices");
-  if (int r = run_traces(hs)) return r;
-  hs->slices.resize(hs->pf.slices.size());
-  return AVR_OK;
-}
-
-}  // namespace
-
-int avr_hooks_compress_begin(avr_ctx* c, const uint8_t* file, size_t n, int model, avr_hooks_session** out) {
-  if (!c || !file || !out) return AVR_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  std::unique_ptr<avr_hooks_session> hs(new avr_hooks_session);
-  hs->c = c;
-  hs->original.assign(file, file + n);
-  uint8_t* avrc = nullptr;
-  size_t avrc_len = 0;
-  if (int r = avr_compress_file(c, file, n, model, &avrc, &avrc_len)) return r;
-  hs->result.assign(avrc, avrc + avrc_len);
-  free(avrc);
-  std::vector<avr::PbBlock> blocks;
-  std::string version;
-  if (!avr::pb_parse(hs->result.data(), hs->result.size(), &blocks, &version))
-    return fail(c, AVR_ERR_FORMAT, "hooks: container does not parse");
-  if (int r = hooks_finish_setup(hs.get(), blocks)) return r;
-  *out = hs.release();
-  return AVR_OK;
-}
-
-int avr_hooks_decompress_begin(avr_ctx* c, const uint8_t* avrc, size_t n, avr_hooks_session** out,
-                               const uint8_t** stream, size_t* stream_len) {
-  if (!c || !avrc || !out) return AVR_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  std::unique_ptr<avr_hooks_session> hs(new (std::nothrow) avr_hooks_session);
-  if (!hs) return fail(c, AVR_ERR_OUT_OF_MEMORY, "host allocation failed");
-  hs->c = c;
-  hs->decompress = true;
-  {
-    // the container's model from its Metadata.version alone (no block list), inside guarded(): no
-    // exception crosses the C ABI
-    int m = 0;
-    bool split = false;   // a long-slice split container: regenerated whole at begin (its pieces are
-                          // a whole-file launch), as a reference-model one is
-    if (int r = guarded(c, [&]() -> int {
-          std::string version;
-          m = avr::pb_read_version(avrc, n, &version) ? avr::model_of_version(version) : 0;
-          if (m == AVR_MODEL_PARALLEL) {
-            std::vector<avr::PbBlock> blocks;
-            if (avr::pb_parse(avrc, n, &blocks, &version))
-              for (const auto& b : blocks) split = split || b.has_seams;
-          }
-          return AVR_OK;
-        }))
-      return r;
-    if (parallel_model(m) && !split && !getenv("AVR_HOOKS_EAGER")) {
-      // the parallel model's slices are independent: plan the container now, regenerate on demand
-      if (int r = guarded(c, [&]() -> int {
-            hs->lazy = true;
-            hs->model = m;
-            hs->original.assign(avrc, avrc + n);   // the container (the job's blocks point into it)
-            if (int e = decompress_setup(c, hs->original.data(), hs->original.size(), &hs->job, &hs->dplan)) return e;
-            hs->stream.assign(hs->job.stream.begin(), hs->job.stream.end());
-            if (int e = parse_file(c, hs->stream.data(), hs->stream.size(), &hs->pf)) return e;
-            if (!coded_from_container(hs->job.blocks, hs->pf.slices.size(), &hs->coded))
-              return fail(c, AVR_ERR_FORMAT, "hooks: container blocks do not match the file's slices");
-            const size_t ns = hs->pf.slices.size();
-            hs->plan_of.assign(ns, -1);
-            hs->block_of.assign(ns, -1);
-            size_t i = 0;
-            for (size_t bi = 0; bi < hs->job.blocks.size(); bi++) {
-              if (hs->job.blocks[bi].has_literal) continue;
-              hs->block_of[i] = (int)bi;
-              if (hs->job.blocks[bi].has_cabac) hs->plan_of[i] = hs->job.desc_of_block[bi];
-              i++;
-            }
-            for (size_t k = 0; k < ns; k++)
-              if (hs->coded[k] && hs->plan_of[k] < 0) return fail(c, AVR_ERR_FORMAT, "hooks: a coded block has no plan slice");
-            hs->regen_done.assign(ns, 0);
-            hs->regen.assign(ns, {});
-            hs->bins.assign(ns, {});
-            hs->maps.assign(ns, {});
-            hs->slices.resize(ns);
-            return AVR_OK;
-          }))
-        return r;
-      if (stream) *stream = hs->stream.data();
-      if (stream_len) *stream_len = hs->stream.size();
-      *out = hs.release();
-      return AVR_OK;
-    }
-  }
-  uint8_t* orig = nullptr;
-  size_t orig_len = 0;
-  if (int r = avr_decompress_file(c, avrc, n, &orig, &orig_len)) return r;
-  hs->original.assign(orig, orig + orig_len);
-  hs->result = hs->original;
-  free(orig);
-  std::vector<avr::PbBlock> blocks;
-  std::string version;
-  if (!avr::pb_parse(avrc, n, &blocks, &version)) return fail(c, AVR_ERR_FORMAT, "hooks: container does not parse");
-  // read_packet (recode.cpp:1359-1409)
-  uint64_t seq = 1;
-  for (auto& b : blocks) {
-    if (b.has_literal) {
-      hs->stream.insert(hs->stream.end(), b.literal, b.literal + b.literal_len);
-    } else if (b.has_cabac) {
-      uint8_t mk[8];
-      avr::surrogate_marker(seq++, mk);
-      hs->stream.insert(hs->stream.end(), mk, mk + 8);
-      hs->stream.insert(hs->stream.end(), (size_t)b.size - 8, (uint8_t)'X');
-    }
-  }
-  if (int r = hooks_finish_setup(hs.get(), blocks)) return r;
-  if (stream) *stream = hs->stream.data();
-  if (stream_len) *stream_len = hs->stream.size();
-  *out = hs.release();
-  return AVR_OK;
-}
-
-int avr_hooks_compress_stream_begin(avr_ctx* c, int model, avr_hooks_session** out) {
-  if (!c || !out) return AVR_ERR_INVALID_ARGUMENT;
-  if (!valid_model(model)) return AVR_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  avr_hooks_session* hs = new (std::nothrow) avr_hooks_session;
-  if (!hs) return AVR_ERR_OUT_OF_MEMORY;
-  hs->c = c;
-  hs->streaming = true;
-  hs->model = model;
-  *out = hs;
-  return AVR_OK;
-}
-
-int avr_hooks_feed(avr_hooks_session* hs, const uint8_t* bytes, size_t n) {
-  if (!hs || (!bytes && n) || !hs->streaming) return AVR_ERR_INVALID_ARGUMENT;
-  try {
-    hs->original.insert(hs->original.end(), bytes, bytes + n);
-  } catch (const std::bad_alloc&) {
-    return AVR_ERR_OUT_OF_MEMORY;
-  }
-  return AVR_OK;
-}
-
-void* avr_hook_init_decoder(void* opaque, void* /*cabac_context*/, const uint8_t* buf, int size) {
-  avr_hooks_session* hs = (avr_hooks_session*)opaque;
-  if (!hs) return nullptr;
-  close_live(hs);
-  if (hs->streaming) {
-    // the slice the decoder starts is in the bytes its demuxer has read (read_packet feeds them
-    // before the packet is decoded): parse what is new
-    int r = guarded(hs->c, [&] {
-      const int e = ingest(hs, false, hs->next_slice + 1);
-      grow_session(hs);
-      return e;
-    });
-    if (r) {
-      hs->fail_once("hooks: the bytes fed so far do not parse (" + std::to_string(r) + "): " + hs->c->err);
-      hs->next_slice++;
-      return nullptr;
-    }
-  }
-  if (hs->next_slice >= hs->pf.slices.size()) {
-    hs->fail_once(hs->streaming ? "hooks: init_decoder for a slice not yet fed" : "hooks: more slices than the file holds");
-    return nullptr;
-  }
-  const size_t i = hs->next_slice++;
-  if (hs->fs_pending) {   // the frame_spec made before this slice's decode
-    hs->fs_pending = false;
-    check_frame_spec(hs, (int)i, hs->pend_num, hs->pend_w, hs->pend_h);
-  }
-  const avr::SliceInfo& s = hs->pf.slices[i];
-  if (!buf || size < 0 || (size_t)size != s.size) {
-    hs->fail_once("hooks: slice " + std::to_string(i) + " size differs from the device's parse");
-    return nullptr;
-  }
-  if (hs->streaming) {
-    // find_next_coded_block (recode.cpp:1139-1145, 1275-1297) on the slice's own bytes: a slice the
-    // device can re-code gets hooks; the container (avr_hooks_end) may still store it skip_coded
-    hs->coded[i] = memcmp(buf, s.payload(), s.size) == 0 && recodable_candidate(s) ? 1 : 0;
-    if (hs->coded[i] && guarded(hs->c, [&] { return stream_device_work(hs, i); }) != AVR_OK) {
-      hs->fail_once("hooks: device trace of slice " + std::to_string(i) + " failed: " + hs->c->err);
-      return nullptr;
-    }
-  }
-  if (!hs->coded[i]) return nullptr;  // not re-coded: decode natively (recode.cpp:1139-1145)
-  if (hs->lazy && !hs->regen_done[i] && guarded(hs->c, [&] { return lazy_device_work(hs, i, true); }) != AVR_OK) {
-    hs->fail_once("hooks: device decode of slice " + std::to_string(i) + " failed: " + hs->c->err);
-    return nullptr;
-  }
-  if (hs->decompress) {
-    // recognize_coded_block (recode.cpp:1546-1573)
-    uint8_t mk[8];
-    avr::surrogate_marker(hs->next_marker++, mk);
-    if (size < 8 || memcmp(buf, mk, 8) != 0) {
-      hs->fail_once("hooks: invalid surrogate marker in slice " + std::to_string(i));
-      return nullptr;
-    }
-  } else if (memcmp(buf, s.payload(), s.size) != 0) {
-    hs->fail_once("hooks: slice " + std::to_string(i) + " payload differs from the file's");
-    return nullptr;
-  }
-  avr_hooks_slice& h = hs->slices[i];
-  h.sess = hs;
-  h.index = (int)i;
-  h.trace = hs->bins[i].data();
-  h.nbins = hs->bins[i].size() / 2;
-  h.cur = 0;
-  h.maps = hs->maps[i].data();
-  h.nmaps = hs->maps[i].size();
-  h.map_cur = 0;
-  hs->live = &h;
-  return &h;
-}
-
-static int hook_bin(void* slice, int kind, uint8_t* state) {
-  avr_hooks_slice* h = (avr_hooks_slice*)slice;
-  if (!h || !h->sess) return 0;
-  if (h->cur >= h->nbins) {
-    h->sess->fail_once("hooks: slice " + std::to_string(h->index) + " asked for more bins than it holds");
-    return 0;
-  }
-  const uint8_t t = h->trace[2 * h->cur], pre = h->trace[2 * h->cur + 1];
-  h->cur++;
-  const int bin = t & 1;
-  if (((t >> 1) & 3) != kind) {
-    h->sess->fail_once("hooks: slice " + std::to_string(h->index) + " bin " + std::to_string(h->cur - 1) +
-                       ": bin kind differs from the device's parse");
-    return bin;
-  }
-  if (state) {
-    if (*state != pre)
-      h->sess->fail_once("hooks: slice " + std::to_string(h->index) + " bin " + std::to_string(h->cur - 1) +
-                         ": context state differs from the device's parse");
-    *state = next_state(*state, bin);
-  }
-  return bin;
-}
-
-int avr_hook_get(void* slice, uint8_t* state) {
-  if (!state) {
-    if (slice && ((avr_hooks_slice*)slice)->sess) ((avr_hooks_slice*)slice)->sess->fail_once("hooks: get without a state");
-    return 0;
-  }
-  return hook_bin(slice, 0, state);
-}
-int avr_hook_get_bypass(void* slice) { return hook_bin(slice, 1, nullptr); }
-int avr_hook_get_terminate(void* slice) { return hook_bin(slice, 2, nullptr); }
-
-const uint8_t* avr_hook_skip_bytes(void* slice, int /*n*/) {
-  avr_hooks_slice* h = (avr_hooks_slice*)slice;
-  if (h && h->sess) h->sess->fail_once("hooks: skip_bytes (I_PCM) is not supported");
-  return nullptr;
-}
-
-void avr_hook_frame_spec(void* opaque, int frame_num, int mb_width, int mb_height) {
-  avr_hooks_session* hs = (avr_hooks_session*)opaque;
-  if (!hs) return;
-  avr_hooks_slice* h = hs->live;
-  if (h && h->cur < h->nbins) {   // inside a slice's decode: that slice's picture
-    check_frame_spec(hs, h->index, frame_num, mb_width, mb_height);
-    return;
-  }
-  if (hs->fs_pending && (hs->pend_num != frame_num || hs->pend_w != mb_width || hs->pend_h != mb_height))
-    hs->fail_once("hooks: two different frame_spec calls before one slice");
-  hs->fs_pending = true;
-  hs->pend_num = frame_num, hs->pend_w = mb_width, hs->pend_h = mb_height;
-}
-
-void avr_hook_mb_xy(void* opaque, int x, int y) {
-  avr_hooks_session* hs = (avr_hooks_session*)opaque;
-  if (!hs) return;
-  hs->mb_calls++;
-  hs->mb_x = x;
-  hs->mb_y = y;
-}
-
-void avr_hook_begin_sub_mb(void* opaque, int cat, int scan8index, int max_coeff, int is_dc, int chroma422) {
-  avr_hooks_session* hs = (avr_hooks_session*)opaque;
-  if (!hs || !hs->live) return;
-  avr_hooks_slice* h = hs->live;
-  if (h->sub_open) hs->fail_once("hooks: begin_sub_mb inside an open sub-macroblock");
-  h->sub_open = true;
-  const int a[5] = {cat, scan8index, max_coeff, is_dc, chroma422};
-  memcpy(h->sub_args, a, sizeof(a));
-}
-
-void avr_hook_end_sub_mb(void* opaque, int cat, int scan8index, int max_coeff, int is_dc, int chroma422) {
-  avr_hooks_session* hs = (avr_hooks_session*)opaque;
-  if (!hs || !hs->live) return;
-  avr_hooks_slice* h = hs->live;
-  const int a[5] = {cat, scan8index, max_coeff, is_dc, chroma422};
-  if (!h->sub_open || memcmp(h->sub_args, a, sizeof(a)) != 0)  // recode.cpp:185-189
-    hs->fail_once("hooks: end_sub_mb does not match begin_sub_mb");
-  h->sub_open = false;
-}
-
-// begin_coding_type(SIG_MAP) (recode.cpp:951-974) starts the model's significance-map keys: it
-// must come exactly before the device's map's first bin, under the device's macroblock (mb_xy)
-// and sub-macroblock (begin_sub_mb), with zigzag_index 0 (recode.cpp:961); end_coding_type right
-// after its last bin (recode.cpp:931-950).  Other coding types carry no device event.
-void avr_hook_begin_coding_type(void* opaque, int coding_type, int zigzag_index, int /*param0*/, int /*param1*/) {
-  avr_hooks_session* hs = (avr_hooks_session*)opaque;
-  if (!hs || !hs->live) return;
-  avr_hooks_slice* h = hs->live;
-  if (h->coding_type != AVR_PIP_UNKNOWN) hs->fail_once("hooks: nested begin_coding_type");
-  h->coding_type = coding_type;
-  if (coding_type != AVR_PIP_SIGNIFICANCE_MAP) return;
-  const std::string where = "hooks: slice " + std::to_string(h->index) + " bin " + std::to_string(h->cur) + ": ";
-  if (h->map_cur >= h->nmaps) {
-    hs->fail_once(where + "begin_coding_type(SIG_MAP) where the device's parse has no significance map");
-    return;
-  }
-  const HookMap& m = h->maps[h->map_cur];
-  if (h->cur != m.begin)
-    hs->fail_once(where + "begin_coding_type(SIG_MAP) where the device's map begins at bin " + std::to_string(m.begin));
-  else if (zigzag_index != 0)
-    hs->fail_once(where + "begin_coding_type(SIG_MAP) with zigzag_index != 0");
-  else if (hs->mb_x != m.x || hs->mb_y != m.y)
-    hs->fail_once(where + "significance map under mb_xy(" + std::to_string(hs->mb_x) + ", " + std::to_string(hs->mb_y) +
-                  "), the device's is (" + std::to_string(m.x) + ", " + std::to_string(m.y) + ")");
-  else if (!h->sub_open || memcmp(h->sub_args, m.sub, sizeof(m.sub)) != 0)
-    hs->fail_once(where + "significance map outside the device's sub-macroblock (cat " + std::to_string(m.sub[0]) +
-                  ", scan8 " + std::to_string(m.sub[1]) + ", max " + std::to_string(m.sub[2]) + ")");
-}
-
-void avr_hook_end_coding_type(void* opaque, int coding_type) {
-  avr_hooks_session* hs = (avr_hooks_session*)opaque;
-  if (!hs || !hs->live) return;
-  avr_hooks_slice* h = hs->live;
-  if (h->coding_type != coding_type) hs->fail_once("hooks: end_coding_type does not match begin_coding_type");
-  h->coding_type = AVR_PIP_UNKNOWN;
-  if (coding_type != AVR_PIP_SIGNIFICANCE_MAP || h->map_cur >= h->nmaps) return;
-  const HookMap& m = h->maps[h->map_cur++];
-  if (h->cur != m.end)
-    hs->fail_once("hooks: slice " + std::to_string(h->index) + " bin " + std::to_string(h->cur) +
-                  ": end_coding_type(SIG_MAP) where the device's map ends at bin " + std::to_string(m.end));
-}
-
-int avr_hooks_end(avr_hooks_session* hs, uint8_t** out, size_t* out_len) {
-  if (!hs || !out || !out_len) return AVR_ERR_INVALID_ARGUMENT;
-  close_live(hs);
-  if (hs->streaming) {
-    // the whole file is in: its last slices, and the container (recode.cpp:1102-1125).  The
-    // parallel model's blocks are final as each slice was traced (slices independent): the container
-    // is assembled from them.  The reference model's estimators chain across slices, so its
-    // container comes from one compress of the whole file.
-    if (int r = guarded(hs->c, [&] {
-          const int e = ingest(hs, true, 0);
-          grow_session(hs);
-          if (!e && hs->err.empty() && parallel_model(hs->model)) return stream_device_work(hs, 0);
-          return e;
-        }))
-      return r;
-    if (hs->err.empty()) {
-      uint8_t* avrc = nullptr;
-      size_t avrc_len = 0;
-      if (parallel_model(hs->model)) {
-        if (int r = guarded(hs->c, [&] {
-              std::vector<char> ok(hs->pf.slices.size(), 0);
-              std::vector<std::pair<const uint8_t*, size_t>> blobs(hs->pf.slices.size(), {nullptr, 0});
-              for (size_t i = 0; i < ok.size(); i++) {
-                ok[i] = recodable_candidate(hs->pf.slices[i]) && hs->block_status[i] == 0;
-                blobs[i] = {hs->blocks[i].data(), hs->blocks[i].size()};
-              }
-              const std::vector<SliceView> sv = views_of(hs->pf);
-              return emit_container(hs->original.data(), hs->original.size(), sv,
-                                    segment(hs->original.data(), hs->original.size(), sv, ok), blobs, hs->model,
-                                    &avrc, &avrc_len);
-            }))
-          return r;
-      } else if (int r = avr_compress_file(hs->c, hs->original.data(), hs->original.size(), hs->model, &avrc,
-                                           &avrc_len)) {
-        return r;
-      }
-      hs->result.assign(avrc, avrc + avrc_len);
-      free(avrc);
-    }
-  }
-  if (hs->lazy && hs->err.empty()) {
-    // the original file: literals and regenerated slices in block order (decompressor::run's output,
-    // recode.cpp:1338-1357), slices no init_decoder reached regenerated now
-    if (int r = guarded(hs->c, [&]() -> int {
-          if (int e = lazy_device_work(hs, 0, false, hs->pf.slices.size())) return e;
-          std::vector<uint8_t> o;
-          o.reserve(hs->stream.size());
-          size_t i = 0;
-          for (const avr::PbBlock& b : hs->job.blocks) {
-            if (b.has_literal) {
-              o.insert(o.end(), b.literal, b.literal + b.literal_len);
-              continue;
-            }
-            if (b.has_cabac) o.insert(o.end(), hs->regen[i].begin(), hs->regen[i].end());
-            i++;
-          }
-          hs->result.swap(o);
-          return AVR_OK;
-        }))
-      return r;
-  }
-  if (hs->next_slice != hs->pf.slices.size())
-    hs->fail_once("hooks: " + std::to_string(hs->next_slice) + " of " + std::to_string(hs->pf.slices.size()) +
-                  " slices were decoded");
-  if (!hs->err.empty()) return fail(hs->c, AVR_ERR_FORMAT, hs->err);
-  *out = (uint8_t*)malloc(hs->result.size() ? hs->result.size() : 1);
-  if (!*out) return AVR_ERR_OUT_OF_MEMORY;
-  memcpy(*out, hs->result.data(), hs->result.size());
-  *out_len = hs->result.size();
-  return AVR_OK;
-}
-
-void avr_hooks_destroy(avr_hooks_session* hs) { delete hs; }
-
-// Debug (tests, host only; not part of include/avrecode.h): how many slices a decompress session
-// has regenerated on the device so far (a lazy parallel-model session: those init_decoder reached,
-// in batches; -1: an eager session, which regenerated the whole file at begin).
-extern "C" int avr_debug_hooks_regenerated(const avr_hooks_session* hs) {
-  if (!hs || !hs->decompress) return AVR_ERR_INVALID_ARGUMENT;
-  if (!hs->lazy) return -1;
-  int k = 0;
-  for (const char d : hs->regen_done) k += d ? 1 : 0;
-  return k;
-}
-
-// Debug (tests, host only; not part of include/avrecode.h): the slices a streaming session's
-// incremental parser finds when `file` is fed in pieces ending at cuts[0] < ... < cuts[ncuts - 1] = n
-// (incremental = 1; after each piece the parser is asked for one slice more than it holds when
-// provisional = 1, as a decoder's next init_decoder would), or that parse_file finds in the whole
-// file (incremental = 0).  out: 4 u64 per slice (NAL offset, NAL size, payload size, picture id).
-// Returns the slice count (at most cap written), or < 0.
-extern "C" int avr_debug_stream_slices(const uint8_t* file, size_t n, const uint64_t* cuts, int ncuts, int incremental,
-                                       int provisional, uint64_t* out, int cap) {
-  if (!file || (incremental && (!cuts || ncuts <= 0)) || (!out && cap)) return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    avr_hooks_session hs;
-    hs.streaming = true;
-    if (incremental) {
-      size_t fed = 0;
-      for (int k = 0; k < ncuts; k++) {
-        const size_t end = std::min<size_t>(n, cuts[k]);
-        if (end > fed) hs.original.insert(hs.original.end(), file + fed, file + end);
-        fed = std::max(fed, end);
-        if (int r = ingest(&hs, false, 0)) return r;
-        if (provisional)
-          if (int r = ingest(&hs, false, hs.pf.slices.size() + 1)) return r;
-      }
-      if (fed < n) hs.original.insert(hs.original.end(), file + fed, file + n);
-      if (int r = ingest(&hs, true, 0)) return r;
-    } else if (int r = parse_file(nullptr, file, n, &hs.pf)) {
-      return r;
-    }
-    const int cnt = (int)hs.pf.slices.size();
-    for (int i = 0; i < cnt && i < cap; i++) {
-      const avr::SliceInfo& si = hs.pf.slices[i];
-      out[4 * i] = si.nal_offset, out[4 * i + 1] = si.nal_size, out[4 * i + 2] = si.size;
-      out[4 * i + 3] = (uint64_t)si.picture_id;
-    }
-    return cnt;
-  });
 }

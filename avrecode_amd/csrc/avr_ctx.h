@@ -1,0 +1,103 @@
+// The device context of the C ABI and what the translation units that launch device work share
+// (internal; includes HIP -- the host-only side is avr_host.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "avr_host.h"
+#include "avr_kernels.h"
+
+namespace avr_host {
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  // zero: a fresh allocation starts zeroed (the estimator tables rely on it, see kEstLogN)
+  hipError_t reserve(size_t n, bool zero = false) {
+    if (n <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipMalloc(&p, n);
+    if (e == hipSuccess && zero) e = hipMemset(p, 0, n);
+    if (e == hipSuccess && zero) e = hipDeviceSynchronize();
+    if (e == hipSuccess) cap = n;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  ~DevBuf() { release(); }
+  template <class T>
+  T* as() const {
+    return (T*)p;
+  }
+};
+
+}  // namespace avr_host
+
+struct avr_ctx : avr_host::ErrSink {
+  using DevBuf = avr_host::DevBuf;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  DevBuf tables, est, frames, frame_meta, in, out, descs, res, packed, offsets, order;
+  DevBuf queue;                                          // largest-first slice queue (launch_slices)
+  DevBuf rm_goff, rm_counts, rm_stop, rm_off, rm_ops;   // parallel reference-model compress
+  DevBuf regen, dec_descs, res_d, verdict;               // compress-side roundtrip check
+  DevBuf file_first, file_op_off;                        // reference model over several files
+  // the parallel model's long-slice split (split_compress / split_decompress): its own stream, so the
+  // long slices' first pass overlaps the rest of the batch, and its own estimator scratch
+  hipStream_t split_stream = nullptr;
+  DevBuf sp_in, sp_out, sp_descs, sp_res, sp_ctl, sp_recs, sp_snapn, sp_est, sp_in2, sp_out2;
+  size_t split_bytes = 0;   // avr_set_split_bytes / AVR_SPLIT_BYTES (0: no split)
+  // avr_decompress_pieces: the batch's PieceCtl array, host (alive while its upload is in flight) and device
+  std::vector<avr::PieceCtl> pc_host;
+  DevBuf pc_ctl;
+  // a batch holding both progressive and field slices runs its field kernel beside the progressive
+  // one (avr::FieldLane); AVR_FIELD_LANE=0 keeps the two in one stream, one after the other
+  hipStream_t fld_stream = nullptr;
+  hipEvent_t fld_ev[2] = {nullptr, nullptr};
+  avr::FieldLane field_lane() const {
+    avr::FieldLane l;
+    if (fld_stream) l.stream = fld_stream, l.fork = fld_ev[0], l.join = fld_ev[1];
+    return l;
+  }
+  bool round_robin = false;   // placement probe passed: the CU schedule (order) may be used
+  int* order_or_null() { return round_robin ? order.as<int>() : nullptr; }
+  // phase breakdown of the current / last whole-file call (avr_phase_times): run_plan adds the
+  // device phases (HIP events ev[0..3] around its uploads, kernels and downloads) and its own wall
+  // time (plan_wall); the file paths add the host phases
+  avr_phase_times phase{};
+  double plan_wall = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~avr_ctx() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (split_stream) (void)hipStreamDestroy(split_stream);
+    for (auto& e : fld_ev)
+      if (e) (void)hipEventDestroy(e);
+    if (fld_stream) (void)hipStreamDestroy(fld_stream);
+  }
+};
+
+#define HIP_TRY(c, expr)                                                                              \
+  do {                                                                                                \
+    hipError_t _e = (expr);                                                                           \
+    if (_e != hipSuccess) return avr_host::fail(c, AVR_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(_e)); \
+  } while (0)
+
+namespace avr_host {
+
+// Upload plan, run the slice kernel over it (one launch, see launch_slices), download results and outputs.
+// verify (parallel compress only): also decompress every slice's output on the device, apply the
+// last-byte rule and compare with the payload (avr_roundtrip_slices); a slice whose output does not
+// regenerate its payload gets status kStatusNoRoundtrip, so no container ever holds a block that
+// cannot be decompressed.
+// out_host: a std::vector<uint8_t> or a Bytes (not zero-filled first: the download overwrites it)
+// (defined in avr_api.cpp and instantiated there for both)
+template <class HostBuf>
+int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_slice_result>* res,
+             HostBuf* out_host, bool verify = false, uint32_t flags = 0);
+
+}  // namespace avr_host

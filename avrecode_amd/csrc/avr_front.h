@@ -112,7 +112,7 @@ struct PbBlock {
   size_t cabac_len = 0;
   std::string last_byte;
   // field 16, this library's own (not in recode.proto): the parallel model's long-slice split of a
-  // coded block (avr_api.cpp "seams"; zlib, the layout oracle/avr_oracle.h avr_seams_encode names)
+  // coded block (avr_seams.cpp; zlib, the layout oracle/avr_oracle.h avr_seams_encode names)
   bool has_seams = false;
   const uint8_t* seams = nullptr;
   size_t seams_len = 0;

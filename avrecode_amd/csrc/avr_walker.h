@@ -3134,9 +3134,9 @@ AVR_FI void parallel_slice(uint8_t* smem, const EngineTables* G, const avr_slice
 // The long-slice split's launches (avr_kernels.h SplitArgs): progressive frame slices and pieces of
 // the parallel model on arithmetic_code<uint64_t, uint8_t>, the model row in LDS; each workgroup
 // takes descriptors blockIdx.x, blockIdx.x + gridDim.x, ... (a grid of at most the resident slots:
-// one estimator scratch per workgroup).  MODE_TRACE: the cut scan -- the CABAC parse of whole long
-// slices (one wave, no model, no output) taking the cut records (PieceCtl::snap).  Compress: the
-// pieces (seam >= 0: started from a record, n_mbs > 0: stopped at the next cut).  Decompress: the
+// one estimator scratch per workgroup).  Compress: whole long slices in a single walk, each cut as
+// it is walked -- the cut records taken (PieceCtl::snap) and the model started afresh at every cut;
+// or pieces (seam >= 0: started from a record, n_mbs > 0: stopped at the next cut).  Decompress: the
 // pieces, from records the host wrote (the container's seams).
 template <int MODE>
 __global__ __launch_bounds__(192, 4) void slices_split_kernel(const EngineTables* G, const avr_slice_desc* descs, int n,

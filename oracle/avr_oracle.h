@@ -302,7 +302,7 @@ long avr_oracle_slices_p(const uint8_t *file, size_t n, long lo, long hi, int ch
 
 /* ------------------------------------------------------------------------------------------ */
 /* Long-slice split of the parallel model (NOT part of the reference: this library's own format,  */
-/* restated here as the checker; avrecode_amd/csrc/avr_api.cpp "seams").  A progressive-frame     */
+/* restated here as the checker; avrecode_amd/csrc/avr_seams.cpp).  A progressive-frame           */
 /* slice is cut at macroblock-row starts into pieces, each re-coded with a fresh parallel model  */
 /* (its estimators reset, its upper row's model bytes zero, as at a slice start), so that the     */
 /* pieces decompress side by side.  A cut (a "seam") comes at the first row start with at least   */

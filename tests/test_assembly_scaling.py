@@ -4,7 +4,7 @@ find_next_coded_block_and_emit_literal (recode.cpp:1275-1297) searches each code
 payload in the file after the previous coded block (memmem).  A payload whose NAL had
 emulation-prevention bytes occurs nowhere, and memmem then scans to the end of the file -- once per
 such slice, O(misses x file): the full-size 4.47 GB configs[3] stream did not get through one step
-in 13 minutes.  avr_api.cpp's find_payload gives memmem's answer from an index of the file's
+in 13 minutes.  avr_assemble.cpp's find_payload gives memmem's answer from an index of the file's
 00 00 0y trigrams instead.  Checked here:
 
 * the containers equal the ones the reference's search gives (Python bytes.find from the previous

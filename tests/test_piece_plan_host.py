@@ -3,7 +3,7 @@ shard.collapse_units, the unit path of shard.sharded_decompress): CPU only.
 
 The containers are the oracle's (recode_oracle compress -p with AVR_SPLIT_BYTES), and the cuts are
 read here from the seams fields themselves -- u32 raw length, zlib, the layout written down at
-avr_api.cpp's seams_encode -- never from the plan under test:
+avr_seams.cpp's seams_encode -- never from the plan under test:
 
 * the plan lists the expected coded slices and units, each unit's stream is its span of Block.cabac,
   its avr_piece and its seam record carry the field's values, its output fits the work buffer;
@@ -29,7 +29,7 @@ from avrecode_amd import shard
 
 FIX = ROOT / "tests" / "fixtures"
 KEEP_ALL = 0xFFFFFFFF
-# SeamRec's head (avr_kernels.h): the decompress side reads first_mb, last_dqp_nz, ce_*, q
+# SeamRec's head (avr_records.h): the decompress side reads first_mb, last_dqp_nz, ce_*, q
 SEAM_HEAD = np.dtype([("first_mb", "<u4"), ("last_dqp_nz", "<u4"), ("cd", "<u4", (4,)), ("ce_low", "<u4"),
                       ("ce_range", "<u4"), ("ce_outstanding", "<u4"), ("ce_cache", "<u4"), ("ce_queue", "<i4"),
                       ("q", "<u4")])
