@@ -24,7 +24,7 @@ __all__ = [
     "SLICE_DESC", "PIECE", "KEEP_ALL",
     "SLICE_RESULT", "SynthParams", "lib", "parse_stream", "assemble_container", "neighbor_tables",
     "plan_decompress", "splice_container", "container_model", "source_sha", "library_path", "EXPORTED_SYMBOLS",
-    "seams_of_container",
+    "seams_of_container", "SPLIT_SLOT", "SplitPlan", "split_plan", "seams_build",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = (
     "avr_plan_decompress", "avr_splice_container", "avr_roundtrip_files", "avr_slice_kernel",
     "avr_compress_chain_range", "avr_decompress_chain_range", "avr_set_split_bytes", "avr_get_split_bytes",
     "avr_dec_plan_load_pieces", "avr_dec_plan_units", "avr_dec_plan_recs", "avr_decompress_pieces", "avr_pack_pieces",
+    "avr_split_plan", "avr_seams_build", "avr_assemble_container_seams", "avr_assemble_container_seams_parsed",
+    "avr_compress_split_slices", "avr_stage_pieces", "avr_verify_units",
 )
 
 # avr_slice_desc / avr_slice_result (include/avrecode.h), C layout
@@ -83,7 +85,16 @@ CODING_TYPES = ("PIP_UNKNOWN", "PIP_UNREACHABLE", "PIP_SIGNIFICANCE_MAP", "PIP_S
 PIECE = np.dtype([("seam", "<i4"), ("n_mbs", "<u4"), ("slice", "<i4"), ("keep", "<u4")], align=True)
 KEEP_ALL = 0xFFFFFFFF    # avr_piece.keep of a last piece or a whole slice
 SLICE_NO_END = -9        # AVR_SLICE_NO_END
-assert SLICE_DESC.itemsize == 96 and SLICE_RESULT.itemsize == 40 and PIECE.itemsize == 16
+SLICE_CODER = -10        # AVR_SLICE_CODER
+SLICE_OVERFLOW = -12     # AVR_SLICE_OVERFLOW
+# avr_split_slot (include/avrecode.h): a slice's cut records in a split compress batch; (-1, 0): none
+SPLIT_SLOT = np.dtype([("first", "<i4"), ("cap", "<u4")], align=True)
+# the head of a seam record in the split kernels' device layout (SeamRec, csrc/avr_records.h); then
+# 1024 context bytes and 40 edge bytes per macroblock column
+SEAM_HEAD = np.dtype([("first_mb", "<u4"), ("last_dqp_nz", "<u4"), ("cd", "<u4", (4,)), ("ce_low", "<u4"),
+                      ("ce_range", "<u4"), ("ce_outstanding", "<u4"), ("ce_cache", "<u4"), ("ce_queue", "<i4"),
+                      ("q", "<u4")])
+assert SLICE_DESC.itemsize == 96 and SLICE_RESULT.itemsize == 40 and PIECE.itemsize == 16 and SPLIT_SLOT.itemsize == 8
 
 
 class AvrError(RuntimeError):
@@ -207,6 +218,14 @@ def lib() -> ctypes.CDLL:
     L.avr_dec_plan_recs.argtypes = [vp, vp, sz]
     L.avr_decompress_pieces.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, sz, vp, vp, vp, vp]
     L.avr_pack_pieces.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.avr_split_plan.argtypes = [vp, i32, sz, vp, vp, pi, psz, pi]
+    L.avr_seams_build.argtypes = [vp, i32, vp, sz, vp, vp, vp, vp, i32, vp, sz, sz, i32, vp, pp, psz, vp, vp]
+    L.avr_assemble_container_seams.argtypes = [vp, sz, i32, i32, vp, vp, sz, vp, vp, vp, sz, vp, vp, pp, psz]
+    L.avr_assemble_container_seams_parsed.argtypes = [vp, sz, i32, vp, i32, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp,
+                                                      pp, psz]
+    L.avr_compress_split_slices.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32, sz, vp, vp, vp]
+    L.avr_stage_pieces.argtypes = [vp, vp, vp, i32, vp, sz, vp, sz, vp, vp, vp]
+    L.avr_verify_units.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.avr_container_model.argtypes = [vp, sz, pi]
     L.avr_synthesize_stream.argtypes = [vp, ctypes.POINTER(_SynthParams), i32, pp, psz]
     L.avr_container_describe.argtypes = [vp, sz, pp, pp, psz]
@@ -495,16 +514,83 @@ def container_bound(n_file: int, n_slices: int, recoded_bytes: int) -> int:
     return int(n_file) + int(recoded_bytes) + 64 * (int(n_slices) + 2)
 
 
+@dataclass
+class SplitPlan:
+    """avr_split_plan's answer for a batch of descriptors at one split_bytes."""
+    slots: np.ndarray          # SPLIT_SLOT[n]: (first, cap) of a candidate's cut records, (-1, 0) otherwise
+    out_capacity: np.ndarray   # uint32[n]: the output space a candidate's split walk needs, 0 otherwise
+    n_recs: int                # cut records in all
+    rec_stride: int            # bytes per record: the widest candidate's
+    n_candidates: int
+
+    @property
+    def candidate(self) -> np.ndarray:
+        return self.slots["first"] >= 0
+
+
+def split_plan(descs, split_bytes: int) -> SplitPlan:
+    """Which descriptors the whole-file MODEL_PARALLEL compress would take through the split walk at
+    split_bytes, and the cut-record slots and output space that walk needs (avr_split_plan: a
+    progressive frame, at most 288 macroblocks wide, of at least 1.5 split_bytes payload bytes;
+    descs' coded field is not read).  Host only."""
+    d = np.ascontiguousarray(descs, dtype=SLICE_DESC)
+    n = len(d)
+    slots = np.zeros(n, dtype=SPLIT_SLOT)
+    cap = np.zeros(n, dtype=np.uint32)
+    nr, nc, rs = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    if split_bytes < 0:
+        raise ValueError("split_plan: split_bytes < 0")
+    r = lib().avr_split_plan(d.ctypes.data, n, int(split_bytes), slots.ctypes.data, cap.ctypes.data, ctypes.byref(nr),
+                             ctypes.byref(rs), ctypes.byref(nc))
+    if r != AVR_OK:
+        raise AvrError(r, "avr_split_plan failed")
+    return SplitPlan(slots, cap, nr.value, rs.value, nc.value)
+
+
+def seams_build(descs, arena, res, slots, cuts, piece_end, recs, rec_stride: int, check_cuts: bool = True):
+    """The Block-field-16 bytes of the cut slices of a split compress batch from what was read back
+    from the device (avr_seams_build): (status int32[n], [bytes per slice, b"" without a cut or with
+    status != 0]).  descs / arena: the host descriptors and payloads; res SLICE_RESULT[n]; slots
+    SPLIT_SLOT[n]; cuts uint32[n]; piece_end uint32[n_recs]; recs: n_recs records of rec_stride bytes.
+    check_cuts: a cut whose re-encoder state is not the host's restatement gives its slice
+    SLICE_CODER.  Raises AvrError(-1) for arrays that do not fit each other.  Host only."""
+    d = np.ascontiguousarray(descs, dtype=SLICE_DESC)
+    n = len(d)
+    rs = np.ascontiguousarray(res, dtype=SLICE_RESULT)
+    sl = np.ascontiguousarray(slots, dtype=SPLIT_SLOT)
+    cu = np.ascontiguousarray(cuts, dtype=np.uint32)
+    pe = np.ascontiguousarray(piece_end, dtype=np.uint32)
+    rc = np.ascontiguousarray(recs, dtype=np.uint8).reshape(-1)
+    ar = np.ascontiguousarray(arena, dtype=np.uint8).reshape(-1)
+    if not (len(rs) == len(sl) == len(cu) == n):
+        raise ValueError("seams_build: one result / slot / cut count per descriptor")
+    status = np.zeros(n, dtype=np.int32)
+    offs = np.zeros(n, dtype=np.uint64)
+    lens = np.zeros(n, dtype=np.uint32)
+    blob, blen = ctypes.c_void_p(), ctypes.c_size_t()
+    P = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+    r = lib().avr_seams_build(P(d), n, ar.ctypes.data, ar.nbytes, P(rs), P(sl), P(cu), P(pe), len(pe), P(rc), rc.nbytes,
+                              int(rec_stride), 1 if check_cuts else 0, P(status), ctypes.byref(blob),
+                              ctypes.byref(blen), P(offs), P(lens))
+    if r != AVR_OK:
+        raise AvrError(r, "avr_seams_build failed")
+    b = _take(blob, blen.value) if blob.value else b""
+    return status, [b[int(o):int(o) + int(ln)] for o, ln in zip(offs, lens)]
+
+
 def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, lens: np.ndarray,
                        model: int = MODEL_PARALLEL, ps: "ParsedStream | None" = None, as_array: bool = False,
-                       out: "np.ndarray | None" = None):
+                       out: "np.ndarray | None" = None, seams=None):
     """Recoded container from per-slice outputs gathered from the ranks (avr_assemble_container; with ps =
     parse_stream(data) already in hand, avr_assemble_container_parsed: no second parse).  recoded:
     bytes or a uint8 array.  model: the model / coder the outputs were made with (PARALLEL, PARALLEL32,
     or CHAINED for Context.compress_chain_range's outputs).  as_array: the container
     as a uint8 array over the library's buffer (no copy into bytes).  out (with ps): a uint8 array
     the container is written into (avr_assemble_container_into; container_bound() bytes suffice);
-    returns the view of it that holds the container.  Host only."""
+    returns the view of it that holds the container.  seams: (blob, offsets, lens) -- slice k's
+    Block field 16 is blob[offsets[k] : offsets[k] + lens[k]], length 0 for none -- or a list of one
+    bytes object per slice (b"" for none): the container of a split compress
+    (avr_assemble_container_seams; MODEL_PARALLEL only, not with out).  Host only."""
     L = lib()
     p, n, keep = _buf(data)
     st = np.ascontiguousarray(status, dtype=np.int32)
@@ -512,6 +598,35 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
     ln = np.ascontiguousarray(lens, dtype=np.uint32)
     rp, rn, keep2 = _buf(recoded)
     res, olen = ctypes.c_void_p(), ctypes.c_size_t()
+    if seams is not None:
+        if out is not None:
+            raise ValueError("assemble_container: seams cannot be combined with out")
+        if isinstance(seams, list):
+            sl = np.array([len(s) for s in seams], dtype=np.uint32)
+            so = (np.cumsum(sl, dtype=np.uint64) - sl).astype(np.uint64)
+            sb = b"".join(seams)
+        else:
+            sb, so, sl = seams
+            so = np.ascontiguousarray(so, dtype=np.uint64)
+            sl = np.ascontiguousarray(sl, dtype=np.uint32)
+        if len(so) != len(st) or len(sl) != len(st) or len(of) != len(st) or len(ln) != len(st):
+            raise ValueError("assemble_container: status / offsets / lens / seams need one entry per slice")
+        sp, sn, keep3 = _buf(sb)
+        if ps is not None:
+            dd = np.ascontiguousarray(ps.descs)
+            if len(dd) != len(st):
+                raise ValueError("assemble_container: status / offsets / lens need one entry per parsed slice")
+            r = L.avr_assemble_container_seams_parsed(p, n, model, dd.ctypes.data, len(dd), ps.arena.ctypes.data,
+                                                      ps.arena.nbytes, st.ctypes.data, rp, rn, of.ctypes.data,
+                                                      ln.ctypes.data, sp, sn, so.ctypes.data, sl.ctypes.data,
+                                                      ctypes.byref(res), ctypes.byref(olen))
+        else:
+            r = L.avr_assemble_container_seams(p, n, model, len(st), st.ctypes.data, rp, rn, of.ctypes.data,
+                                               ln.ctypes.data, sp, sn, so.ctypes.data, sl.ctypes.data,
+                                               ctypes.byref(res), ctypes.byref(olen))
+        if r != AVR_OK:
+            raise AvrError(r, "avr_assemble_container_seams failed")
+        return _take_array(res, olen.value) if as_array else _take(res, olen.value)
     if out is not None:
         if ps is None or out.dtype != np.uint8 or not out.flags.c_contiguous:
             raise ValueError("assemble_container: out needs ps and a contiguous uint8 array")
@@ -813,6 +928,45 @@ class Context:
         P = self._ptr
         self._check(lib().avr_pack_pieces(self._h, P(d_desc), P(d_pieces), P(d_res), n, P(d_out), P(d_packed),
                                           P(d_offsets), P(d_kept), P(d_status), self._stream(stream)), "pack_pieces")
+
+    # the split compress of slice batches (ABI 8); the two host steps need no context
+    split_plan = staticmethod(split_plan)
+    seams_build = staticmethod(seams_build)
+
+    def compress_split_slices(self, d_desc, n, max_w, max_h, d_in, d_out, d_res, slots, split_bytes, d_recs, n_recs,
+                              rec_stride, d_cuts, d_piece_end, stream=None):
+        """avr_compress_split_slices: the split walk over a batch of progressive MODEL_PARALLEL slices,
+        each cut as it is walked.  slots: split_plan's SPLIT_SLOT array on the HOST (checked there
+        before the launch); d_recs / d_cuts (uint32[n]) / d_piece_end (uint32[n_recs]): what the walk
+        writes, on the device, the latter two zeroed on the stream first."""
+        sl = np.ascontiguousarray(slots, dtype=SPLIT_SLOT)
+        if len(sl) != n:
+            raise ValueError("compress_split_slices: one SPLIT_SLOT per slice")
+        P = self._ptr
+        self._check(lib().avr_compress_split_slices(self._h, P(d_desc), n, max_w, max_h, P(d_in), P(d_out), P(d_res),
+                                                    sl.ctypes.data, int(split_bytes), P(d_recs), n_recs, rec_stride,
+                                                    P(d_cuts), P(d_piece_end), self._stream(stream)),
+                    "compress_split_slices")
+
+    def stage_pieces(self, d_desc, d_src, n, d_out, out_len, d_arena, arena_cap, d_offsets, d_status, stream=None):
+        """avr_stage_pieces: unit k's stream (d_desc[k].payload_size bytes at d_out + d_src[k], any
+        alignment) copied to d_arena + d_offsets[k], 16-byte aligned with at least 16 zero bytes
+        after it; d_desc[k].payload_offset / read_limit set; d_status[k] SLICE_OVERFLOW when it does
+        not fit out_len / arena_cap."""
+        P = self._ptr
+        self._check(lib().avr_stage_pieces(self._h, P(d_desc), P(d_src), n, P(d_out), int(out_len), P(d_arena),
+                                           int(arena_cap), P(d_offsets), P(d_status), self._stream(stream)),
+                    "stage_pieces")
+
+    def verify_units(self, d_desc, d_res_c, n, d_first, n_units, d_in, d_packed, d_offsets, d_kept, d_unit_status,
+                     d_verdict, stream=None):
+        """avr_verify_units: d_verdict[k] (1 bit-exact, 0 mismatch, 2 not coded) of slice k from the
+        packed kept bytes of its units [d_first[k], d_first[k + 1]) (pack_pieces' outputs) against its
+        payload in d_in, under the last-byte rule."""
+        P = self._ptr
+        self._check(lib().avr_verify_units(self._h, P(d_desc), P(d_res_c), n, P(d_first), n_units, P(d_in), P(d_packed),
+                                           P(d_offsets), P(d_kept), P(d_unit_status), P(d_verdict),
+                                           self._stream(stream)), "verify_units")
 
     def pack_outputs(self, d_desc, d_res, n, d_out, d_packed, d_offsets, stream=None):
         P = self._ptr

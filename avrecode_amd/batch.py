@@ -228,6 +228,174 @@ class UnitBatch:
         return self.d_res.cpu().numpy().reshape(-1).view(SLICE_RESULT)[: self.n]
 
 
+class SplitBatch:
+    """A rank's split candidates (split_plan of ps.descs at split_bytes: every slice of ps must be one)
+    on the device, compressed as the whole-file MODEL_PARALLEL compress compresses them: each slice
+    cut as it is walked, its pieces' streams one after the other in d_out.  roundtrip() runs, on one
+    stream,
+      compress()    avr_compress_split_slices
+      read_back()   waits for it; cuts, piece ends, records and results to the host, where the unit
+                    descriptors and the PIECE array of every piece are built (the streams stay on the
+                    device); a slice whose cut count or piece ends are not a walk's gets SLICE_CODER
+      stage()       avr_stage_pieces: the pieces' streams into the aligned layout the decompress reads
+      decompress()  avr_decompress_pieces over all units
+      pack()        avr_pack_pieces: every piece cut down to its share of its slice
+      verify()      avr_verify_units: d_verdict per slice
+    and the halves are callable one by one in that order.  recoded() / verdicts() / seams() give the
+    host what a container needs."""
+
+    def __init__(self, ctx: Context, ps: ParsedStream, split_bytes: int, device=None):
+        from . import split_plan
+        self.ctx, self.ps, self.split_bytes = ctx, ps, int(split_bytes)
+        self.device = dev = torch.device("cuda", ctx.device) if device is None else device
+        self.n = n = len(ps.descs)
+        self.plan = plan = split_plan(ps.descs, split_bytes)
+        if plan.n_candidates != n:
+            raise ValueError("SplitBatch: every slice of the batch must be a split candidate (split_plan)")
+        d = ps.descs.copy()
+        d["out_capacity"] = plan.out_capacity
+        room = (d["out_capacity"].astype(np.int64) + 15) & ~15
+        d["out_offset"] = np.cumsum(room) - room
+        self.descs = d
+        self.work_len = int(room.sum())
+        self.max_w = int(d["mb_width"].max()) if n else 1
+        self.d_desc = _dev_bytes(d, dev)
+        self.d_in = _dev_bytes(ps.arena, dev)
+        self.d_out = torch.zeros(self.work_len + 16, dtype=torch.uint8, device=dev)
+        self.d_res_c = torch.zeros(max(1, n) * SLICE_RESULT.itemsize, dtype=torch.uint8, device=dev)
+        self.d_recs = torch.zeros(plan.n_recs * plan.rec_stride + 64, dtype=torch.uint8, device=dev)
+        self.d_cuts = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        self.d_piece_end = torch.zeros(max(1, plan.n_recs), dtype=torch.int32, device=dev)
+        self.d_verdict = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        self.nu = 0
+
+    def compress(self, stream=None):
+        p = self.plan
+        self.ctx.compress_split_slices(self.d_desc, self.n, self.max_w, self.ps.max_mb_height, self.d_in, self.d_out,
+                                       self.d_res_c, p.slots, self.split_bytes, self.d_recs, p.n_recs, p.rec_stride,
+                                       self.d_cuts, self.d_piece_end, stream)
+
+    def read_back(self, stream=None):
+        from . import SEAM_HEAD, SLICE_CODER
+        (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
+        p, n = self.plan, self.n
+        self.res = self.d_res_c.cpu().numpy().view(SLICE_RESULT)[:n].copy()
+        self.cuts = self.d_cuts.cpu().numpy().view(np.uint32)[:n].copy()
+        self.piece_end = self.d_piece_end.cpu().numpy().view(np.uint32)[:p.n_recs].copy()
+        self.recs = self.d_recs.cpu().numpy()[:p.n_recs * p.rec_stride].copy()
+        # what the walk itself can fail (split_finish's first check): too many cuts, piece ends that
+        # are not the stream's
+        self.status = self.res["status"].astype(np.int32)
+        rows, pc, src, first = [], [], [], [0]   # per unit: (slice, first_mb, stream length), PIECE, source
+        for k in range(n):
+            f, cap, nc = int(p.slots[k]["first"]), int(p.slots[k]["cap"]), int(self.cuts[k])
+            size, mb0 = int(self.descs[k]["payload_size"]), int(self.descs[k]["first_mb"])
+            if self.status[k] == 0:
+                ends = [int(e) for e in self.piece_end[f:f + nc + 1]] if nc < cap else None
+                head = self.recs.reshape(-1, p.rec_stride)[f:f + nc, :SEAM_HEAD.itemsize].copy().view(SEAM_HEAD).reshape(-1)
+                mbs = [mb0] + [int(x) for x in head["first_mb"]]
+                qs = [0] + [int(x) for x in head["q"]]
+                # cuts move forward in macroblocks and in bytes of the payload
+                if (ends is None or ends != sorted(ends) or ends[-1] != int(self.res[k]["out_len"])
+                        or any(y <= x for x, y in zip(mbs, mbs[1:])) or any(y <= x for x, y in zip(qs, qs[1:]))
+                        or qs[-1] >= size):
+                    self.status[k] = SLICE_CODER
+            if self.status[k] == 0:
+                for i in range(nc + 1):
+                    last = i == nc
+                    begin = ends[i - 1] if i else 0
+                    rows.append((k, mbs[i], ends[i] - begin))
+                    pc.append((f + i - 1 if i else -1, 0 if last else mbs[i + 1] - mbs[i], k,
+                               KEEP_ALL if last else qs[i + 1] - qs[i]))
+                    src.append(int(self.descs[k]["out_offset"]) + begin)
+            first.append(len(rows))
+        self.nu = nu = len(rows)
+        self.units = self.descs[[r[0] for r in rows]].copy() if nu else np.zeros(0, SLICE_DESC)
+        self.pieces = np.array(pc, dtype=PIECE) if nu else np.zeros(0, PIECE)
+        if nu:
+            self.units["first_mb"] = [r[1] for r in rows]
+            self.units["payload_size"] = self.units["read_limit"] = [r[2] for r in rows]
+            self.units["out_capacity"] = self.descs["payload_size"][[r[0] for r in rows]] + 4096
+        self.first = np.array(first, dtype=np.uint32)
+        room = (self.units["out_capacity"].astype(np.int64) + 15) & ~15
+        self.units["out_offset"] = np.cumsum(room) - room
+        self.unit_work_len = int(room.sum())
+        self.arena_cap = int((((self.units["payload_size"].astype(np.int64) + 16 + 15) & ~15).sum())) + 16
+        dev = self.device
+        self.d_units = _dev_bytes(self.units, dev) if nu else torch.zeros(16, dtype=torch.uint8, device=dev)
+        self.d_src = torch.from_numpy(np.array(src, dtype=np.int64)).to(dev) if nu else torch.zeros(1, dtype=torch.int64, device=dev)
+        self.d_first = torch.from_numpy(self.first.view(np.int32).copy()).to(dev)
+        self.d_arena = torch.zeros(self.arena_cap, dtype=torch.uint8, device=dev)
+        self.d_stage_off = torch.zeros(nu + 1, dtype=torch.int64, device=dev)
+        self.d_stage_status = torch.zeros(max(1, nu), dtype=torch.int32, device=dev)
+        self.d_unit_work = torch.zeros(self.unit_work_len + 16, dtype=torch.uint8, device=dev)
+        self.d_unit_res = torch.zeros(max(1, nu) * SLICE_RESULT.itemsize, dtype=torch.uint8, device=dev)
+
+    def stage(self, stream=None):
+        self.ctx.stage_pieces(self.d_units, self.d_src, self.nu, self.d_out, self.work_len, self.d_arena, self.arena_cap,
+                              self.d_stage_off, self.d_stage_status, stream)
+
+    def decompress(self, stream=None):
+        if self.nu:
+            self.ctx.decompress_pieces(self.d_units, self.pieces, self.nu, self.max_w, self.ps.max_mb_height,
+                                       self.d_recs, self.plan.n_recs, self.plan.rec_stride, self.d_arena,
+                                       self.d_unit_work, self.d_unit_res, stream)
+
+    def pack(self, stream=None):
+        nu, dev = self.nu, self.device
+        self.d_pieces = _dev_bytes(self.pieces, dev) if nu else torch.zeros(16, dtype=torch.uint8, device=dev)
+        self.d_packed = torch.zeros(self.unit_work_len + 16, dtype=torch.uint8, device=dev)
+        self.d_pack_off = torch.zeros(nu + 1, dtype=torch.int64, device=dev)
+        self.d_kept = torch.zeros(max(1, nu), dtype=torch.int32, device=dev)
+        self.d_unit_status = torch.zeros(max(1, nu), dtype=torch.int32, device=dev)
+        self.ctx.pack_pieces(self.d_units, self.d_pieces, self.d_unit_res, nu, self.d_unit_work, self.d_packed,
+                             self.d_pack_off, self.d_kept, self.d_unit_status, stream)
+
+    def verify(self, stream=None):
+        self.ctx.verify_units(self.d_desc, self.d_res_c, self.n, self.d_first, self.nu, self.d_in, self.d_packed,
+                              self.d_pack_off, self.d_kept, self.d_unit_status, self.d_verdict, stream)
+
+    def roundtrip(self, stream=None):
+        if stream is not None:   # the constructor's uploads and zero fills ran on the current stream
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(stream) if stream is not None else _null():
+            self.compress(stream)
+            self.read_back(stream)
+            self.stage(stream)
+            self.decompress(stream)
+            self.pack(stream)
+            self.verify(stream)
+
+    def pack_recoded(self, stream=None):
+        """The slices' re-coded bytes packed contiguously on the device (avr_pack_outputs):
+        (d_packed uint8, d_offsets int64[n + 1])."""
+        d_packed = torch.zeros(self.work_len + 16, dtype=torch.uint8, device=self.device)
+        d_offsets = torch.zeros(max(1, self.n) + 1, dtype=torch.int64, device=self.device)
+        self.ctx.pack_outputs(self.d_desc, self.d_res_c, self.n, self.d_out, d_packed, d_offsets, stream)
+        return d_packed, d_offsets
+
+    # ----------------------------------------------------------------- results (host copies)
+    def verdicts(self) -> np.ndarray:
+        """1 bit-exact, 0 mismatch (or refused at read_back), 2 not coded, per slice."""
+        return self.d_verdict.cpu().numpy()[: self.n]
+
+    def recoded(self) -> list[bytes]:
+        """Per-slice re-coded bytes, the pieces' streams one after the other (b'' where the walk failed)."""
+        work = self.d_out.cpu().numpy()
+        return [work[int(d["out_offset"]):int(d["out_offset"]) + int(r["out_len"])].tobytes() if st == 0 else b""
+                for d, r, st in zip(self.descs, self.res, self.status)]
+
+    def seams(self, check_cuts: bool = True):
+        """(status int32[n], [Block field 16 per slice, b'' without a cut]) through avr_seams_build; a
+        slice refused at read_back keeps SLICE_CODER and gets no field."""
+        from . import seams_build
+        res = self.res.copy()
+        res["status"] = self.status
+        p = self.plan
+        return seams_build(self.ps.descs, self.ps.arena, res, p.slots, self.cuts, self.piece_end, self.recs,
+                           p.rec_stride, check_cuts)
+
+
 class _null:
     def __enter__(self):
         return self

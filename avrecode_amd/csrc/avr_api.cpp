@@ -1716,6 +1716,82 @@ int avr_pack_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* d
   return AVR_OK;
 }
 
+// split_begin's launch for a caller's device-resident batch (include/avrecode.h, ABI 8): the split
+// walk on the caller's stream into the caller's records, cut counts and piece ends.  The slots are
+// checked here, before anything is launched: a record outside d_recs would be written.  The kernel
+// gets one record less than each slot holds: a walk that filled its slot would write the end of its
+// last piece one entry past it, and avr_split_plan's slots have that one to spare (cuts < cap).
+int avr_compress_split_slices(avr_ctx* c, const avr_slice_desc* d_desc, int n, int max_w, int max_h,
+                              const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res,
+                              const avr_split_slot* slots, size_t split_bytes, uint8_t* d_recs, int n_recs,
+                              size_t rec_stride, uint32_t* d_cuts, uint32_t* d_piece_end, void* stream) {
+  if (!c || n < 0 || n_recs < 0 || (n && (!d_desc || !d_in || !d_out || !d_res || !slots || !d_cuts)) ||
+      (n_recs && (!d_recs || !d_piece_end)) || max_w <= 0 || max_h <= 0)
+    return AVR_ERR_INVALID_ARGUMENT;
+  if (max_w > avr::kMringCols || rec_stride < avr::seam_rec_bytes(max_w) || rec_stride > UINT32_MAX)
+    return fail(c, AVR_ERR_INVALID_ARGUMENT, "avr_compress_split_slices: picture wider than a seam record");
+  if (!split_bytes || split_bytes >= ((size_t)1 << 28))
+    return fail(c, AVR_ERR_INVALID_ARGUMENT, "avr_compress_split_slices: split_bytes outside (0, 2^28)");
+  for (int k = 0; k < n; k++) {
+    const avr_split_slot& s = slots[k];
+    if (s.first == -1 && s.cap == 0) continue;
+    if (s.first < 0 || s.cap == 0 || (uint64_t)s.first + s.cap > (uint64_t)n_recs)
+      return fail(c, AVR_ERR_INVALID_ARGUMENT,
+                  "avr_compress_split_slices: slice " + std::to_string(k) + " has its cut records outside the batch's");
+  }
+  if (!n) return AVR_OK;
+  return guarded(c, [&]() -> int {
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    c->sc_host.resize(n);
+    for (int k = 0; k < n; k++)
+      c->sc_host[k] = slots[k].first < 0 ? avr::PieceCtl{-1, 0, -1, 0}
+                                         : avr::PieceCtl{-1, 0, slots[k].first, slots[k].cap - 1};
+    HIP_TRY(c, c->sc_ctl.reserve(sizeof(avr::PieceCtl) * n));
+    HIP_TRY(c, c->sp_est.reserve(sizeof(uint16_t) * (size_t)avr::kEstGlobal * std::max(1, avr::split_grid(n, max_w)), true));
+    if (!d_recs) HIP_TRY(c, c->sp_recs.reserve(64));   // a batch without slots: no record is written
+    HIP_TRY(c, hipMemcpyAsync(c->sc_ctl.p, c->sc_host.data(), sizeof(avr::PieceCtl) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(d_cuts, 0, sizeof(uint32_t) * n, st));
+    if (n_recs) HIP_TRY(c, hipMemsetAsync(d_piece_end, 0, sizeof(uint32_t) * n_recs, st));
+    avr::SplitArgs sa;
+    sa.ctl = c->sc_ctl.as<avr::PieceCtl>();
+    sa.recs = d_recs ? d_recs : c->sp_recs.as<uint8_t>();
+    sa.rec_stride = (uint32_t)rec_stride;
+    sa.split_bits = (uint32_t)(8 * split_bytes);
+    sa.snap_n = d_cuts;
+    sa.piece_end = n_recs ? d_piece_end : nullptr;
+    HIP_TRY(c, avr::launch_split(0, c->tables.as<avr::EngineTables>(), d_desc, n, max_w, d_in, d_out, d_res,
+                                 c->sp_est.as<uint16_t>(), sa, 0, st));
+    return AVR_OK;
+  });
+}
+
+int avr_stage_pieces(avr_ctx* c, avr_slice_desc* d_desc, const uint64_t* d_src, int n, const uint8_t* d_out,
+                     size_t out_len, uint8_t* d_arena, size_t arena_cap, uint64_t* d_offsets, int32_t* d_status,
+                     void* stream) {
+  if (!c || n < 0 || (n && (!d_desc || !d_src || !d_out || !d_arena || !d_offsets || !d_status)) ||
+      ((uintptr_t)d_arena & 15))
+    return AVR_ERR_INVALID_ARGUMENT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, avr::launch_stage_pieces(d_desc, d_src, n, d_out, out_len, d_arena, arena_cap, d_offsets, d_status,
+                                      (hipStream_t)stream));
+  return AVR_OK;
+}
+
+int avr_verify_units(avr_ctx* c, const avr_slice_desc* d_desc, const avr_slice_result* d_res_c, int n,
+                     const uint32_t* d_first, int n_units, const uint8_t* d_in, const uint8_t* d_packed,
+                     const uint64_t* d_offsets, const uint32_t* d_kept, const int32_t* d_unit_status,
+                     int32_t* d_verdict, void* stream) {
+  if (!c || n < 0 || n_units < 0 ||
+      (n && (!d_desc || !d_res_c || !d_first || !d_in || !d_packed || !d_offsets || !d_kept || !d_unit_status ||
+             !d_verdict)))
+    return AVR_ERR_INVALID_ARGUMENT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, avr::launch_verify_units(d_desc, d_res_c, n, d_first, n_units, d_in, d_packed, d_offsets, d_kept,
+                                      d_unit_status, d_verdict, (hipStream_t)stream));
+  return AVR_OK;
+}
+
 static int synthesize_stream(avr_ctx* c, const avr_synth_params* p, int n, uint8_t** out, size_t* out_len) {
   if (!c || !p || n <= 0 || !out || !out_len || p->mb_width <= 0 || p->mb_height <= 0 || p->slice_type < 0 ||
       p->slice_type > 2 || p->chroma_format_idc < 1 || p->chroma_format_idc > 3 || p->gop_length < 0 ||

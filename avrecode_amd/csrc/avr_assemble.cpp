@@ -142,22 +142,38 @@ const uint8_t* find_before(const uint8_t* in, size_t from, size_t own, const uin
 }
 
 // Rank 0's container from gathered per-slice outputs (both avr_assemble_container entry points).
+// The optional seams fields of avr_assemble_container_seams: slice i's Block field 16 is
+// p[offsets[i] .. + lens[i]) (length 0: none; p null: none at all).
+struct SeamsArg {
+  const uint8_t* p = nullptr;
+  size_t len = 0;
+  const uint64_t* offsets = nullptr;
+  const uint32_t* lens = nullptr;
+};
+
 int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceView>& sv, const int32_t* status,
              const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out,
-             size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0) {
+             size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0, const SeamsArg& sa = SeamsArg()) {
   std::vector<char> ok(sv.size(), 0);
-  std::vector<std::pair<const uint8_t*, size_t>> blobs(sv.size(), {nullptr, 0});
+  std::vector<std::pair<const uint8_t*, size_t>> blobs(sv.size(), {nullptr, 0}), fields;
+  if (sa.p) fields.assign(sv.size(), {nullptr, 0});
   for (size_t i = 0; i < sv.size(); i++) {
     ok[i] = sv[i].candidate && status[i] == 0;
     if (ok[i]) {
       if (!recoded || offsets[i] > recoded_len || lens[i] > recoded_len - offsets[i]) return AVR_ERR_INVALID_ARGUMENT;
       blobs[i] = {recoded + offsets[i], lens[i]};
     }
+    if (sa.p && sa.lens[i]) {
+      // a seams field belongs to a coded slice of the parallel model on the u64 coder, and lies in the blob
+      if (model != AVR_MODEL_PARALLEL || !ok[i] || sa.offsets[i] > sa.len || sa.lens[i] > sa.len - sa.offsets[i])
+        return AVR_ERR_INVALID_ARGUMENT;
+      fields[i] = {sa.p + sa.offsets[i], sa.lens[i]};
+    }
   }
   const double t0 = now_s();
   const std::vector<const uint8_t*> found = segment(file, n, sv, ok);
   const double t1 = now_s();
-  const int r = emit_container(file, n, sv, found, blobs, model, out, out_len, dst, cap);
+  const int r = emit_container(file, n, sv, found, blobs, model, out, out_len, dst, cap, sa.p ? &fields : nullptr);
   if (getenv("AVR_ASM_TIMING")) fprintf(stderr, "assemble: segment %.3f s, emit %.3f s\n", t1 - t0, now_s() - t1);
   return r;
 }
@@ -165,9 +181,9 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
 int assemble_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
                     const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
                     size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out, size_t* out_len,
-                    uint8_t* dst, size_t cap) {
+                    uint8_t* dst, size_t cap, const SeamsArg& sa = SeamsArg()) {
   if (!file || !out_len || n_slices < 0 || (n_slices && (!descs || !arena || !status || !offsets || !lens)) ||
-      !assemblable(model))
+      !assemblable(model) || (sa.p && n_slices && (!sa.offsets || !sa.lens)))
     return AVR_ERR_INVALID_ARGUMENT;
   return guarded(nullptr, [&]() -> int {
     std::vector<SliceView> sv((size_t)n_slices);
@@ -190,7 +206,7 @@ int assemble_parsed(const uint8_t* file, size_t n, int model, const avr_slice_de
       }
       sv[i] = {P, m, d.coded != 0, d.file_offset};
     }
-    return assemble(file, n, model, sv, status, recoded, recoded_len, offsets, lens, out, out_len, dst, cap);
+    return assemble(file, n, model, sv, status, recoded, recoded_len, offsets, lens, out, out_len, dst, cap, sa);
   });
 }
 
@@ -337,17 +353,39 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
 
 extern "C" {
 
-int avr_assemble_container(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
-                           const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens,
-                           uint8_t** out, size_t* out_len) {
-  if (!file || !out || !out_len || n_slices < 0 || (n_slices && (!status || !offsets || !lens)) || !assemblable(model))
+int avr_assemble_container_seams(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
+                                 const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets,
+                                 const uint32_t* lens, const uint8_t* seams, size_t seams_len,
+                                 const uint64_t* seam_offsets, const uint32_t* seam_lens, uint8_t** out,
+                                 size_t* out_len) {
+  if (!file || !out || !out_len || n_slices < 0 || (n_slices && (!status || !offsets || !lens)) || !assemblable(model) ||
+      (seams && n_slices && (!seam_offsets || !seam_lens)))
     return AVR_ERR_INVALID_ARGUMENT;
   return guarded(nullptr, [&]() -> int {
     ParsedFile pf;
     if (int r = parse_file(nullptr, file, n, &pf, /*views=*/true)) return r;
     if ((size_t)n_slices != pf.slices.size()) return AVR_ERR_INVALID_ARGUMENT;
-    return assemble(file, n, model, views_of(pf), status, recoded, recoded_len, offsets, lens, out, out_len);
+    return assemble(file, n, model, views_of(pf), status, recoded, recoded_len, offsets, lens, out, out_len, nullptr, 0,
+                    SeamsArg{seams, seams_len, seam_offsets, seam_lens});
   });
+}
+
+int avr_assemble_container(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
+                           const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens,
+                           uint8_t** out, size_t* out_len) {
+  return avr_assemble_container_seams(file, n, model, n_slices, status, recoded, recoded_len, offsets, lens, nullptr, 0,
+                                      nullptr, nullptr, out, out_len);
+}
+
+int avr_assemble_container_seams_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs,
+                                        int n_slices, const uint8_t* arena, size_t arena_len, const int32_t* status,
+                                        const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets,
+                                        const uint32_t* lens, const uint8_t* seams, size_t seams_len,
+                                        const uint64_t* seam_offsets, const uint32_t* seam_lens, uint8_t** out,
+                                        size_t* out_len) {
+  if (!out) return AVR_ERR_INVALID_ARGUMENT;
+  return assemble_parsed(file, n, model, descs, n_slices, arena, arena_len, status, recoded, recoded_len, offsets, lens,
+                         out, out_len, nullptr, 0, SeamsArg{seams, seams_len, seam_offsets, seam_lens});
 }
 
 int avr_assemble_container_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,

@@ -54,6 +54,9 @@ struct avr_ctx : avr_host::ErrSink {
   // avr_decompress_pieces: the batch's PieceCtl array, host (alive while its upload is in flight) and device
   std::vector<avr::PieceCtl> pc_host;
   DevBuf pc_ctl;
+  // avr_compress_split_slices: the same for its batch (its own pair: the two calls may be in flight together)
+  std::vector<avr::PieceCtl> sc_host;
+  DevBuf sc_ctl;
   // a batch holding both progressive and field slices runs its field kernel beside the progressive
   // one (avr::FieldLane); AVR_FIELD_LANE=0 keeps the two in one stream, one after the other
   hipStream_t fld_stream = nullptr;

@@ -155,5 +155,16 @@ hipError_t launch_pack(const avr_slice_desc* descs, const avr_slice_result* res,
 hipError_t launch_pack_pieces(const avr_slice_desc* descs, const avr_piece* pieces, const avr_slice_result* res, int n,
                               const uint8_t* out, uint8_t* packed, uint64_t* offsets, uint32_t* kept, int32_t* status,
                               hipStream_t stream);
+// avr_stage_pieces (avr_k_pieces.hip): units' streams from anywhere in `out` (src[k], desc[k].payload_size
+// bytes) into an arena of cap bytes, each 16-byte aligned and followed by >= 16 zero bytes; the scan
+// writes offsets (n + 1), desc[k].payload_offset / read_limit and status (AVR_SLICE_OVERFLOW for a
+// unit whose source or place lies outside its buffer: not copied)
+hipError_t launch_stage_pieces(avr_slice_desc* descs, const uint64_t* src, int n, const uint8_t* out, uint64_t out_len,
+                               uint8_t* arena, uint64_t cap, uint64_t* offsets, int32_t* status, hipStream_t stream);
+// avr_verify_units (avr_k_pieces.hip): launch_verify for slices whose regenerated bytes are the packed
+// kept bytes of their units [first[k], first[k + 1]) (launch_pack_pieces' outputs)
+hipError_t launch_verify_units(const avr_slice_desc* descs, const avr_slice_result* rc, int n, const uint32_t* first,
+                               int n_units, const uint8_t* in, const uint8_t* packed, const uint64_t* offsets, const uint32_t* kept,
+                               const int32_t* ustatus, int32_t* verdict, hipStream_t stream);
 
 }  // namespace avr

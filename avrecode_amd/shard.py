@@ -8,8 +8,12 @@ rank 0 (point-to-point send/recv over xGMI with backend "nccl" = RCCL; CPU tenso
   sharded_compress    re-coded blocks -> rank 0 builds the Recoded container (avr_assemble_container)
   sharded_decompress  regenerated CABAC payloads -> rank 0 splices them with the container's
                       literals and applies the last-byte patch (avr_splice_container)
-sharded_decompress is byte-identical to the single-GPU call; sharded_compress is where no slice is
-long enough for the whole-file compress to cut it (see its docstring).
+Both are byte-identical to the single-GPU calls.  The whole-file compress cuts the parallel model's
+long slices into pieces (Context.split_bytes); sharded_compress(split_bytes=...) does the same on
+each rank for its range's long slices -- the split walk, a check of the pieces on the device and the
+seams fields (batch.SplitBatch), beside the batch of the rest -- and a second gather brings the
+fields to rank 0, which writes them into the container (avr_assemble_container_seams).  Its default,
+split_bytes=None, codes every slice whole: the whole-file container at ctx.split_bytes = 0.
 
 A container whose long slices were cut into pieces (Context.split_bytes; Block field 16) is
 decompressed by units instead of slices: a unit is what one workgroup regenerates, a whole slice or
@@ -181,6 +185,29 @@ def subset(ps: ParsedStream, lo: int, hi: int, copy_arena: bool = True) -> Parse
     return ParsedStream(d, arena.copy() if copy_arena else arena, w1 - w0, ps.max_mb_width, ps.max_mb_height)
 
 
+def select(ps: ParsedStream, idx) -> ParsedStream:
+    """subset() for a list of slice indices (ascending or not): those slices as a self-contained
+    batch in the order given -- the payloads copied into an arena of their own (each 16-byte aligned
+    and followed by at least 16 zero bytes), the outputs placed one after the other.  max_mb_width is
+    the widest LDS ring among the selected coded slices (3 W + 7 for an MBAFF slice), so a selection
+    of progressive slices is not widened by the MBAFF ones it leaves out."""
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+    d = ps.descs[idx].copy()
+    if len(d) == 0:
+        return ParsedStream(d, np.zeros(16, np.uint8), 0, 1, ps.max_mb_height)
+    span = d["read_limit"].astype(np.int64)
+    room = (span + 16 + 15) & ~15
+    off = np.cumsum(room) - room
+    arena = np.zeros(int(room.sum()) + 16, np.uint8)
+    for o, s, n in zip(off, ps.descs["payload_offset"][idx].astype(np.int64), span):
+        arena[o:o + n] = ps.arena[s:s + n]
+    d["payload_offset"] = off
+    wroom = (d["out_capacity"].astype(np.int64) + 15) & ~15
+    d["out_offset"] = np.cumsum(wroom) - wroom
+    cols = np.where(d["structure"] == 3, 3 * d["mb_width"] + 7, d["mb_width"])[d["coded"] != 0]
+    return ParsedStream(d, arena, int(wroom.sum()), int(cols.max()) if len(cols) else 1, ps.max_mb_height)
+
+
 def subset_units(pu: ParsedStream, lo: int, hi: int, copy_arena: bool = True) -> ParsedStream:
     """The units [lo, hi) of a piece plan's batch (DecompressPlan.parsed_units) as a self-contained
     batch: subset(), plus the seam records the range's pieces start from, seam rebased to the first
@@ -230,46 +257,131 @@ def collapse_units(pieces, status, offsets, lens):
     return st.astype(np.int32), off.astype(np.uint64), ln.astype(np.uint32)
 
 
-def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = None,
-                     model: int = MODEL_PARALLEL) -> bytes | None:
-    """PARALLEL-model compress of one file across all ranks; the container is returned on rank 0.
-
-    Every rank parses the file (host), takes its contiguous slice range (partition), runs it on its
-    GPU (compress + device roundtrip check: a slice is coded only if it regenerates its payload),
-    packs the re-coded bytes on the device and sends them to rank 0 (gather_flat over RCCL), which
-    assembles the Recoded container from its own parse (avr_assemble_container_parsed).
-    model = MODEL_PARALLEL or MODEL_PARALLEL32.  Byte-identical to ctx.compress(data, model) where
-    no slice is a split candidate (a progressive slice of at least 1.5 ctx.split_bytes payload
-    bytes), or with ctx.split_bytes = 0: the whole-file compress cuts such a slice into pieces, this
-    one codes every slice whole (the seams are not carried through the gather and the assembly)."""
+def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL, split_bytes: int = 0):
+    """This rank's slice range of a sharded compress on its GPU: (flat uint8 tensor, status, offsets,
+    lens, seams) with slice k's re-coded bytes at flat[offsets[k] : offsets[k] + lens[k]] and status 0
+    where it is to be coded (-1: stored skip_coded).  split_bytes 0 (or a model other than
+    MODEL_PARALLEL): every slice whole through batch.DeviceBatch, seams None.  Otherwise the range's
+    split candidates (split_plan at split_bytes, coded slices only) go through batch.SplitBatch on a
+    side stream beside the DeviceBatch of the rest; the two are joined before the packs; seams is one
+    bytes per slice (b"" without a cut).  A candidate whose walk, cut check or verify fails is
+    stored skip_coded, as the whole-file compress stores it: no unsplit retry."""
     import torch
-    import torch.distributed as dist
 
-    from .batch import DeviceBatch
+    from . import split_plan
+    from .batch import DeviceBatch, SplitBatch
 
-    rank, world = dist.get_rank(), dist.get_world_size()
-    ps = ps if ps is not None else parse_stream(data)
-    lo, hi = partition(ps.descs["payload_size"], world)[rank]
-    part = subset(ps, lo, hi)
-    dev = _gather_device(ctx, device)
-    if hi > lo:
-        b = DeviceBatch(ctx, part)
+    n = len(part.descs)
+    dev = torch.device("cuda", ctx.device) if device is None else device
+    cand = np.zeros(n, bool)
+    if split_bytes and model == MODEL_PARALLEL:
+        cand = split_plan(part.descs, split_bytes).candidate & (part.descs["coded"] != 0)
+    if not cand.any():
+        b = DeviceBatch(ctx, part, device=dev)
         b.roundtrip(model)
         flat, d_off = b.pack()
         torch.cuda.synchronize()
         v = b.verdicts()
         res = b.results("c")
-        offs = d_off.cpu().numpy()[: hi - lo].astype(np.int64)
+        offs = d_off.cpu().numpy()[:n].astype(np.int64)
         lens = np.where(res["status"] == 0, res["out_len"], 0).astype(np.int64)
         status = np.where(v == 1, 0, -1).astype(np.int64)
+        return flat, status, offs, lens, ([b""] * n if split_bytes and model == MODEL_PARALLEL else None)
+    idx_c, idx_r = np.flatnonzero(cand), np.flatnonzero(~cand)
+    cur = torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(dev)
+    sb = SplitBatch(ctx, select(part, idx_c), split_bytes, device=dev)
+    side.wait_stream(cur)                   # after the batch's uploads and zero fills on the current stream
+    sb.compress(side)                       # the long walks first, beside everything below
+    b = None
+    if len(idx_r):
+        b = DeviceBatch(ctx, select(part, idx_r), device=dev)
+        b.roundtrip(model)
+    with torch.cuda.stream(side):
+        sb.read_back(side)
+        sb.stage(side)
+        sb.decompress(side)
+        sb.pack(side)
+        sb.verify(side)
+    cur.wait_stream(side)                   # joined before the packs
+    flat_c, off_c = sb.pack_recoded()
+    if b is not None:
+        flat_r, off_r = b.pack()
+    torch.cuda.synchronize()
+    status = np.full(n, -1, np.int64)
+    offs, lens = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    seams = [b""] * n
+    st_c, fields = sb.seams(check_cuts=True)
+    ok = (sb.verdicts() == 1) & (st_c == 0)
+    total_c = int(off_c.cpu().numpy()[len(idx_c)])
+    status[idx_c] = np.where(ok, 0, -1)
+    offs[idx_c] = off_c.cpu().numpy()[:len(idx_c)]
+    lens[idx_c] = np.where(ok, sb.res["out_len"], 0)
+    for j, k in enumerate(idx_c):
+        if ok[j]:
+            seams[k] = fields[j]
+    flat = flat_c[:max(16, total_c)]
+    if b is not None:
+        res = b.results("c")
+        status[idx_r] = np.where(b.verdicts() == 1, 0, -1)
+        offs[idx_r] = off_r.cpu().numpy()[:len(idx_r)] + total_c
+        lens[idx_r] = np.where(res["status"] == 0, res["out_len"], 0)
+        total_r = int(off_r.cpu().numpy()[len(idx_r)])
+        flat = torch.cat([flat_c[:total_c], flat_r[:max(16, total_r)]])
+    return flat, status, offs, lens, seams
+
+
+def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = None,
+                     model: int = MODEL_PARALLEL, split_bytes: int | None = None, run_range=None) -> bytes | None:
+    """PARALLEL-model compress of one file across all ranks; the container is returned on rank 0.
+
+    Every rank parses the file (host), takes its contiguous slice range (partition), runs it on its
+    GPU (compress_range: compress + device roundtrip check -- a slice is coded only if it regenerates
+    its payload -- and the re-coded bytes packed on the device) and sends them to rank 0 (gather_flat
+    over RCCL), which assembles the Recoded container from its own parse
+    (avr_assemble_container_parsed).  model = MODEL_PARALLEL or MODEL_PARALLEL32.
+    split_bytes None or 0 (the default): every slice is coded whole -- byte-identical to
+    ctx.compress(data, model) at ctx.split_bytes = 0, or where no slice is a split candidate.
+    split_bytes = s with MODEL_PARALLEL (MODEL_PARALLEL32 ignores it, as the whole-file call does):
+    each rank takes its range's split candidates (a progressive slice of at least 1.5 s payload
+    bytes) through the split walk, checks them piece by piece on the device and builds their seams
+    fields (batch.SplitBatch); a second gather_flat brings the fields to rank 0, which assembles with
+    them (avr_assemble_container_seams_parsed).  Byte-identical to ctx.compress(data, MODEL_PARALLEL)
+    at ctx.split_bytes = s; sharded_compress(ctx, x, split_bytes=ctx.split_bytes) is the whole-file
+    container.  A slice is one rank's: the cut pieces help the decompress, a single slice's compress
+    walk stays one chain.
+    run_range(part) -> compress_range's tuple replaces the device step (CPU tests)."""
+    import torch
+    import torch.distributed as dist
+
+    rank, world = dist.get_rank(), dist.get_world_size()
+    ps = ps if ps is not None else parse_stream(data)
+    split = int(split_bytes or 0) if model == MODEL_PARALLEL else 0
+    lo, hi = partition(ps.descs["payload_size"], world)[rank]
+    part = subset(ps, lo, hi)
+    dev = _gather_device(ctx, device)
+    seams = None
+    if hi > lo:
+        flat, status, offs, lens, seams = (run_range or (lambda p: compress_range(ctx, p, None, model, split)))(part)
     else:
-        import torch as _t
-        flat = _t.zeros(16, dtype=_t.uint8, device=dev)
+        flat = torch.zeros(16, dtype=torch.uint8, device=dev)
         offs = lens = status = np.zeros(0, np.int64)
     g = gather_flat(flat, status, offs, lens, dst=0, device=dev)
+    gs = None
+    if split:
+        # the seams fields, by the same gather: one (possibly empty) field per slice
+        fields = seams if seams is not None else [b""] * (hi - lo)
+        sl = np.array([len(f) for f in fields], dtype=np.int64)
+        so = np.cumsum(sl) - sl
+        sflat = torch.from_numpy(np.frombuffer(b"".join(fields) + b"\0" * 16, dtype=np.uint8).copy())
+        gs = gather_flat(sflat.to(dev) if dev.type == "cuda" else sflat, np.asarray(status, np.int64), so, sl, dst=0,
+                         device=dev)
     if g is None:
         return None
     st, blob, offs, lens = g
+    if gs is not None:
+        _, sblob, soffs, slens = gs
+        return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, seams=(sblob, soffs, slens))
     return assemble_container(data, st, blob, offs, lens, model=model, ps=ps)
 
 

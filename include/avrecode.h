@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define AVRECODE_ABI_VERSION 7  /* 7: piece plans (avr_dec_plan_load_pieces, avr_decompress_pieces, avr_pack_pieces);
+#define AVRECODE_ABI_VERSION 8  /* 8: split compress of slice batches (avr_split_plan, avr_compress_split_slices,
+                                 *    avr_seams_build, avr_stage_pieces, avr_verify_units, avr_assemble_container_seams);
+                                 * 7: piece plans (avr_dec_plan_load_pieces, avr_decompress_pieces, avr_pack_pieces);
                                  * 6: the parallel model's long-slice split (avr_set_split_bytes, Block field 16);
                                  * 5: avr_slice_desc.file_offset (96 B), dec-plan handle, ranged parse */
 
@@ -93,6 +95,8 @@ void avr_free(void* p);
  * whole at begin, as a reference-model container) and, piece by piece on any number of ranks,
  * through the piece plans (avr_dec_plan_load_pieces, avr_decompress_pieces, avr_pack_pieces); the
  * per-slice plans (avr_plan_decompress, avr_dec_plan_load) refuse them with AVR_ERR_UNSUPPORTED.
+ * A caller that holds slice batches on the device makes them with avr_split_plan,
+ * avr_compress_split_slices, avr_seams_build and avr_assemble_container_seams (ABI 8, below).
  * split_bytes = 0: no split.  Default: the environment's AVR_SPLIT_BYTES, else 98304.  Checked by the oracle's
  * restatement (oracle/oracle_seams.c). */
 int avr_set_split_bytes(avr_ctx* ctx, size_t split_bytes);
@@ -438,6 +442,99 @@ int avr_decompress_pieces(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_
 int avr_pack_pieces(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_piece* d_pieces,
                     const avr_slice_result* d_res, int n, const uint8_t* d_out, uint8_t* d_packed,
                     uint64_t* d_offsets, uint32_t* d_kept, int32_t* d_status, void* stream);
+
+/* Split compress of slice batches (ABI 8): what avr_compress_file does with the parallel model's long
+ * slices, for a caller that holds a rank's slices on the device -- so a sharded compress writes the
+ * container the whole-file call writes.  No reference counterpart (the reference codes a slice as
+ * one chain, recode.cpp:1134-1268).
+ *
+ * avr_split_plan (host only): which of n descriptors the whole-file compress would take through the
+ * split walk at split_bytes -- a progressive frame (AVR_STRUCT_FRAME), mb_width <= 288,
+ * 2 * payload_size >= 3 * split_bytes, 0 < split_bytes < 2^28 (desc.coded is not read: the caller
+ * plans its recodable slices) -- and what that walk needs.  slots[k] = {first, cap}: the candidate's
+ * cut records are [first, first + cap) of the batch's *n_recs, cap = 8 * payload_size /
+ * (8 * split_bytes) + 1 (a walk makes fewer cuts than cap); {-1, 0} for the others.
+ * out_capacity[k] (optional) = 2 * payload_size + 256 + 64 * cap for a candidate, else 0.
+ * *rec_stride = the record size of the widest candidate (of one column without any),
+ * *n_candidates (optional) their number. */
+typedef struct {
+  int32_t first;   /* first cut record of the slice's slot; -1: not a candidate, no cut is made */
+  uint32_t cap;    /* records in the slot */
+} avr_split_slot;
+int avr_split_plan(const avr_slice_desc* descs, int n, size_t split_bytes, avr_split_slot* slots,
+                   uint32_t* out_capacity, int* n_recs, size_t* rec_stride, int* n_candidates);
+/* The split walk on `stream` over the caller's device buffers (d_desc / d_in / d_out / d_res as
+ * avr_compress_slices; every slice a progressive frame of AVR_MODEL_PARALLEL, out_capacity as
+ * avr_split_plan gives it): each slice is cut as it is walked -- a cut candidate every
+ * 8 * split_bytes decoded bits.  slots = avr_split_plan's HOST array.  Slice k's pieces' streams stand
+ * one after the other at its out_offset (d_res[k].out_len bytes in all); d_cuts[k] = its cuts,
+ * d_piece_end[slots[k].first + i] = where piece i ends in them, d_recs (n_recs records of rec_stride
+ * bytes, the split kernels' device layout) record slots[k].first + i = cut i.  d_cuts (n) and
+ * d_piece_end (n_recs) are zeroed on the stream first.  Checked on the host before anything is
+ * launched (AVR_ERR_INVALID_ARGUMENT): max_mb_width <= 288, rec_stride no less than a record of
+ * max_mb_width columns, 0 < split_bytes < 2^28, every slot {-1, 0} or inside n_recs with cap >= 1.
+ * Scratch is the context's split scratch (avr_decompress_pieces' too): the call may run beside an
+ * avr_compress_slices launch on another stream, not beside another split launch.  Nothing is
+ * synchronised. */
+int avr_compress_split_slices(avr_ctx* ctx, const avr_slice_desc* d_desc, int n, int max_mb_width, int max_mb_height,
+                              const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res,
+                              const avr_split_slot* slots, size_t split_bytes, uint8_t* d_recs, int n_recs,
+                              size_t rec_stride, uint32_t* d_cuts, uint32_t* d_piece_end, void* stream);
+/* Host only: the Block-field-16 bytes of every cut slice of such a batch, from what the caller read
+ * back -- descs / arena (the host descriptors and payloads, avr_parse_stream's), res, cuts,
+ * piece_end (n_recs entries) and recs (n_recs * rec_stride bytes, at least recs_len).  status[k] =
+ * res[k].status, or with check_cuts AVR_SLICE_CODER when a cut's re-encoder state is not what the
+ * host restates from the record's CABAC decoder state and the payload (what avr_compress_file
+ * checks; without it the records' re-encoder fields are taken as they are).  A slice with status 0
+ * and at least one cut gets its field at *seams + offsets[k], lens[k] bytes (lens[k] = 0 otherwise);
+ * *seams is malloc'd (avr_free).  AVR_ERR_INVALID_ARGUMENT, with nothing read out of range, when a
+ * slot is not {-1, 0} or inside n_recs, cuts[k] >= cap (or non-zero without a slot), a status-0
+ * slice's piece ends decrease or its last is not out_len, rec_stride is less than a record of the
+ * slice's mb_width (1 .. 288), its slice_type or (P / B) cabac_init_idc is not 0 .. 2, a payload lies
+ * outside arena_len, or recs_len < n_recs * rec_stride. */
+int avr_seams_build(const avr_slice_desc* descs, int n, const uint8_t* arena, size_t arena_len,
+                    const avr_slice_result* res, const avr_split_slot* slots, const uint32_t* cuts,
+                    const uint32_t* piece_end, int n_recs, const uint8_t* recs, size_t recs_len, size_t rec_stride,
+                    int check_cuts, int32_t* status, uint8_t** seams, size_t* seams_len, uint64_t* offsets,
+                    uint32_t* lens);
+/* avr_assemble_container(_parsed) with one optional seams field per slice: slice k's Block field 16
+ * is seams[seam_offsets[k] .. + seam_lens[k]) (length 0: none; seams NULL: none at all), so rank 0
+ * of a sharded compress writes avr_compress_file's container.  AVR_ERR_INVALID_ARGUMENT when a field
+ * lies outside seams_len, when one is given with a model other than AVR_MODEL_PARALLEL, or for a
+ * slice that is not coded (not a candidate, or status[k] != 0). */
+int avr_assemble_container_seams(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
+                                 const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets,
+                                 const uint32_t* lens, const uint8_t* seams, size_t seams_len,
+                                 const uint64_t* seam_offsets, const uint32_t* seam_lens, uint8_t** out,
+                                 size_t* out_len);
+int avr_assemble_container_seams_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs,
+                                        int n_slices, const uint8_t* arena, size_t arena_len, const int32_t* status,
+                                        const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets,
+                                        const uint32_t* lens, const uint8_t* seams, size_t seams_len,
+                                        const uint64_t* seam_offsets, const uint32_t* seam_lens, uint8_t** out,
+                                        size_t* out_len);
+/* The two device steps that let a rank check its split slices without their bytes leaving the device
+ * (all pointers device pointers, nothing synchronised).
+ * avr_stage_pieces: the units' streams -- unit k's d_desc[k].payload_size bytes at d_out + d_src[k],
+ * at any alignment (a split walk leaves a slice's pieces one after the other) -- copied into d_arena
+ * in unit order, each 16-byte aligned and followed by at least 16 zero bytes: avr_decompress_pieces'
+ * input layout.  Unit k stands at d_offsets[k] (n + 1 entries; d_offsets[k + 1] - d_offsets[k] =
+ * its length + 16 rounded up to 16), and d_desc[k].payload_offset / read_limit are set to it.
+ * d_status[k] = 0, or AVR_SLICE_OVERFLOW for a unit whose source reaches past out_len or whose place
+ * past arena_cap (checked on the device; it is not copied).  d_arena must be 16-byte aligned.
+ * avr_verify_units: avr_verify_slices for split slices after avr_pack_pieces.  Slice k's units are
+ * [d_first[k], d_first[k + 1]) (n + 1 entries) of the packed batch's n_units (d_packed, d_offsets, d_kept,
+ * d_unit_status: avr_pack_pieces' outputs); their kept bytes, contiguous there, are compared with
+ * the payload at d_in + d_desc[k].payload_offset under the last-byte rule (recode.cpp:1345-1356:
+ * payload_size or payload_size - 1 bytes, the final byte not compared).  d_verdict[k] = 1 bit-exact,
+ * 0 mismatch -- also when a unit failed, the slice has no unit or the lengths do not add up --
+ * 2 not coded (desc.coded = 0 or d_res_c[k].status != 0). */
+int avr_stage_pieces(avr_ctx* ctx, avr_slice_desc* d_desc, const uint64_t* d_src, int n, const uint8_t* d_out,
+                     size_t out_len, uint8_t* d_arena, size_t arena_cap, uint64_t* d_offsets, int32_t* d_status,
+                     void* stream);
+int avr_verify_units(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_slice_result* d_res_c, int n,
+                     const uint32_t* d_first, int n_units, const uint8_t* d_in, const uint8_t* d_packed, const uint64_t* d_offsets,
+                     const uint32_t* d_kept, const int32_t* d_unit_status, int32_t* d_verdict, void* stream);
 
 /* Container codec check (host only): parse a Recoded protobuf (recode.proto:1-19) with the
  * library's own wire codec -- the one avr_decompress_file uses -- and return (a) its fields as JSON,
