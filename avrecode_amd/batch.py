@@ -283,7 +283,7 @@ class SplitBatch:
         self.cuts = self.d_cuts.cpu().numpy().view(np.uint32)[:n].copy()
         self.piece_end = self.d_piece_end.cpu().numpy().view(np.uint32)[:p.n_recs].copy()
         self.recs = self.d_recs.cpu().numpy()[:p.n_recs * p.rec_stride].copy()
-        # what the walk itself can fail (split_finish's first check): too many cuts, piece ends that
+        # what the walk itself can fail (seams_build's index checks): too many cuts, piece ends that
         # are not the stream's
         self.status = self.res["status"].astype(np.int32)
         rows, pc, src, first = [], [], [], [0]   # per unit: (slice, first_mb, stream length), PIECE, source

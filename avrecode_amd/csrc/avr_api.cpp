@@ -336,11 +336,6 @@ constexpr int32_t kStatusNoRoundtrip = AVR_SLICE_NO_ROUNDTRIP;
 // i's bytes up to cut i's q.
 constexpr size_t kSplitBytesDefault = 98304;
 
-bool split_candidate(const avr_slice_desc& d, size_t split_bytes) {
-  return split_bytes && split_bytes < ((size_t)1 << 28) && d.structure == AVR_STRUCT_FRAME &&
-         d.mb_width <= avr::kMringCols && 2 * (uint64_t)d.payload_size >= 3 * (uint64_t)split_bytes;
-}
-
 // The two timing events around a split launch, owned by the job they time: destroyed with it on
 // every path out, the failed ones included.
 struct EventPair {
@@ -352,7 +347,59 @@ struct EventPair {
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
   }
+  int create(avr_ctx* c) {
+    HIP_TRY(c, hipEventCreate(&e0));
+    HIP_TRY(c, hipEventCreate(&e1));
+    return AVR_OK;
+  }
 };
+
+// The launches of the split kernel, each stated once for the whole-file calls (split_begin,
+// split_launch: the context's sp_* buffers on split_stream) and for the ABI's calls on a caller's
+// device buffers and stream (avr_compress_split_slices, avr_decompress_pieces).  Everything but ctl
+// is device memory.  ctl is the launch's host PieceCtl array, uploaded to ctl_dev on st: the caller
+// keeps it alive while that is in flight.  ev (optional): recorded directly around the kernel.
+// Mode 1, the pieces: piece k starts at record ctl[k].seam of d_recs (null: no piece does).
+int launch_split_ctl(avr_ctx* c, int mode, const avr_slice_desc* d_desc, int n, int max_w, const uint8_t* d_in,
+                     uint8_t* d_out, avr_slice_result* d_res, const avr::PieceCtl* ctl, DevBuf* ctl_dev,
+                     avr::SplitArgs sa, uint32_t flags, hipStream_t st, const EventPair* ev) {
+  HIP_TRY(c, ctl_dev->reserve(sizeof(avr::PieceCtl) * n));
+  HIP_TRY(c, c->sp_est.reserve(sizeof(uint16_t) * (size_t)avr::kEstGlobal * std::max(1, avr::split_grid(n, max_w)), true));
+  if (!sa.recs) {   // a batch without records: none is read or written
+    HIP_TRY(c, c->sp_recs.reserve(64));
+    sa.recs = c->sp_recs.as<uint8_t>();
+  }
+  HIP_TRY(c, hipMemcpyAsync(ctl_dev->p, ctl, sizeof(avr::PieceCtl) * n, hipMemcpyHostToDevice, st));
+  sa.ctl = ctl_dev->as<avr::PieceCtl>();
+  if (ev) HIP_TRY(c, hipEventRecord(ev->e0, st));
+  HIP_TRY(c, avr::launch_split(mode, c->tables.as<avr::EngineTables>(), d_desc, n, max_w, d_in, d_out, d_res,
+                               c->sp_est.as<uint16_t>(), sa, flags, st));
+  if (ev) HIP_TRY(c, hipEventRecord(ev->e1, st));
+  return AVR_OK;
+}
+// Mode 0, the split walk: slice k may write the records of its slot (avr_split_plan's; {-1, 0}: it is
+// not cut), its cut count to d_cuts[k] and its pieces' ends to d_piece_end from slots[k].first, both
+// zeroed here first.  The kernel is offered cap - 1 records of a slot, not cap: a walk that filled
+// its slot would write its last piece's end one entry past it, into the next slice's or past the
+// array.  The rule leaves that one to spare: cut candidates are at least split_bits apart and need
+// split_bits / 2 still ahead (Walker::seam_cut), so cuts <= 8 size / split_bits - 1/2 <= cap - 1.
+int launch_split_walk(avr_ctx* c, const avr_slice_desc* d_desc, int n, int max_w, const uint8_t* d_in, uint8_t* d_out,
+                      avr_slice_result* d_res, const avr_split_slot* slots, uint8_t* d_recs, int n_recs, size_t rec_stride,
+                      uint32_t* d_cuts, uint32_t* d_piece_end, size_t split_bytes, uint32_t flags, hipStream_t st,
+                      std::vector<avr::PieceCtl>* ctl, DevBuf* ctl_dev, const EventPair* ev) {
+  ctl->resize(n);
+  for (int k = 0; k < n; k++)
+    (*ctl)[k] = slots[k].first < 0 ? avr::PieceCtl{-1, 0, -1, 0} : avr::PieceCtl{-1, 0, slots[k].first, slots[k].cap - 1};
+  HIP_TRY(c, hipMemsetAsync(d_cuts, 0, sizeof(uint32_t) * n, st));
+  if (n_recs) HIP_TRY(c, hipMemsetAsync(d_piece_end, 0, sizeof(uint32_t) * n_recs, st));
+  avr::SplitArgs sa;
+  sa.recs = d_recs;
+  sa.rec_stride = (uint32_t)rec_stride;
+  sa.split_bits = (uint32_t)(8 * split_bytes);
+  sa.snap_n = d_cuts;
+  sa.piece_end = n_recs ? d_piece_end : nullptr;
+  return launch_split_ctl(c, 0, d_desc, n, max_w, d_in, d_out, d_res, ctl->data(), ctl_dev, sa, flags, st, ev);
+}
 
 // Compress of the long slices, in two calls around the rest of the batch: begin uploads them and
 // launches the split compress on the split stream (each slice cut as it is walked: the records,
@@ -365,68 +412,51 @@ struct SplitOut {
 };
 struct SplitJob {
   std::vector<const avr::SliceInfo*> sl;
-  std::vector<avr_slice_desc> d;
-  std::vector<avr::PieceCtl> ctl;
+  std::vector<avr_slice_desc> d;      // compress_files: the header's fields and payload_size
+  std::vector<avr_split_slot> slots;
+  std::vector<avr::PieceCtl> ctl;     // the walk's upload
   Bytes arena;
   uint64_t out_total = 0;
-  uint32_t nrec = 0, split_bits = 0;
+  uint32_t nrec = 0;
   size_t stride = 0;
   int max_w = 1;
-  uint32_t flags = 0;
   EventPair ev;   // around the split compress kernel
 };
 
 int split_begin(avr_ctx* c, SplitJob* j, size_t split_bytes, uint32_t flags) {
   const int n = (int)j->sl.size();
   if (!n) return AVR_OK;
-  j->flags = flags & avr::kFlagBill;
-  j->split_bits = (uint32_t)(8 * split_bytes);
-  j->d.resize(n);
-  j->ctl.resize(n);
+  j->slots.resize(n);
   for (int k = 0; k < n; k++) {
     const avr::SliceInfo& s = *j->sl[k];
     avr_slice_desc& d = j->d[k];
-    d = desc_from_header(s);
     append_aligned(&j->arena, s.payload(), s.read_limit, 16, &d.payload_offset);
-    d.payload_size = (uint32_t)s.size;
     d.read_limit = (uint32_t)s.read_limit;
-    const uint32_t cap = (uint32_t)(8ull * s.size / j->split_bits) + 1;
-    d.out_capacity = (uint32_t)(s.size * 2 + 256 + 64 * (size_t)cap);
+    uint64_t cap = 0, oc = 0;
+    if (!split_slot(d, split_bytes, &cap, &oc) || oc > UINT32_MAX || j->nrec + cap > INT32_MAX)
+      return fail(c, AVR_ERR_INVALID_ARGUMENT, "split: a slice too long for its cut records");
+    d.out_capacity = (uint32_t)oc;
     place_output(&d, &j->out_total);
     j->max_w = std::max(j->max_w, d.mb_width);
-    j->ctl[k] = avr::PieceCtl{-1, 0, (int32_t)j->nrec, cap};
-    j->nrec += cap;
+    j->slots[k] = avr_split_slot{(int32_t)j->nrec, (uint32_t)cap};
+    j->nrec += (uint32_t)cap;
   }
   j->stride = avr::seam_rec_bytes(j->max_w);
-  const int grid = avr::split_grid(n, j->max_w);
   HIP_TRY(c, c->sp_in.reserve(j->arena.size() + 4096));
   HIP_TRY(c, c->sp_out.reserve(j->out_total + 4096));
   HIP_TRY(c, c->sp_descs.reserve(sizeof(avr_slice_desc) * n));
   HIP_TRY(c, c->sp_res.reserve(sizeof(avr_slice_result) * n));
-  HIP_TRY(c, c->sp_ctl.reserve(sizeof(avr::PieceCtl) * n));
   HIP_TRY(c, c->sp_recs.reserve(j->stride * j->nrec + 64));
   HIP_TRY(c, c->sp_snapn.reserve(sizeof(uint32_t) * ((size_t)n + j->nrec)));
-  HIP_TRY(c, c->sp_est.reserve(sizeof(uint16_t) * (size_t)avr::kEstGlobal * std::max(1, grid), true));
-  HIP_TRY(c, hipEventCreate(&j->ev.e0));
-  HIP_TRY(c, hipEventCreate(&j->ev.e1));
+  if (int r = j->ev.create(c)) return r;
   hipStream_t st = c->split_stream;
   HIP_TRY(c, hipMemcpyAsync(c->sp_in.p, j->arena.data(), j->arena.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(c->sp_descs.p, j->d.data(), sizeof(avr_slice_desc) * n, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(c->sp_ctl.p, j->ctl.data(), sizeof(avr::PieceCtl) * n, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemsetAsync(c->sp_snapn.p, 0, sizeof(uint32_t) * ((size_t)n + j->nrec), st));
-  avr::SplitArgs sa;
-  sa.ctl = c->sp_ctl.as<avr::PieceCtl>();
-  sa.recs = c->sp_recs.as<uint8_t>();
-  sa.rec_stride = (uint32_t)j->stride;
-  sa.split_bits = j->split_bits;
-  sa.snap_n = c->sp_snapn.as<uint32_t>();
-  sa.piece_end = sa.snap_n + n;
-  HIP_TRY(c, hipEventRecord(j->ev.e0, st));
-  HIP_TRY(c, avr::launch_split(0, c->tables.as<avr::EngineTables>(), c->sp_descs.as<avr_slice_desc>(), n, j->max_w,
-                               c->sp_in.as<uint8_t>(), c->sp_out.as<uint8_t>(), c->sp_res.as<avr_slice_result>(),
-                               c->sp_est.as<uint16_t>(), sa, j->flags, st));
-  HIP_TRY(c, hipEventRecord(j->ev.e1, st));
-  return AVR_OK;
+  uint32_t* cuts = c->sp_snapn.as<uint32_t>();   // then the piece ends
+  return launch_split_walk(c, c->sp_descs.as<avr_slice_desc>(), n, j->max_w, c->sp_in.as<uint8_t>(),
+                           c->sp_out.as<uint8_t>(), c->sp_res.as<avr_slice_result>(), j->slots.data(),
+                           c->sp_recs.as<uint8_t>(), (int)j->nrec, j->stride, cuts, cuts + n, split_bytes,
+                           flags & avr::kFlagBill, st, &j->ctl, &c->sp_ctl, &j->ev);
 }
 
 // One launch of pieces on the split stream: descs / ctl uploaded, records already in sp_recs,
@@ -454,9 +484,9 @@ int split_wait(avr_ctx* c, SplitPending* pend) {
   c->phase.kernel_s += 1e-3 * ms;
   return AVR_OK;
 }
-int split_launch(avr_ctx* c, int mode, std::vector<avr_slice_desc>& d, const std::vector<avr::PieceCtl>& ctl,
-                 const uint8_t* in_dev, int max_w, size_t stride, uint32_t flags, std::vector<avr_slice_result>* res,
-                 Bytes* out, DevBuf* out_dev, SplitPending* pending = nullptr) {
+int split_launch(avr_ctx* c, std::vector<avr_slice_desc>& d, const std::vector<avr::PieceCtl>& ctl, const uint8_t* in_dev,
+                 int max_w, size_t stride, uint32_t flags, std::vector<avr_slice_result>* res, Bytes* out,
+                 DevBuf* out_dev, SplitPending* pending = nullptr) {
   const int n = (int)d.size();
   uint64_t total = 0;
   for (auto& x : d) place_output(&x, &total);
@@ -467,23 +497,16 @@ int split_launch(avr_ctx* c, int mode, std::vector<avr_slice_desc>& d, const std
   HIP_TRY(c, out_dev->reserve(total + 4096));
   HIP_TRY(c, c->sp_descs.reserve(sizeof(avr_slice_desc) * n));
   HIP_TRY(c, c->sp_res.reserve(sizeof(avr_slice_result) * n));
-  HIP_TRY(c, c->sp_ctl.reserve(sizeof(avr::PieceCtl) * n));
-  HIP_TRY(c, c->sp_est.reserve(sizeof(uint16_t) * (size_t)avr::kEstGlobal * std::max(1, avr::split_grid(n, max_w)), true));
   HIP_TRY(c, hipMemcpyAsync(c->sp_descs.p, d.data(), sizeof(avr_slice_desc) * n, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(c->sp_ctl.p, ctl.data(), sizeof(avr::PieceCtl) * n, hipMemcpyHostToDevice, st));
   avr::SplitArgs sa;
-  sa.ctl = c->sp_ctl.as<avr::PieceCtl>();
   sa.recs = c->sp_recs.as<uint8_t>();
   sa.rec_stride = (uint32_t)stride;
   SplitPending local;
   SplitPending* pend = pending ? pending : &local;
-  HIP_TRY(c, hipEventCreate(&pend->ev.e0));
-  HIP_TRY(c, hipEventCreate(&pend->ev.e1));
-  HIP_TRY(c, hipEventRecord(pend->ev.e0, st));
-  HIP_TRY(c, avr::launch_split(mode, c->tables.as<avr::EngineTables>(), c->sp_descs.as<avr_slice_desc>(), n, max_w,
-                               in_dev, out_dev->as<uint8_t>(), c->sp_res.as<avr_slice_result>(), c->sp_est.as<uint16_t>(),
-                               sa, flags, st));
-  HIP_TRY(c, hipEventRecord(pend->ev.e1, st));
+  if (int r = pend->ev.create(c)) return r;
+  if (int r = launch_split_ctl(c, 1, c->sp_descs.as<avr_slice_desc>(), n, max_w, in_dev, out_dev->as<uint8_t>(),
+                               c->sp_res.as<avr_slice_result>(), ctl.data(), &c->sp_ctl, sa, flags, st, &pend->ev))
+    return r;
   pend->res = res->data();
   pend->res_dev = c->sp_res.p;
   pend->res_bytes = sizeof(avr_slice_result) * n;
@@ -511,97 +534,47 @@ int split_finish(avr_ctx* c, SplitJob* j, bool verify, std::vector<SplitOut>* ou
   HIP_TRY(c, hipEventElapsedTime(&ms, j->ev.e0, j->ev.e1));
   if (split_timing()) fprintf(stderr, "split: compress kernel %.3f s (%d slices)\n", 1e-3 * ms, n);
   c->phase.kernel_s += 1e-3 * ms;
-  const uint32_t* piece_end = cnt.data() + n;
-  // 2) every cut checked against the host's restatement (seam_encoder), the pieces' lengths
-  std::vector<std::vector<const avr::SeamRec*>> cuts(n);
-  std::vector<std::vector<SeamCe>> ces(n);
-  std::vector<std::vector<uint32_t>> plen(n);
+  // 2) the seams step (seams_build): every cut checked against the host's restatement, the pieces'
+  //    lengths, the fields.  What the device wrote and does not fit fails its slice.
+  std::vector<SliceSeams> ss;
+  if (seams_build(j->d.data(), n, j->arena.data(), j->arena.size(), r1.data(), j->slots.data(), cnt.data(),
+                  cnt.data() + n, (int)j->nrec, recs.data(), j->stride, true, AVR_SLICE_CODER, &ss))
+    return fail(c, AVR_ERR_DEVICE, "zlib failed");
   for (int k = 0; k < n; k++) {
     SplitOut& so = (*out)[k];
-    so.status = r1[k].status;
+    so.status = ss[k].status;
     so.bill = r1[k];
     if (so.status) continue;
-    const avr::SliceInfo& s = *j->sl[k];
-    const uint32_t nc = cnt[k], base = (uint32_t)j->ctl[k].snap;
-    if (nc >= j->ctl[k].snap_cap || piece_end[base + nc] != r1[k].out_len) {
-      so.status = AVR_SLICE_CODER;
-      continue;
-    }
-    for (uint32_t i = 0; i < nc && !so.status; i++) {
-      const avr::SeamRec* r = (const avr::SeamRec*)(recs.data() + (size_t)(base + i) * j->stride);
-      SeamCe ce;
-      const uint64_t bitpos = 8ull * r->cd_next - r->cd_k;
-      if (!seam_encoder(s.payload(), s.size, bitpos, r->cd_low >> r->cd_k, r->cd_range, &ce) || ce.q != r->q ||
-          ce.low != r->ce_low || ce.range != r->ce_range || ce.outstanding != r->ce_outstanding ||
-          ce.cache != r->ce_cache || ce.queue != r->ce_queue)
-        so.status = AVR_SLICE_CODER;
-      cuts[k].push_back(r);
-      ces[k].push_back(ce);
-    }
-    for (uint32_t i = 0; i <= nc; i++) plen[k].push_back(piece_end[base + i] - (i ? piece_end[base + i - 1] : 0u));
-    if (!so.status)
-      so.recoded.assign(out1.begin() + j->d[k].out_offset, out1.begin() + j->d[k].out_offset + r1[k].out_len);
+    so.recoded.assign(out1.begin() + j->d[k].out_offset, out1.begin() + j->d[k].out_offset + r1[k].out_len);
+    so.seams.swap(ss[k].field);
   }
   // 3) verify: the pieces decompressed from the records as a container gives them, spliced, compared
-  if (verify) {
-    std::vector<avr_slice_desc> dd;
-    std::vector<avr::PieceCtl> pc;
-    std::vector<int> first(n, -1);
-    Bytes arena;
-    for (int k = 0; k < n; k++) {
-      if ((*out)[k].status) continue;
-      first[k] = (int)dd.size();
-      uint64_t off = 0;
-      const size_t np = cuts[k].size() + 1;
-      for (size_t i = 0; i < np; i++) {
-        avr_slice_desc d = j->d[k];
-        if (i) d.first_mb = (int32_t)cuts[k][i - 1]->first_mb;
-        append_aligned(&arena, (*out)[k].recoded.data() + off, plen[k][i], 16, &d.payload_offset);
-        off += plen[k][i];
-        d.payload_size = d.read_limit = plen[k][i];
-        d.out_capacity = (uint32_t)j->sl[k]->size + 4096;
-        const uint32_t next = i + 1 < np ? cuts[k][i]->first_mb : 0u;
-        pc.push_back(avr::PieceCtl{i ? j->ctl[k].snap + (int32_t)i - 1 : -1, next ? next - (uint32_t)d.first_mb : 0u,
-                                   -1, 0});
-        dd.push_back(d);
-      }
-    }
-    if (!dd.empty()) {
-      HIP_TRY(c, c->sp_in2.reserve(arena.size() + 4096));
-      HIP_TRY(c, hipMemcpyAsync(c->sp_in2.p, arena.data(), arena.size(), hipMemcpyHostToDevice, st));
-      std::vector<avr_slice_result> r3;
-      Bytes out3;
-      if (int e = split_launch(c, 1, dd, pc, c->sp_in2.as<uint8_t>(), j->max_w, j->stride, 0, &r3, &out3, &c->sp_out2))
-        return e;
-      for (int k = 0; k < n; k++) {
-        if (first[k] < 0) continue;
-        const avr::SliceInfo& s = *j->sl[k];
-        const size_t np = cuts[k].size() + 1;
-        std::vector<const uint8_t*> p(np);
-        std::vector<uint32_t> len(np), q(np - 1);
-        std::vector<int32_t> stt(np);
-        for (size_t i = 0; i < np; i++) {
-          const int x = first[k] + (int)i;
-          p[i] = out3.data() + dd[x].out_offset;
-          len[i] = r3[x].out_len;
-          stt[i] = r3[x].status;
-          if (i + 1 < np) q[i] = ces[k][i].q;
-        }
-        std::vector<uint8_t> regen;
-        bool ok = splice_pieces(p, len, stt, q, &regen);
-        if (ok) {
-          last_byte_patch(&regen, s.payload(), s.size);
-          ok = regen.size() == s.size && memcmp(regen.data(), s.payload(), s.size) == 0;
-        }
-        if (!ok) (*out)[k].status = AVR_SLICE_NO_ROUNDTRIP;
-      }
-    }
+  Plan vp;
+  std::vector<avr::PieceCtl> pc;
+  std::vector<int> first(n, -1);
+  for (int k = 0; verify && k < n; k++) {
+    if ((*out)[k].status) continue;
+    first[k] = (int)vp.descs.size();
+    append_pieces(&vp, &pc, j->d[k], (*out)[k].recoded.data(), ss[k].piece_len, ss[k].first_mb,
+                  (uint32_t)j->slots[k].first, [&](size_t) { return (uint32_t)j->sl[k]->size + 4096; });
   }
-  // 4) the seams fields
+  if (vp.descs.empty()) return AVR_OK;
+  HIP_TRY(c, c->sp_in2.reserve(vp.arena.size() + 4096));
+  HIP_TRY(c, hipMemcpyAsync(c->sp_in2.p, vp.arena.data(), vp.arena.size(), hipMemcpyHostToDevice, st));
+  std::vector<avr_slice_result> r3;
+  Bytes out3;
+  if (int e = split_launch(c, vp.descs, pc, c->sp_in2.as<uint8_t>(), j->max_w, j->stride, 0, &r3, &out3, &c->sp_out2))
+    return e;
   for (int k = 0; k < n; k++) {
-    SplitOut& so = (*out)[k];
-    if (so.status || cuts[k].empty()) continue;
-    if (!seams_encode(cuts[k], ces[k], j->d[k], plen[k], &so.seams)) return fail(c, AVR_ERR_DEVICE, "zlib failed");
+    if (first[k] < 0) continue;
+    const avr::SliceInfo& s = *j->sl[k];
+    std::vector<uint8_t> regen;
+    bool ok = splice_pieces(&vp.descs[first[k]], &r3[first[k]], out3.data(), ss[k].q, &regen);
+    if (ok) {
+      last_byte_patch(&regen, s.payload(), s.size);
+      ok = regen.size() == s.size && memcmp(regen.data(), s.payload(), s.size) == 0;
+    }
+    if (!ok) (*out)[k].status = AVR_SLICE_NO_ROUNDTRIP;
   }
   return AVR_OK;
 }
@@ -661,7 +634,7 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   //    carry the same parse / restore verdict) and demotes the failures, so a well-formed file
   //    costs one reference-model pass, not a parallel-model pass before it.
   Plan plan;
-  // the parallel model's long slices (split_candidate): the split job, its first pass on the split
+  // the parallel model's long slices (split_slot): the split job, its first pass on the split
   // stream beside the batch (cand_of = -2 - index there)
   SplitJob sj;
   const size_t split_bytes = model == AVR_MODEL_PARALLEL ? c->split_bytes : 0;
@@ -674,9 +647,11 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
       if (!recodable_candidate(s)) continue;
       avr_slice_desc d = desc_from_header(s);
       d.payload_size = (uint32_t)s.size;
-      if (split_candidate(d, split_bytes)) {
+      uint64_t cap, oc;
+      if (split_slot(d, split_bytes, &cap, &oc)) {
         cand_of[f][i] = -2 - (int)sj.sl.size();
         sj.sl.push_back(&s);
+        sj.d.push_back(d);
         continue;
       }
       append_aligned(&plan.arena, s.payload(), s.read_limit, 16, &d.payload_offset);
@@ -880,8 +855,8 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
     HIP_TRY(c, c->sp_recs.reserve(sp.recs.size() + 64));
     HIP_TRY(c, hipMemcpyAsync(c->sp_in.p, sp.plan.arena.data(), sp.plan.arena.size(), hipMemcpyHostToDevice, ss));
     HIP_TRY(c, hipMemcpyAsync(c->sp_recs.p, sp.recs.data(), sp.recs.size(), hipMemcpyHostToDevice, ss));
-    if (int r = split_launch(c, 1, sp.plan.descs, sp.ctl, c->sp_in.as<uint8_t>(), sp.plan.max_w, sp.stride, flags, &pr,
-                             &po, &c->sp_out, &pend)) {
+    if (int r = split_launch(c, sp.plan.descs, sp.ctl, c->sp_in.as<uint8_t>(), sp.plan.max_w, sp.stride, flags, &pr, &po,
+                             &c->sp_out, &pend)) {
       (void)hipStreamSynchronize(ss);
       return r;
     }
@@ -907,19 +882,10 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
     for (int f = 0; f < nf; f++) {
       if (st[f]) continue;
       for (SplitBlock& x : jobs[f].splits) {
-        std::vector<const uint8_t*> pp(x.pieces);
-        std::vector<uint32_t> len(x.pieces);
-        std::vector<int32_t> stt(x.pieces);
-        for (int i = 0; i < x.pieces; i++) {
-          const int k = x.first + i;
-          pp[i] = po.data() + sp.plan.descs[k].out_offset;
-          len[i] = pr[k].out_len;
-          stt[i] = pr[k].status;
+        for (int k = x.first; k < x.first + x.pieces; k++)
           if (pr[k].status == 0)
             for (int b = 0; b < 6; b++) x.bill.bill[b] += pr[k].bill[b];
-        }
-        x.status = splice_pieces(pp, len, stt, x.q, &x.regen) ? 0 : AVR_SLICE_NO_END;
-        for (int i = 0; i < x.pieces && !x.status; i++) x.status = stt[i];
+        x.status = splice_pieces(&sp.plan.descs[x.first], &pr[x.first], po.data(), x.q, &x.regen) ? 0 : AVR_SLICE_NO_END;
       }
     }
     c->plan_wall += t_split + (now_s() - t);
@@ -1688,20 +1654,13 @@ int avr_decompress_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_pi
   if (!n) return AVR_OK;
   return guarded(c, [&]() -> int {
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
     c->pc_host.resize(n);
     for (int k = 0; k < n; k++) c->pc_host[k] = avr::PieceCtl{pieces[k].seam, pieces[k].n_mbs, -1, 0};
-    HIP_TRY(c, c->pc_ctl.reserve(sizeof(avr::PieceCtl) * n));
-    HIP_TRY(c, c->sp_est.reserve(sizeof(uint16_t) * (size_t)avr::kEstGlobal * std::max(1, avr::split_grid(n, max_w)), true));
-    if (!d_recs) HIP_TRY(c, c->sp_recs.reserve(64));   // a batch without cuts: no record is read
-    HIP_TRY(c, hipMemcpyAsync(c->pc_ctl.p, c->pc_host.data(), sizeof(avr::PieceCtl) * n, hipMemcpyHostToDevice, st));
     avr::SplitArgs sa;
-    sa.ctl = c->pc_ctl.as<avr::PieceCtl>();
-    sa.recs = d_recs ? const_cast<uint8_t*>(d_recs) : c->sp_recs.as<uint8_t>();
+    sa.recs = const_cast<uint8_t*>(d_recs);
     sa.rec_stride = (uint32_t)rec_stride;
-    HIP_TRY(c, avr::launch_split(1, c->tables.as<avr::EngineTables>(), d_desc, n, max_w, d_in, d_out, d_res,
-                                 c->sp_est.as<uint16_t>(), sa, 0, st));
-    return AVR_OK;
+    return launch_split_ctl(c, 1, d_desc, n, max_w, d_in, d_out, d_res, c->pc_host.data(), &c->pc_ctl, sa, 0,
+                            (hipStream_t)stream, nullptr);
   });
 }
 
@@ -1716,11 +1675,9 @@ int avr_pack_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* d
   return AVR_OK;
 }
 
-// split_begin's launch for a caller's device-resident batch (include/avrecode.h, ABI 8): the split
-// walk on the caller's stream into the caller's records, cut counts and piece ends.  The slots are
-// checked here, before anything is launched: a record outside d_recs would be written.  The kernel
-// gets one record less than each slot holds: a walk that filled its slot would write the end of its
-// last piece one entry past it, and avr_split_plan's slots have that one to spare (cuts < cap).
+// The split walk (launch_split_walk) for a caller's device-resident batch (include/avrecode.h, ABI 8):
+// on the caller's stream into the caller's records, cut counts and piece ends.  The slots are checked
+// here, before anything is launched: a record outside d_recs would be written.
 int avr_compress_split_slices(avr_ctx* c, const avr_slice_desc* d_desc, int n, int max_w, int max_h,
                               const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res,
                               const avr_split_slot* slots, size_t split_bytes, uint8_t* d_recs, int n_recs,
@@ -1742,27 +1699,8 @@ int avr_compress_split_slices(avr_ctx* c, const avr_slice_desc* d_desc, int n, i
   if (!n) return AVR_OK;
   return guarded(c, [&]() -> int {
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    c->sc_host.resize(n);
-    for (int k = 0; k < n; k++)
-      c->sc_host[k] = slots[k].first < 0 ? avr::PieceCtl{-1, 0, -1, 0}
-                                         : avr::PieceCtl{-1, 0, slots[k].first, slots[k].cap - 1};
-    HIP_TRY(c, c->sc_ctl.reserve(sizeof(avr::PieceCtl) * n));
-    HIP_TRY(c, c->sp_est.reserve(sizeof(uint16_t) * (size_t)avr::kEstGlobal * std::max(1, avr::split_grid(n, max_w)), true));
-    if (!d_recs) HIP_TRY(c, c->sp_recs.reserve(64));   // a batch without slots: no record is written
-    HIP_TRY(c, hipMemcpyAsync(c->sc_ctl.p, c->sc_host.data(), sizeof(avr::PieceCtl) * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(d_cuts, 0, sizeof(uint32_t) * n, st));
-    if (n_recs) HIP_TRY(c, hipMemsetAsync(d_piece_end, 0, sizeof(uint32_t) * n_recs, st));
-    avr::SplitArgs sa;
-    sa.ctl = c->sc_ctl.as<avr::PieceCtl>();
-    sa.recs = d_recs ? d_recs : c->sp_recs.as<uint8_t>();
-    sa.rec_stride = (uint32_t)rec_stride;
-    sa.split_bits = (uint32_t)(8 * split_bytes);
-    sa.snap_n = d_cuts;
-    sa.piece_end = n_recs ? d_piece_end : nullptr;
-    HIP_TRY(c, avr::launch_split(0, c->tables.as<avr::EngineTables>(), d_desc, n, max_w, d_in, d_out, d_res,
-                                 c->sp_est.as<uint16_t>(), sa, 0, st));
-    return AVR_OK;
+    return launch_split_walk(c, d_desc, n, max_w, d_in, d_out, d_res, slots, d_recs, n_recs, rec_stride, d_cuts,
+                             d_piece_end, split_bytes, 0, (hipStream_t)stream, &c->sc_host, &c->sc_ctl, nullptr);
   });
 }
 

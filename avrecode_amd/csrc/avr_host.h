@@ -217,9 +217,25 @@ bool seam_encoder(const uint8_t* pay, size_t n, uint64_t bitpos, uint32_t offset
 bool seams_encode(const std::vector<const avr::SeamRec*>& recs, const std::vector<SeamCe>& ce, const avr_slice_desc& d,
                   const std::vector<uint32_t>& piece_len, std::vector<uint8_t>* out);
 bool seams_decode(const uint8_t* p, size_t n, const avr_slice_desc& d, size_t rec_stride, SeamsDecoded* sd);
-bool splice_pieces(const std::vector<const uint8_t*>& p, const std::vector<uint32_t>& len,
-                   const std::vector<int32_t>& status, const std::vector<uint32_t>& q, std::vector<uint8_t>* o);
+bool splice_pieces(const avr_slice_desc* d, const avr_slice_result* r, const uint8_t* out, const std::vector<uint32_t>& q,
+                   std::vector<uint8_t>* o);
 void last_byte_patch(std::vector<uint8_t>* o, const uint8_t* payload, size_t size);
+// The long-slice split's rule and sizes: whether the parallel model's compress takes d (payload_size
+// set) through the split walk at split_bytes, the cut records of its slot and its output space.
+bool split_slot(const avr_slice_desc& d, size_t split_bytes, uint64_t* cap, uint64_t* out_capacity);
+// The seams step over what a split walk has left (the arrays of avr_seams_build, include/avrecode.h,
+// with rec_stride > 0 and n_recs records in recs): every index checked before anything is read
+// through it, every cut checked against seam_encoder (check_cuts), the pieces' lengths, Block field 16.
+// A slice whose indices do not fit the arrays gets status `misfit`, or with misfit 0 (the caller
+// brought the arrays) fails the call: AVR_ERR_INVALID_ARGUMENT.  AVR_ERR_OUT_OF_MEMORY: zlib failed.
+struct SliceSeams {
+  int32_t status = 0;           // res[k].status, misfit, or AVR_SLICE_CODER: a cut the host does not restate
+  std::vector<uint8_t> field;   // status 0 and at least one cut
+  std::vector<uint32_t> piece_len, first_mb, q;   // status 0, in a slot: per piece; per cut
+};
+int seams_build(const avr_slice_desc* descs, int n, const uint8_t* arena, size_t arena_len, const avr_slice_result* res,
+                const avr_split_slot* slots, const uint32_t* cuts, const uint32_t* piece_end, int n_recs,
+                const uint8_t* recs, size_t rec_stride, bool check_cuts, int32_t misfit, std::vector<SliceSeams>* out);
 
 // ------------------------------------------------------------------ avr_plan.cpp: the decompress planner
 // A split block (the parallel model's long-slice split): its pieces in the split plan, the cuts' q
@@ -238,6 +254,27 @@ struct SplitPlan {
   size_t stride = avr::seam_rec_bytes(kMringCols);
   static constexpr int kMringCols = avr::kMringCols;   // widest picture a record holds
 };
+// The pieces of a cut slice appended to a plan: copies of its descriptor d, piece i's stream
+// (piece_len[i] bytes of `streams`, one after the other) in the arena, starting at cut i - 1's
+// first_mb and record rec0 + i - 1 (the slice's own start for piece 0), out_capacity(i) bytes of output.
+template <class Cap>
+void append_pieces(Plan* plan, std::vector<avr::PieceCtl>* ctl, const avr_slice_desc& d, const uint8_t* streams,
+                   const std::vector<uint32_t>& piece_len, const std::vector<uint32_t>& first_mb, uint32_t rec0,
+                   Cap&& out_capacity) {
+  const size_t cuts = first_mb.size();
+  uint64_t off = 0;
+  for (size_t i = 0; i <= cuts; i++) {
+    avr_slice_desc pd = d;
+    if (i) pd.first_mb = (int32_t)first_mb[i - 1];
+    append_aligned(&plan->arena, streams + off, piece_len[i], 16, &pd.payload_offset);
+    off += piece_len[i];
+    pd.payload_size = pd.read_limit = piece_len[i];
+    pd.out_capacity = out_capacity(i);
+    plan->max_w = std::max(plan->max_w, pd.mb_width);
+    plan->descs.push_back(pd);
+    ctl->push_back(avr::PieceCtl{i ? (int32_t)(rec0 + i - 1) : -1, i < cuts ? first_mb[i] - (uint32_t)pd.first_mb : 0u, -1, 0});
+  }
+}
 struct DecJob {
   std::vector<avr::PbBlock> blocks;
   Bytes stream;                      // read_packet's stream: literals + surrogate blocks

@@ -110,19 +110,9 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
       x.q = sd.q;
       const uint32_t rec0 = (uint32_t)(sp->recs.size() / sp->stride);
       sp->recs.insert(sp->recs.end(), sd.recs.begin(), sd.recs.end());
-      uint64_t off = 0;
-      for (int i = 0; i <= sd.cuts; i++) {
-        avr_slice_desc pd = d;
-        if (i) pd.first_mb = (int32_t)sd.first_mb[i - 1];
-        append_aligned(&sp->plan.arena, b.cabac + off, sd.piece_len[i], 16, &pd.payload_offset);
-        off += sd.piece_len[i];
-        pd.payload_size = pd.read_limit = sd.piece_len[i];
-        pd.out_capacity = (uint32_t)((i < sd.cuts ? sd.q[i] : (uint32_t)b.size) - (i ? sd.q[i - 1] : 0u) + 4096);
-        sp->plan.max_w = std::max(sp->plan.max_w, pd.mb_width);
-        sp->plan.descs.push_back(pd);
-        sp->ctl.push_back(avr::PieceCtl{i ? (int32_t)(rec0 + i - 1) : -1,
-                                        i < sd.cuts ? sd.first_mb[i] - (uint32_t)pd.first_mb : 0u, -1, 0});
-      }
+      append_pieces(&sp->plan, &sp->ctl, d, b.cabac, sd.piece_len, sd.first_mb, rec0, [&](size_t i) {   // its share of q
+        return (uint32_t)((i < (size_t)sd.cuts ? sd.q[i] : (uint32_t)b.size) - (i ? sd.q[i - 1] : 0u) + 4096);
+      });
       j->desc_of_block[next_coded] = -2 - (int)j->splits.size();
       j->splits.push_back(std::move(x));
       next_coded++;

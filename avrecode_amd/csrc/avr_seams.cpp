@@ -1,9 +1,10 @@
 // The seams codec of the parallel model's long-slice split (avr_api.cpp, "the long-slice split"):
 // the re-encoder state at a cut restated on the host, Block field 16 written and read, and the
-// splice of a split slice's pieces; at the end, the host steps of the split compress of slice batches
-// (avr_split_plan, avr_seams_build).  No HIP: seams_decode reads untrusted bytes and is reached by
-// the stand-alone sanitizer program tests/native/plan_fuzz.cpp, avr_seams_build reads what a caller
-// brought back from its device and is reached by tests/native/seams_build_fuzz.cpp.
+// splice of a split slice's pieces; at the end, the host steps of the split's compress side (split_slot,
+// seams_build), which the whole-file compress and the ABI's avr_split_plan / avr_seams_build share.
+// No HIP: seams_decode reads untrusted bytes and is reached by the stand-alone sanitizer program
+// tests/native/plan_fuzz.cpp, seams_build reads what came back from a device and is reached through
+// avr_seams_build by tests/native/seams_build_fuzz.cpp.
 #include <zlib.h>
 
 #include "avr_host.h"
@@ -148,21 +149,22 @@ bool seams_decode(const uint8_t* p, size_t n, const avr_slice_desc& d, size_t re
   return true;
 }
 
-// the regenerated bytes of a split slice: piece i's bytes up to cut i's q (the cut's first byte),
-// the last piece whole; false if a piece failed or came out short
-bool splice_pieces(const std::vector<const uint8_t*>& p, const std::vector<uint32_t>& len,
-                   const std::vector<int32_t>& status, const std::vector<uint32_t>& q, std::vector<uint8_t>* o) {
+// the regenerated bytes of a split slice from its q.size() + 1 pieces, units d[i] / r[i] of a pieces
+// launch that wrote `out`: piece i's bytes up to cut i's q (the cut's first byte), the last piece
+// whole; false if a piece failed or came out short
+bool splice_pieces(const avr_slice_desc* d, const avr_slice_result* r, const uint8_t* out, const std::vector<uint32_t>& q,
+                   std::vector<uint8_t>* o) {
   o->clear();
-  for (size_t i = 0; i < p.size(); i++) {
-    if (status[i]) return false;
+  for (size_t i = 0; i <= q.size(); i++) {
+    if (r[i].status) return false;
     const size_t start = i ? q[i - 1] : 0;
     if (o->size() != start) return false;
-    size_t keep = len[i];
+    size_t keep = r[i].out_len;
     if (i < q.size()) {
-      if (q[i] < start || q[i] - start > len[i]) return false;
+      if (q[i] < start || q[i] - start > keep) return false;
       keep = q[i] - start;
     }
-    o->insert(o->end(), p[i], p[i] + keep);
+    o->insert(o->end(), out + d[i].out_offset, out + d[i].out_offset + keep);
   }
   return true;
 }
@@ -173,34 +175,106 @@ void last_byte_patch(std::vector<uint8_t>* o, const uint8_t* payload, size_t siz
   else if (!o->empty()) o->back() = payload[size - 1];
 }
 
+// ------------------------------------------------------------ the compress side of the split
+bool split_slot(const avr_slice_desc& d, size_t split_bytes, uint64_t* cap, uint64_t* out_capacity) {
+  if (!split_bytes || split_bytes >= ((size_t)1 << 28) || d.structure != AVR_STRUCT_FRAME || d.mb_width < 1 ||
+      d.mb_width > avr::kMringCols || 2 * (uint64_t)d.payload_size < 3 * (uint64_t)split_bytes)
+    return false;
+  *cap = 8ull * d.payload_size / (8ull * split_bytes) + 1;
+  *out_capacity = 2ull * d.payload_size + 256 + 64 * *cap;
+  return true;
+}
+
+int seams_build(const avr_slice_desc* descs, int n, const uint8_t* arena, size_t arena_len, const avr_slice_result* res,
+                const avr_split_slot* slots, const uint32_t* cuts, const uint32_t* piece_end, int n_recs,
+                const uint8_t* recs, size_t rec_stride, bool check_cuts, int32_t misfit, std::vector<SliceSeams>* out) {
+  out->assign(n, SliceSeams());
+  // every index first: nothing below reads out of range
+  for (int k = 0; k < n; k++) {
+    const avr_split_slot& s = slots[k];
+    const avr_slice_desc& d = descs[k];
+    SliceSeams& o = (*out)[k];
+    o.status = res[k].status;
+    bool fits = true;
+    if (s.first == -1 && s.cap == 0) {
+      fits = cuts[k] == 0;
+    } else if (s.first < 0 || s.cap == 0 || (uint64_t)s.first + s.cap > (uint64_t)n_recs || cuts[k] >= s.cap) {
+      fits = false;
+    } else if (!o.status) {
+      // (slice_type / cabac_init_idc index the context init tables of the field's state XOR)
+      fits = d.mb_width >= 1 && d.mb_width <= avr::kMringCols && rec_stride >= avr::seam_rec_bytes(d.mb_width) &&
+             d.payload_offset <= arena_len && d.payload_size <= arena_len - d.payload_offset && d.slice_type >= 0 &&
+             d.slice_type <= 2 && (d.slice_type == 2 || (d.cabac_init_idc >= 0 && d.cabac_init_idc <= 2));
+      uint32_t prev = 0;
+      for (uint32_t i = 0; fits && i <= cuts[k]; i++) {
+        const uint32_t e = piece_end[s.first + i];
+        fits = e >= prev;
+        o.piece_len.push_back(e - prev);
+        prev = e;
+      }
+      fits = fits && prev == res[k].out_len;
+    }
+    if (fits) continue;
+    if (!misfit) return AVR_ERR_INVALID_ARGUMENT;
+    o.status = misfit;
+  }
+  for (int k = 0; k < n; k++) {
+    SliceSeams& o = (*out)[k];
+    const uint32_t nc = cuts[k];
+    if (o.status || !nc) continue;
+    const avr_slice_desc& d = descs[k];
+    std::vector<const avr::SeamRec*> rp;
+    std::vector<SeamCe> ce(nc);
+    // copies of the records: the caller's buffer and stride need not be aligned for a SeamRec
+    const size_t rb = avr::seam_rec_bytes(d.mb_width);
+    std::vector<uint64_t> copy((rb / 8 + 1) * nc);
+    for (uint32_t i = 0; i < nc; i++) {
+      uint64_t* raw = copy.data() + (rb / 8 + 1) * i;
+      memcpy(raw, recs + (size_t)((uint32_t)slots[k].first + i) * rec_stride, rb);
+      const avr::SeamRec& r = *(const avr::SeamRec*)raw;
+      SeamCe& c = ce[i];
+      if (check_cuts) {
+        const uint64_t bitpos = 8ull * r.cd_next - r.cd_k;
+        if (r.cd_k >= 32 || 8ull * r.cd_next < r.cd_k ||
+            !seam_encoder(arena + d.payload_offset, d.payload_size, bitpos, r.cd_low >> r.cd_k, r.cd_range, &c) ||
+            c.q != r.q || c.low != r.ce_low || c.range != r.ce_range || c.outstanding != r.ce_outstanding ||
+            c.cache != r.ce_cache || c.queue != r.ce_queue) {
+          o.status = AVR_SLICE_CODER;
+          break;
+        }
+      } else {
+        c = SeamCe{r.q, r.ce_low, r.ce_outstanding, r.ce_cache, r.ce_range, r.ce_queue};
+      }
+      rp.push_back(&r);
+      o.first_mb.push_back(r.first_mb);
+      o.q.push_back(c.q);
+    }
+    if (!o.status && !seams_encode(rp, ce, d, o.piece_len, &o.field)) return AVR_ERR_OUT_OF_MEMORY;
+  }
+  return AVR_OK;
+}
+
 }  // namespace avr_host
 
 // ------------------------------------------------------------ the split compress of slice batches
-// (include/avrecode.h, ABI 8): the whole-file compress's rule and sizes (avr_api.cpp split_candidate /
-// split_begin) and its seams step (split_finish 2 and 4) for a caller that ran the split walk over
-// its own device buffers.  Everything read here is the caller's: every index is checked first.
+// (include/avrecode.h, ABI 8): the rule and sizes, and the seams step, for a caller that ran the split
+// walk over its own device buffers.  Everything read here is the caller's.
 extern "C" {
 
 int avr_split_plan(const avr_slice_desc* descs, int n, size_t split_bytes, avr_split_slot* slots,
                    uint32_t* out_capacity, int* n_recs, size_t* rec_stride, int* n_candidates) {
   if (n < 0 || (n && (!descs || !slots)) || !n_recs || !rec_stride) return AVR_ERR_INVALID_ARGUMENT;
-  const bool on = split_bytes && split_bytes < ((size_t)1 << 28);
-  uint64_t nrec = 0;
+  uint64_t nrec = 0, cap, oc;
   int max_w = 1, cand = 0;
   for (int k = 0; k < n; k++) {
-    const avr_slice_desc& d = descs[k];
     slots[k] = avr_split_slot{-1, 0};
     if (out_capacity) out_capacity[k] = 0;
-    if (!on || d.structure != AVR_STRUCT_FRAME || d.mb_width < 1 || d.mb_width > avr::kMringCols ||
-        2 * (uint64_t)d.payload_size < 3 * (uint64_t)split_bytes)
-      continue;
-    const uint64_t cap = 8ull * d.payload_size / (8ull * split_bytes) + 1;
-    const uint64_t oc = 2ull * d.payload_size + 256 + 64 * cap;
+    if (!avr_host::split_slot(descs[k], split_bytes, &cap, &oc)) continue;
     if (nrec + cap > INT32_MAX || oc > UINT32_MAX) return AVR_ERR_INVALID_ARGUMENT;
     slots[k] = avr_split_slot{(int32_t)nrec, (uint32_t)cap};
     if (out_capacity) out_capacity[k] = (uint32_t)oc;
     nrec += cap;
-    max_w = std::max(max_w, (int)d.mb_width);
+    max_w = std::max(max_w, (int)descs[k].mb_width);
     cand++;
   }
   *n_recs = (int)nrec;
@@ -221,79 +295,31 @@ int avr_seams_build(const avr_slice_desc* descs, int n, const uint8_t* arena, si
     return AVR_ERR_INVALID_ARGUMENT;
   *seams = nullptr;
   *seams_len = 0;
-  // every index first: nothing below reads out of range
-  for (int k = 0; k < n; k++) {
-    const avr_split_slot& s = slots[k];
-    const avr_slice_desc& d = descs[k];
-    if (s.first == -1 && s.cap == 0) {
-      if (cuts[k]) return AVR_ERR_INVALID_ARGUMENT;
-      continue;
-    }
-    if (s.first < 0 || s.cap == 0 || (uint64_t)s.first + s.cap > (uint64_t)n_recs || cuts[k] >= s.cap)
-      return AVR_ERR_INVALID_ARGUMENT;
-    if (res[k].status) continue;
-    // (slice_type / cabac_init_idc index the context init tables of the field's state XOR)
-    if (d.mb_width < 1 || d.mb_width > avr::kMringCols || rec_stride < avr::seam_rec_bytes(d.mb_width) ||
-        d.payload_offset > arena_len || d.payload_size > arena_len - d.payload_offset || d.slice_type < 0 ||
-        d.slice_type > 2 || (d.slice_type != 2 && (d.cabac_init_idc < 0 || d.cabac_init_idc > 2)))
-      return AVR_ERR_INVALID_ARGUMENT;
-    uint32_t prev = 0;
-    for (uint32_t i = 0; i <= cuts[k]; i++) {
-      const uint32_t e = piece_end[s.first + i];
-      if (e < prev) return AVR_ERR_INVALID_ARGUMENT;
-      prev = e;
-    }
-    if (prev != res[k].out_len) return AVR_ERR_INVALID_ARGUMENT;
-  }
   return guarded(nullptr, [&]() -> int {
-    std::vector<uint8_t> blob, field;
-    for (int k = 0; k < n; k++) {
-      status[k] = res[k].status;
-      offsets[k] = blob.size();
-      lens[k] = 0;
-      const uint32_t nc = cuts[k];
-      if (status[k] || !nc) continue;
-      const avr_slice_desc& d = descs[k];
-      const uint32_t base = (uint32_t)slots[k].first;
-      std::vector<const avr::SeamRec*> rp;
-      std::vector<SeamCe> ce(nc);
-      std::vector<uint32_t> plen;
-      // copies of the records: the caller's buffer and stride need not be aligned for a SeamRec
-      const size_t rb = avr::seam_rec_bytes(d.mb_width);
-      std::vector<uint64_t> copy((rb / 8 + 1) * nc);
-      for (uint32_t i = 0; i < nc; i++) {
-        uint64_t* raw = copy.data() + (rb / 8 + 1) * i;
-        memcpy(raw, recs + (size_t)(base + i) * rec_stride, rb);
-        const avr::SeamRec& r = *(const avr::SeamRec*)raw;
-        SeamCe& c = ce[i];
-        if (check_cuts) {
-          const uint64_t bitpos = 8ull * r.cd_next - r.cd_k;
-          if (r.cd_k >= 32 || 8ull * r.cd_next < r.cd_k ||
-              !seam_encoder(arena + d.payload_offset, d.payload_size, bitpos, r.cd_low >> r.cd_k, r.cd_range, &c) ||
-              c.q != r.q || c.low != r.ce_low || c.range != r.ce_range || c.outstanding != r.ce_outstanding ||
-              c.cache != r.ce_cache || c.queue != r.ce_queue) {
-            status[k] = AVR_SLICE_CODER;
-            break;
-          }
-        } else {
-          c = SeamCe{r.q, r.ce_low, r.ce_outstanding, r.ce_cache, r.ce_range, r.ce_queue};
-        }
-        rp.push_back((const avr::SeamRec*)raw);
-      }
-      if (status[k]) continue;
-      for (uint32_t i = 0; i <= nc; i++) plen.push_back(piece_end[base + i] - (i ? piece_end[base + i - 1] : 0u));
-      if (!seams_encode(rp, ce, d, plen, &field)) return AVR_ERR_OUT_OF_MEMORY;
-      if (field.size() > UINT32_MAX) return AVR_ERR_INVALID_ARGUMENT;
-      lens[k] = (uint32_t)field.size();
-      blob.insert(blob.end(), field.begin(), field.end());
+    std::vector<SliceSeams> ss;
+    if (int r = seams_build(descs, n, arena, arena_len, res, slots, cuts, piece_end, n_recs, recs, rec_stride,
+                            check_cuts != 0, 0, &ss))
+      return r;
+    size_t total = 0;
+    for (const SliceSeams& s : ss) {
+      if (s.field.size() > UINT32_MAX) return AVR_ERR_INVALID_ARGUMENT;
+      total += s.field.size();
     }
-    uint8_t* o = (uint8_t*)malloc(blob.size() ? blob.size() : 1);
+    uint8_t* o = (uint8_t*)malloc(total ? total : 1);
     if (!o) return AVR_ERR_OUT_OF_MEMORY;
-    if (!blob.empty()) memcpy(o, blob.data(), blob.size());
+    size_t at = 0;
+    for (int k = 0; k < n; k++) {
+      status[k] = ss[k].status;
+      offsets[k] = at;
+      lens[k] = (uint32_t)ss[k].field.size();
+      if (lens[k]) memcpy(o + at, ss[k].field.data(), lens[k]);
+      at += lens[k];
+    }
     *seams = o;
-    *seams_len = blob.size();
+    *seams_len = total;
     return AVR_OK;
   });
 }
 
 }  // extern "C"
+

@@ -90,6 +90,31 @@ def test_split_plan_of_an_empty_batch():
     assert (len(p.slots), p.n_recs, p.n_candidates, p.rec_stride) == (0, 0, 0, 64 + 1024 + 48)
 
 
+def test_no_walk_fills_its_slot_and_some_leave_one_record():
+    """Every split block of the oracle's P containers of both fixtures at split_bytes 512, 1024 and
+    2048 has cuts <= cap - 1 (cap from avr_split_plan on the parsed descriptors): the split walk is
+    offered cap - 1 records of a slot, so that the end of its last piece stays inside it.  Slices with
+    cuts == cap - 1, the case that offer decides, are among them at every one of the sizes (realshort:
+    3, 16 and 1 slices, e.g. slice 31 of 1002 bytes with one cut at 512; cockatoo: 69, 106 and 37).
+    realshort at 512 and 2048 and cockatoo at 512 and 2048 are cases of
+    test_gpu_split.py::test_fixture_split_matches_oracle, so the device's walk with cap - 1 records is
+    already held to the oracle's container there and no GPU case is added."""
+    full = {}
+    for name in ("realshort.mp4", "cockatoo.mp4"):
+        ps = avr.parse_stream((FIX / name).read_bytes())
+        for split_bytes in (512, 1024, 2048):
+            info, _ = avr.describe_container(_container(name, split_bytes))
+            blocks = [b for b in info["blocks"] if "literal" not in b]
+            assert len(blocks) == len(ps.descs)
+            slots = avr.split_plan(ps.descs, split_bytes).slots
+            cut = [(k, len(_seams(bytes.fromhex(b["seams"]))[2])) for k, b in enumerate(blocks) if "seams" in b]
+            assert cut
+            for k, cuts in cut:
+                assert 1 <= cuts <= int(slots[k]["cap"]) - 1, (name, split_bytes, k)
+            full[name, split_bytes] = sum(cuts == int(slots[k]["cap"]) - 1 for k, cuts in cut)
+    assert all(full.values()), full   # the GPU test's sizes among them
+
+
 @lru_cache(None)
 def _batch(name, split_bytes):
     """The oracle's split container of a fixture as the batch a split walk would have left: the
