@@ -142,7 +142,7 @@ int trace_slices(avr_hooks_session* hs, const std::vector<int>& which) {
     if (res[k].status != 0)
       return fail(c, AVR_ERR_FORMAT, "hooks: device trace of slice " + std::to_string(i) + " failed (" +
                                          std::to_string(res[k].status) + ")");
-    // split the records: bins (kinds 0-2) and map events (kind 3, avr_walker.h TRACE_EV_*)
+    // split the records: bins (kinds 0-2) and map events (kind 3, avr_slice_lds.h TRACE_EV_*)
     const uint8_t* t = traces.data() + plan.descs[k].out_offset;
     const size_t len = res[k].out_len;
     std::vector<uint8_t>& b = hs->bins[i];

@@ -1,6 +1,7 @@
 // parallel slice kernel, MODE_DECOMPRESS, the reference's arithmetic_code<uint64_t, uint8_t> coder (one
 // translation unit per kernel: see avr_walker.h).
-#include "avr_walker.h"
+#include "avr_prof.h"
+#include "avr_slice_kernels.h"
 
 namespace avr {
 
@@ -10,27 +11,9 @@ hipError_t launch_parallel_decompress(const EngineTables* T, const avr_slice_des
 }
 
 // AVR_PROFILE builds: read (and clear) this kernel's section cycle counters; zeros otherwise.
-hipError_t profile_parallel_decompress(unsigned long long* out16) {
-#if defined(AVR_PROFILE) || defined(AVR_WATCHDOG)
-  hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(avr_prof), sizeof(unsigned long long) * 64);
-  unsigned long long z[64] = {};
-  if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(avr_prof), z, sizeof(z));
-  return e;
-#else
-  for (int i = 0; i < 64; i++) out16[i] = 0;
-  return hipSuccess;
-#endif
-}
+hipError_t profile_parallel_decompress(unsigned long long* out16) { return read_clear_prof(AVR_PROF_SYM, out16); }
 
 // AVR_PROFILE builds: per-slice wave placement (see avr_place); zeros otherwise.
-hipError_t placement_parallel_decompress(uint32_t* out, int n) {
-  if (n > 4096) n = 4096;
-#ifdef AVR_PROFILE
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(avr_place), sizeof(uint32_t) * 8 * n);
-#else
-  for (int i = 0; i < 8 * n; i++) out[i] = 0;
-  return hipSuccess;
-#endif
-}
+hipError_t placement_parallel_decompress(uint32_t* out, int n) { return read_placement(AVR_PLACE_SYM, out, n); }
 
 }  // namespace avr

@@ -1,7 +1,7 @@
 // parallel slice kernel, MODE_DECOMPRESS, P32 coder: the parallel model's optional 32-bit container coder
 // (avr_engine.h PEncoder / PDecoder, tag avrecode-amd:P32; one translation unit per kernel, see
 // avr_walker.h).
-#include "avr_walker.h"
+#include "avr_slice_kernels.h"
 
 namespace avr {
 

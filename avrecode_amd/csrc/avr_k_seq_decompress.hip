@@ -1,5 +1,6 @@
 // sequential slice kernel, MODE_DECOMPRESS (one translation unit per kernel: see avr_walker.h).
-#include "avr_walker.h"
+#include "avr_prof.h"
+#include "avr_slice_kernels.h"
 
 namespace avr {
 
@@ -17,16 +18,6 @@ hipError_t launch_sequential_decompress(const EngineTables* T, const avr_slice_d
 }
 
 // AVR_PROFILE builds: read (and clear) this kernel's section cycle counters; zeros otherwise.
-hipError_t profile_sequential_decompress(unsigned long long* out16) {
-#if defined(AVR_PROFILE) || defined(AVR_WATCHDOG)
-  hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(avr_prof), sizeof(unsigned long long) * 64);
-  unsigned long long z[64] = {};
-  if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(avr_prof), z, sizeof(z));
-  return e;
-#else
-  for (int i = 0; i < 64; i++) out16[i] = 0;
-  return hipSuccess;
-#endif
-}
+hipError_t profile_sequential_decompress(unsigned long long* out16) { return read_clear_prof(AVR_PROF_SYM, out16); }
 
 }  // namespace avr

@@ -1,7 +1,7 @@
-// The long-slice split's kernels (avr_walker.h slices_split_kernel, avr_kernels.h SplitArgs): the
+// The long-slice split's kernels (avr_slice_kernels.h slices_split_kernel, avr_kernels.h SplitArgs): the
 // parallel model on arithmetic_code<uint64_t, uint8_t>, compress (whole slices, cut as they are
 // walked) and decompress (the pieces), in one translation unit with its own CU board.
-#include "avr_walker.h"
+#include "avr_slice_kernels.h"
 
 namespace avr {
 

@@ -12,7 +12,7 @@ namespace avr {
 struct EngineTables;
 
 // Per model instance (u16 units): the dense SIG + NZ estimator table (kEstTable entries), then
-// the write log that lets the next user clear only what was written (see avr_walker.h): a u32
+// the write log that lets the next user clear only what was written (see avr_slice_lds.h): a u32
 // count at kEstLogN (kEstLogOverflow: clear the whole table) and kEstLogCap u32 entry indices.
 constexpr int kEstTable = 294016;
 constexpr int kEstLogN = kEstTable;
@@ -136,7 +136,7 @@ hipError_t launch_rmode_estimators(const uint32_t* ops, uint64_t N, const uint64
 hipError_t launch_rcode(const EngineTables* T, const avr_slice_desc* descs, int n, const uint32_t* rops,
                         const uint64_t* op_off, const uint32_t* counts, uint8_t* out, avr_slice_result* res,
                         const int32_t* stop_ok, uint32_t flags, hipStream_t stream);
-// section cycle counters of AVR_PROFILE builds (avr_walker.h); zeros otherwise
+// section cycle counters of AVR_PROFILE builds (avr_prof.h); zeros otherwise
 hipError_t profile_parallel_compress(unsigned long long* out16);
 hipError_t placement_parallel_compress(uint32_t* out8n, int n);
 hipError_t placement_parallel_decompress(uint32_t* out8n, int n);

@@ -1,5 +1,5 @@
-// The per-slice walker shared by the slice kernels (included by the avr_k_*.hip translation
-// units only; each instantiates one kernel so the kernels compile in parallel).
+// The per-slice walker shared by the slice kernels (included through avr_slice_kernels.h by the
+// avr_k_*.hip units only; each instantiates one kernel so the kernels compile in parallel).
 //
 // One wavefront (64 lanes) owns one CABAC slice and runs the whole hot path for it:
 //   compress:    CABAC decode (fork ff_get_cabac*) -> H.264 slice_data() parse (the fork's
@@ -16,627 +16,15 @@
 // Model modes: RM = true reproduces recode.cpp exactly (estimators and frame metadata persist
 // across slices; one wavefront walks all slices in file order).  RM = false applies the same
 // model to each slice from a fresh state (independent slices, one wavefront per slice).
+//
+// This header: struct Walker (the parse, the model keys, the per-bin engines) and the walk of one
+// slice.  The other waves' bodies are in avr_coder.h, the kernels in avr_slice_kernels.h.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <type_traits>
 
-#include "../../include/avrecode.h"
-#include "avr_engine.h"
-#include "avr_kernels.h"
-
-#define AVR_FI __device__ __forceinline__
-
-// Cycle accounting per walker section, compiled in with -DAVR_PROFILE only (scripts/prof_sections):
-// 0 slice, 1 macroblock syntax, 2 residual, 3 map decode, 4 nnz bins, 5 map re-code, 6 levels,
-// 7 per-macroblock bookkeeping; [8 + i] bins coded in section i.  Summed over slices into avr_prof (one copy per TU).
-#ifdef AVR_PROFILE
-#define PROF_T() ((uint64_t)__builtin_readcyclecounter())
-#define PROF_BEGIN(v) const uint64_t v = PROF_T(); const uint32_t v##_b = bins
-#define PROF_BEGINW(v) const uint64_t v = PROF_T(); const uint32_t v##_b = w.bins
-#define PROF_END(i, v) prof[i] += PROF_T() - (v), profb[i] += bins - v##_b
-#define PROF_ENDW(i, v) w.prof[i] += PROF_T() - (v), w.profb[i] += w.bins - v##_b
-// macroblock-layer sub-sections (avr_prof[32 + i] cycles, [40 + i] bins): 0 macroblock start,
-// 1 mb_skip_flag, 2 mb_type + sub_mb_type, 3 intra prediction modes, 4 ref_idx, 5 mvd,
-// 6 coded_block_pattern + transform_size_8x8_flag + mb_qp_delta, 7 end_of_slice + publish
-#define SPROF_END(i, v) sprof[i] += PROF_T() - (v), sprofb[i] += bins - v##_b
-#define SPROF_ENDW(i, v) w.sprof[i] += PROF_T() - (v), w.sprofb[i] += w.bins - v##_b
-#else
-#define SPROF_END(i, v)
-#define SPROF_ENDW(i, v)
-#define PROF_BEGINW(v)
-#define PROF_ENDW(i, v)
-#define PROF_BEGIN(v)
-#define PROF_END(i, v)
-#endif
+#include "avr_slice_lds.h"
 
 namespace avr {
-
-#if defined(AVR_PROFILE) && defined(AVR_WATCHDOG)
-#error "AVR_WATCHDOG records share avr_prof with the AVR_PROFILE section counters: build one at a time"
-#endif
-#if defined(AVR_PROFILE) || defined(AVR_WATCHDOG)
-static __device__ unsigned long long avr_prof[64];
-#endif
-#ifdef AVR_PROFILE
-// wave placement per slice (AVR_PROFILE builds): HW_ID of waves 0..2, XCC_ID, walker start / end
-// (s_memtime low 32 bits), walker start / end (s_memrealtime, 100 MHz) -- scripts/placement.py
-constexpr int kPlaceSlices = 4096;
-static __device__ uint32_t avr_place[kPlaceSlices][8];
-AVR_FI void record_placement(int s, int wave) {
-  if (s < kPlaceSlices && __lane_id() == 0) {
-    avr_place[s][wave] = __builtin_amdgcn_s_getreg(4 | (31 << 11));        // HW_REG_HW_ID
-    if (wave == 0) avr_place[s][3] = __builtin_amdgcn_s_getreg(20 | (15 << 11));  // HW_REG_XCC_ID
-  }
-}
-#define AVR_PLACE(s, wave) record_placement(s, wave)
-#define AVR_PLACE_T(s, k) if ((s) < kPlaceSlices && __lane_id() == 0) { \
-    avr_place[s][4 + (k)] = (uint32_t)__builtin_readcyclecounter(); \
-    avr_place[s][6 + (k)] = (uint32_t)__builtin_amdgcn_s_memrealtime(); }
-#else
-#define AVR_PLACE(s, wave)
-#define AVR_PLACE_T(s, k)
-#endif
-
-// MODE_TRACE: the compress-side CABAC decode + parse alone, recording every bin in decode order
-// (2 bytes: bin | kind << 1, the context's state byte before the bin) -- the bin sequence the
-// libavcodec-hooks layer (avr_hook_*) serves to its caller -- and, between the bins, the model
-// events that decide the model keys (kind 3 records, TRACE_EV_*): where each significance map
-// begins and ends, with the model coordinates (mb_xy) and sub-macroblock (begin_sub_mb) it runs
-// under; the hooks layer checks the caller's begin/end_coding_type(SIG_MAP), mb_xy and
-// begin_sub_mb against them (recode.cpp:166-207, 951-974).
-enum { MODE_COMPRESS = 0, MODE_DECOMPRESS = 1, MODE_GENERATE = 2, MODE_TRACE = 3 };
-enum { F_DEC = 1, F_SKIP = 2, F_INTRA = 4, F_I16 = 8, F_D16 = 16, F_T8 = 32, F_CPRED = 64 };
-enum { SE_OTHER = 0, SE_REF, SE_QPDELTA, SE_MVD_SUFFIX, SE_LEVEL_SUFFIX, SE_EOS, SE_PCM };
-// MODE_TRACE event records: 0x06 (kind 3), type, payload.  MAP_BEGIN: mb_x, model row (u16 LE
-// each), cat, scan8 index, max_coeff, is_dc | chroma422 << 1 (10 bytes); MAP_END: 2 bytes.
-enum { TRACE_EV_MAP_BEGIN = 1, TRACE_EV_MAP_END = 2 };
-
-static __constant__ uint8_t c_scan8[51] = {
-  4 + 1 * 8,  5 + 1 * 8,  4 + 2 * 8,  5 + 2 * 8,  6 + 1 * 8,  7 + 1 * 8,  6 + 2 * 8,  7 + 2 * 8,
-  4 + 3 * 8,  5 + 3 * 8,  4 + 4 * 8,  5 + 4 * 8,  6 + 3 * 8,  7 + 3 * 8,  6 + 4 * 8,  7 + 4 * 8,
-  4 + 6 * 8,  5 + 6 * 8,  4 + 7 * 8,  5 + 7 * 8,  6 + 6 * 8,  7 + 6 * 8,  6 + 7 * 8,  7 + 7 * 8,
-  4 + 8 * 8,  5 + 8 * 8,  4 + 9 * 8,  5 + 9 * 8,  6 + 8 * 8,  7 + 8 * 8,  6 + 9 * 8,  7 + 9 * 8,
-  4 + 11 * 8, 5 + 11 * 8, 4 + 12 * 8, 5 + 12 * 8, 6 + 11 * 8, 7 + 11 * 8, 6 + 12 * 8, 7 + 12 * 8,
-  4 + 13 * 8, 5 + 13 * 8, 4 + 14 * 8, 5 + 14 * 8, 6 + 13 * 8, 7 + 13 * 8, 6 + 14 * 8, 7 + 14 * 8,
-  0 + 0 * 8,  0 + 5 * 8,  0 + 10 * 8,
-};
-static __constant__ uint8_t c_b_pairs[9][2] = {{1, 1}, {2, 2}, {1, 2}, {2, 1}, {1, 3}, {2, 3}, {3, 1}, {3, 2}, {3, 3}};
-constexpr int kSigEst = 229376;
-constexpr int kNzEst = 63 * 2 * 3 * 3 * 57;
-constexpr int kEstDefault = 1026;
-static_assert(kEstTable >= kSigEst + kNzEst, "estimator table size");
-
-struct MbRec {
-  uint8_t flags, is8x8;
-  uint16_t cbp;         // FFmpeg cbp_table layout: luma b0-3, chroma b4-5, chroma DC b6-7, luma DC b8-10
-  uint8_t nnz[3][16];   // coefficient count per 4x4, raster per plane
-  uint8_t mvd[2][16][2];
-  int8_t ref[2][4];
-  uint8_t direct8[4];
-  uint8_t mnnz[52];     // model BlockMeta.num_nonzeros[51]
-};
-// bottom edge of the macroblock above, dword j gathered from MbRec dword Walker::edge_src (lane j)
-// at the publish; 92 B keeps four 1080p workgroups within a CU's LDS
-struct EdgeRec {
-  uint8_t flags, pad;
-  uint16_t cbp;
-  uint8_t nnz[3][4];    // bottom row of each plane
-  uint8_t mvd[2][4][2]; // bottom row
-  int8_t ref[2][2];     // bottom two 8x8 of each list
-  uint8_t direct8[2], pad2[2];
-  uint8_t mnnz[52];
-};
-static_assert(sizeof(EdgeRec) == 92, "EdgeRec layout");
-// The progressive walkers' ring holds EdgeRec's first ten dwords only (the parse's neighbour
-// fields); the model bytes of each column (EdgeRec::mnnz, read by the NZ-tree keys of the parallel
-// model) live in a row of their own, `mring`: in LDS after the ring, or -- when that is what lets
-// four wide workgroups share a CU's LDS (4K: 240 columns x 92 B would leave room for three) -- in
-// the workgroup's global scratch (kFlagMringGlobal).  Only the upper macroblock's bottom-row
-// blocks and DC entries are ever read there (get_neighbor_sub_mb's upper neighbours: mnnz bytes
-// 8-15, 24-31, 40-50, i.e. dwords 2, 3, 6, 7, 10, 11, 12 -- tests/test_oracle_geometry.py checks
-// the table), so a column keeps those 7 dwords, dword d at ((d >> 2) << 1) | (d & 1): 28 B instead
-// of 52 (round 6: the 4K stream's model-row write-backs were most of its HBM writes).
-struct EdgeCore {
-  uint8_t flags, pad;
-  uint16_t cbp;
-  uint8_t nnz[3][4];
-  uint8_t mvd[2][4][2];
-  int8_t ref[2][2];
-  uint8_t direct8[2], pad2[2];
-};
-static_assert(sizeof(EdgeCore) == 40 && offsetof(EdgeRec, mnnz) == 40, "EdgeCore = EdgeRec's first ten dwords");
-constexpr int kMringDwords = 7;      // per column: the read dwords of EdgeRec::mnnz
-constexpr uint32_t kEdgeMringNz = 0x200u;   // EdgeCore dword 0: the column's model row was stored (global row)
-constexpr uint32_t kMringUsed = 0x1CCCu;   // those dwords (2, 3, 6, 7, 10, 11, 12) of the 13
-AVR_FI uint32_t mring_dword(uint32_t d) { return (d >> 2) << 1 | (d & 1); }
-static_assert(sizeof(MbRec) == 180, "MbRec layout (dword map in Walker::edge_src)");
-
-// LDS layout (per workgroup = one slice); the ring is sized by mb_width at launch.
-// SIG + NZ estimators: an LDS hash table (4096 slots, 16 KB) in front of the dense per-model
-// table in HBM (kEstTable u16 entries).  A slice touches ~3.5-5.5 K distinct SIG/NZ keys out of
-// 294 K, so the first ones seen get an LDS slot for the rest of the model's life and only the
-// keys that find their probe window full live in HBM (0.4 % of lookups at QP 22, none at QP 30,
-// vs ~11 % misses for the direct-mapped write-back cache this replaces).  Keys never leave the
-// table, so "not in the window and the window has a free slot" means "never seen": a new key
-// starts at the default estimator without any HBM access.
-//   key p = idx * kEstKeyMul mod 2^19 (a bijection), home slot p >> 7, tag p & 127; one probe is
-//   one LDS read per lane over the 64 slots home .. home + 63; slot = (0x8000 | disp << 7 | tag)
-//   << 16 | estimator, 0 = free.
-// The HBM table is cleared lazily and sparsely: an entry stored there carries bit 15 (estimators
-// use 15 bits: neg - 1 <= 0x60), so its first store is recognised and its index appended to the
-// table's write log; the next model using the table zeroes the logged entries (the whole table
-// only if the log overflowed) instead of clearing 588 KB per slice.
-constexpr int kEtabBits = 12;
-constexpr int kEtabSize = 1 << kEtabBits;
-constexpr uint32_t kEstKeyMul = 0x4F1BBu;   // odd: multiplication mod 2^19 is a bijection
-constexpr uint32_t kEstWritten = 0x8000u;
-static_assert(kEstTable < (1 << 19), "estimator key space");
-
-// Producer -> consumer ring of coding operations (see "Two waves per slice" below).
-constexpr int kFifo = 512;
-
-struct Shared {
-  HotTables tab;          // copy of EngineTables::hot (per-bin lookups stay in LDS)
-  uint32_t fifo[2][kFifo];   // [0] walker -> next wave, [1] modeler -> coder (compress only)
-  uint32_t fifo_head[2];     // operations published by the ring's producer (monotonic)
-  uint32_t fifo_tail[2];     // operations retired by the ring's consumer (monotonic)
-  int32_t p_status, p_stop_ok, c_err;  // slice results of the two waves
-  uint32_t elog_n;           // entries appended to the HBM table's write log by this model
-  uint32_t prio;             // the slice's current wave priority (walker -> modeler / coder)
-  uint32_t qnext;            // persistent launches: the queue entry this workgroup drew
-#if defined(AVR_QUEUE_EAGER) && AVR_QUEUE_EAGER == 1
-  uint32_t qcell;            // experiment build: the walker's board cell, set before the first draw
-#endif
-#ifdef AVR_WATCHDOG
-  uint32_t wd_epoch[4];      // watchdog build: barrier checkpoints passed, per wave
-#endif
-  uint32_t c_len, c_last;
-  uint32_t bill[6];          // the coder's h264_model billing by CodingType (kFlagBill launches)
-  uint32_t blk[64];       // residual blocks of the current macroblock (packed, see push_block)
-  uint8_t state[1024];
-  uint16_t est[kEstDefault + 2];
-  uint8_t in_stage[kStage];
-  MbRec cur, left;
-  union {
-    uint32_t etab[kEtabSize + 64]; // compress/decompress: LDS hash table of the SIG + NZ estimators
-                                   //   (home slots 0 .. kEtabSize - 1, probe windows do not wrap)
-    uint16_t gen_p[1024];          // generator: P(bin = 1) in 1/65536 per context
-  };
-};
-
-// ---------------------------------------------------------------------------------------
-// Several waves per slice.  The hot path is a chain of serial recurrences that only meet in the
-// bin value, so each runs on its own wave and they overlap on the SIMD instead of adding up:
-//   compress:   walker (CABAC decode + slice_data parse + model keys)  --ring 0-->
-//               modeler (estimator lookup/update, recode.cpp:816-820, 1030-1047)  --ring 1-->
-//               coder (arithmetic_code<uint64_t,uint8_t> encoder, recode.cpp:1074, 1092-1094)
-//   decompress: walker (recoded decode + model + parse: the parse needs each bin at once)
-//               --ring 0--> coder (cabac::encoder, cabac_code.h:33-67)
-// Consumers retire a ring in batches of up to 64 ops (one entry per lane, plus whatever table
-// record that lane can gather), then run their serial chain over the batch from registers.
-//
-// ring 0, compress (model ops): bit 0 bin, bit 1 SIG/NZ estimator (else per-context), bit 2
-//   significance-map threshold 0x50 (else 0x60), bits 3-21 estimator index.
-// ring 1, compress (coder ops): bit 0 bin, bits 1-7 pos, bits 8-14 pos+neg of the estimator
-//   before its update.
-// ring 0, decompress: bit 0 bin, bits 1-2 kind (0 decision, 1 bypass, 2 terminate), bits 3-12
-//   ctxIdx.
-// Billing classes (h264_model::coding_type at the put, recode.cpp:615-661): compress coder ops
-//   carry it in bits 15-16 (0 UNKNOWN, 1 SIGNIFICANCE_MAP, 2 SIGNIFICANCE_NZ), decompress walker
-//   ops in bits 13-14 (0 UNKNOWN, 1 SIGNIFICANCE_MAP, 2 SIGNIFICANCE_EOB).
-// OP_FINISH = arithmetic_code::encoder::finish (terminate = 1); OP_END closes a slice's stream.
-enum { PIPC_UNKNOWN = 0, PIPC_UNREACHABLE, PIPC_SIG_MAP, PIPC_SIG_EOB, PIPC_SIG_NZ, PIPC_RESIDUALS };
-constexpr uint32_t OPC_SHIFT_C = 15, OPC_SHIFT_D = 13;
-__host__ __device__ inline int op_class_pip_c(uint32_t c) { return c == 1 ? PIPC_SIG_MAP : c == 2 ? PIPC_SIG_NZ : PIPC_UNKNOWN; }
-__host__ __device__ inline int op_class_pip_d(uint32_t c) { return c == 1 ? PIPC_SIG_MAP : c == 2 ? PIPC_SIG_EOB : PIPC_UNKNOWN; }
-constexpr uint32_t OP_FINISH = 1u << 30;
-constexpr uint32_t OP_END = 1u << 31;
-// compress rings of the long-slice split (SPL): with OP_FINISH at a cut -- the modeler starts a fresh
-// model after it, the coder a fresh stream (bit 29: no model or coder op reaches it)
-constexpr uint32_t OP_RESTART = 1u << 29;
-enum { OPK_DECISION = 0, OPK_BYPASS = 1, OPK_TERMINATE = 2, OPK_MACRO = 3 };
-
-constexpr uint32_t OPM_CACHE = 2, OPM_THR50 = 4;
-AVR_FI uint32_t op_model(int bin, uint32_t flags, uint32_t idx) { return (uint32_t)bin | flags | idx << 3; }
-AVR_FI uint32_t op_recode(int bin, uint32_t est) {
-  const uint32_t pos = (est & 0xff) + 1, tot = pos + (est >> 8) + 1;
-  return (uint32_t)bin | pos << 1 | tot << 8;
-}
-// Decompress macro ops (kind OPK_MACRO, progressive walkers): the coder expands them into the bins
-// and contexts the walker would have sent one by one.  Bits 3-4 select the op:
-//   0 map segment: ctxBlockCat bits 5-8, positions coded in this 16-position segment - 1 bits 9-12,
-//     bit 13 = the map ended on a last_significant_coeff_flag of 1 at its highest significant
-//     position (else: a full segment, or the map ran to max - 1), bits 14-29 the
-//     significant_coeff_flag of each position.  The coder tracks the segment's first position; a
-//     map's last segment resets it and the level counters (gt1 / eq1 of residual_block_cabac);
-//   1 level: ctxBlockCat bits 5-8, sign bit 9, min(coeff_abs_level_minus1 + 1, 15) bits 10-13 (15:
-//     the prefix only; the escape's suffix and the sign follow as bypass ops);
-//   2 mvd component: vertical bit 5 (ctxIdxOffset 47, else 40), ctxIdxInc of the first bin bits 6-7,
-//     sign bit 8, min(|mvd|, 9) bits 9-12 (9: the prefix only; the UEG3 suffix and the sign follow
-//     as bypass ops).
-AVR_FI uint32_t op_map(int cat, int npos, int ended, uint32_t mask) {
-  return OPK_MACRO << 1 | (uint32_t)cat << 5 | (uint32_t)(npos - 1) << 9 | (uint32_t)ended << 13 | mask << 14;
-}
-AVR_FI uint32_t op_level(int cat, int absl, int sign) {
-  return OPK_MACRO << 1 | 1u << 3 | (uint32_t)cat << 5 | (uint32_t)sign << 9 | (uint32_t)absl << 10;
-}
-AVR_FI uint32_t op_mvd(int comp, int inc, int amvd, int sign) {
-  return OPK_MACRO << 1 | 2u << 3 | (uint32_t)comp << 5 | (uint32_t)inc << 6 | (uint32_t)sign << 8 | (uint32_t)amvd << 9;
-}
-// Watchdog build (-DAVR_WATCHDOG, diagnostics only): every wait of a slice workgroup is bounded in
-// time, and the kernels check their own invariants.  A wait that lasts kWdTicks records where it
-// was (site, workgroup, wave, the counters it waited on, the queue entry, HW_ID) in avr_prof and
-// ends its wave, so a workgroup that would hang drains instead and the host reads the records
-// (avr_debug_profile).  Layout of avr_prof: [0] records written, [1 + 3 i .. 3 + 3 i] record i
-// (i < 16), [50] invariant violations, [51..53] the first one's record.  Sites: 1-4 ring waits
-// (push, push_v, take, modeler -> coder room); 10 board cell out of range; 11 ring overfilled;
-// 12 queue entries drawn out of order; 13 waves of a workgroup at different barriers.
-enum { WD_PUSH = 1, WD_PUSHV = 2, WD_TAKE = 3, WD_ROOM1 = 4, WD_CELL = 10, WD_RING = 11, WD_QORDER = 12,
-       WD_EPOCH = 13 };
-#ifdef AVR_WATCHDOG
-constexpr uint64_t kWdTicks = 300000000ull;   // s_memrealtime runs at 100 MHz: 3 s
-AVR_FI void wd_put(unsigned long long* rec, uint32_t site, uint32_t a, uint32_t b, uint32_t k) {
-  rec[0] = (unsigned long long)site << 48 | (unsigned long long)(threadIdx.x >> 6) << 40 | blockIdx.x;
-  rec[1] = (unsigned long long)a << 32 | b;
-  rec[2] = (unsigned long long)k << 32 | __builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_REG_HW_ID
-}
-AVR_FI void wd_violation(uint32_t site, uint32_t a, uint32_t b, uint32_t k) {
-  if (__lane_id() != 0) return;
-  if (atomicAdd(&avr_prof[50], 1ull) == 0) wd_put(&avr_prof[51], site, a, b, k);
-  __threadfence();
-}
-// One poll of a wait that started at *t0 (0: not yet): past kWdTicks, record and end the wave.
-AVR_FI void wd_poll(uint64_t* t0, uint32_t site, uint32_t a, uint32_t b, uint32_t k) {
-  const uint64_t t = __builtin_amdgcn_s_memrealtime();
-  if (*t0 == 0) { *t0 = t; return; }
-  if (t - *t0 < kWdTicks) return;
-  if (__lane_id() == 0) {
-    const unsigned long long i = atomicAdd(&avr_prof[0], 1ull);
-    if (i < 16) wd_put(&avr_prof[1 + 3 * i], site, a, b, k);
-    __threadfence();
-  }
-  __builtin_amdgcn_endpgm();
-}
-#define WD_T0 uint64_t wd_t0 = 0
-#define WD_POLL(site, a, b, k) wd_poll(&wd_t0, site, a, b, k)
-#define WD_CHECK(cond, site, a, b, k) do { if (!(cond)) wd_violation(site, a, b, k); } while (0)
-#else
-#define WD_T0
-#define WD_POLL(site, a, b, k)
-#define WD_CHECK(cond, site, a, b, k)
-#endif
-
-// Queue trace build (-DAVR_QTRACE, diagnostics only): each workgroup of a persistent launch writes
-// its progress to host-mapped coherent memory (avr_debug_qtrace, compress kernel only), so the
-// host can read where every workgroup and wave is while a launch has not returned.  Per
-// workgroup 8 u32: [0..2] wave w's (slices drawn << 8 | phase), [3] the queue entry drawn, [4]
-// the walker's macroblocks of the current slice.  Phases: 1 drawn, 2 estimator table reset,
-// 3 slice state set up, 4 the wave's role done, 5 slice finished, 6 left the loop.
-// -DAVR_QTRACE=1 records only the queue entries drawn and the exit (the least perturbation),
-// -DAVR_QTRACE=2 every phase and the walker's macroblocks too.
-#ifdef AVR_QTRACE
-static __device__ uint32_t* avr_qtrace;
-AVR_FI void qtrace(uint32_t slot, uint32_t v) {
-  uint32_t* t = avr_qtrace;
-  if (t && __lane_id() == 0) __hip_atomic_store(&t[blockIdx.x * 8 + slot], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-#define QTRACE1(slot, v) qtrace(slot, v)
-#if AVR_QTRACE >= 2
-#define QTRACE(slot, v) qtrace(slot, v)
-#else
-#define QTRACE(slot, v)
-#endif
-#else
-#define QTRACE1(slot, v)
-#define QTRACE(slot, v)
-#endif
-
-// Ring counters: plain LDS accesses.  LDS is one memory per CU and executes each wave's accesses
-// in program order, so a counter store issued after the entry stores cannot be seen before them;
-// the asm statements only keep the compiler from reordering (an acquire/release fence would
-// also wait for, or write back, this wave's outstanding global stores).
-// The casts to address space 3 matter: a volatile access through a generic pointer stays a
-// flat access with cache-bypass bits and a vmcnt(0) wait (the address-space inference pass does
-// not rewrite volatile accesses), which costs a global-memory round trip per counter update.
-typedef __attribute__((address_space(3))) volatile uint32_t lds_vu32;
-AVR_FI uint32_t ld_volatile(const uint32_t* p) {
-  const uint32_t v = *(lds_vu32*)p;
-  asm volatile("" ::: "memory");
-  return __builtin_amdgcn_readfirstlane(v);
-}
-AVR_FI void st_volatile(uint32_t* p, uint32_t v) {
-  asm volatile("" ::: "memory");
-  *(lds_vu32*)p = v;
-}
-// LDS hand-offs between the lanes of ONE wave need no barrier (a wave's LDS operations execute in
-// order); only the compiler must not move memory operations across the hand-off.
-AVR_FI void wave_sync() {
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// Wave priority (s_setprio): the SQ issues from higher-priority waves first, then the oldest.
-// A batch's time is its longest slice's, and the slices sharing a CU compete for the issue slots,
-// so every wave of a slice runs at a priority that grows with the slice's remaining input
-// (longest-remaining-first); the walker sets it once per macroblock and publishes it in LDS,
-// the modeler and coder follow it once per ring batch.
-AVR_FI void set_prio(uint32_t p) {
-  switch (p) {
-    case 0: __builtin_amdgcn_s_setprio(0); break;
-    case 1: __builtin_amdgcn_s_setprio(1); break;
-    case 2: __builtin_amdgcn_s_setprio(2); break;
-    default: __builtin_amdgcn_s_setprio(3); break;
-  }
-}
-// The slices that share a CU (up to 4 resident workgroups) rank themselves by remaining input on
-// a per-CU board in global memory (one copy per kernel): each walker registers a cell of its CU
-// (HW_ID / XCC_ID registers), posts its remaining bytes there once per macroblock and takes
-// priority 3 - (number of CU neighbours with more input left), so the CU's issue slots go to the
-// longest remaining slice first and the co-resident slices tend to finish together.  The board
-// is shared by waves of one CU only, so workgroup-scope accesses (through the CU's own vector
-// cache and the XCD's L2) suffice; agent scope would send every post to memory.  A stale read
-// only delays a priority change.
-constexpr int kCuIds = 2048;   // XCC (3 bits) x SE (3) x SH (1) x CU (4)
-static __device__ uint32_t avr_cu_count[kCuIds];
-static __device__ uint32_t avr_cu_rem[kCuIds * 4];
-AVR_FI uint32_t cu_cell() {
-  const uint32_t hw = __builtin_amdgcn_s_getreg(4 | (31 << 11));    // HW_REG_HW_ID
-  const uint32_t xcc = __builtin_amdgcn_s_getreg(20 | (15 << 11));  // HW_REG_XCC_ID
-  const uint32_t cu = (((xcc & 7) * 8 + ((hw >> 13) & 7)) * 2 + ((hw >> 12) & 1)) * 16 + ((hw >> 8) & 15);
-  uint32_t slot = 0;
-  if (__lane_id() == 0) slot = atomicAdd(&avr_cu_count[cu], 1u);
-  return cu * 4 + (__builtin_amdgcn_readfirstlane(slot) & 3);
-}
-// Host side: zero this translation unit's board before a launch (stream-ordered).
-static inline hipError_t reset_cu_board(hipStream_t stream) {
-  void *cnt = nullptr, *rem = nullptr;
-  hipError_t e = hipGetSymbolAddress(&cnt, HIP_SYMBOL(avr_cu_count));
-  if (e == hipSuccess) e = hipGetSymbolAddress(&rem, HIP_SYMBOL(avr_cu_rem));
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(avr_cu_count), stream);
-  if (e == hipSuccess) e = hipMemsetAsync(rem, 0, sizeof(avr_cu_rem), stream);
-  return e;
-}
-constexpr uint32_t kNoCell = 0xffffffffu;   // Walker::prio_cell not assigned yet
-AVR_FI void cu_post(uint32_t cell, uint32_t rem) {
-  if (__lane_id() == 0) __hip_atomic_store(&avr_cu_rem[cell], rem, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-AVR_FI uint32_t cu_rank_prio(uint32_t cell, uint32_t rem) {
-  const uint32_t lane = __lane_id(), me = cell & 3;
-  uint32_t v = 0;
-  if (lane < 4) v = __hip_atomic_load(&avr_cu_rem[(cell & ~3u) + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  const uint64_t ahead = __ballot(lane < 4 && lane != me && (v > rem || (v == rem && lane < me)));
-  return 3u - (uint32_t)__builtin_popcountll(ahead);
-}
-
-AVR_FI void follow_prio(Shared* sh, uint32_t* cur) {
-  const uint32_t p = __builtin_amdgcn_readfirstlane(*(volatile __attribute__((address_space(3))) uint32_t*)&sh->prio);
-  if (p != *cur) {
-    *cur = p;
-    set_prio(p);
-  }
-}
-
-AVR_FI uint64_t readlane64(uint64_t v, uint32_t j) {
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, j);
-  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), j);
-  return (uint64_t)hi << 32 | lo;
-}
-
-// v_writelane_b32 (clang has no builtin for it; the LLVM intrinsic by its name)
-extern "C" __device__ int avr_llvm_writelane(int src, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
-
-// Producer end of ring r: entries go to LDS at once, the head counter every 32 entries (and on
-// demand), the tail is re-read only when the ring looks full.
-template <bool STAGED>
-struct RingOutT {
-  Shared* sh;
-  int r;
-  uint32_t head, room;
-  AVR_FI void init(Shared* s, int ring) {
-    sh = s;
-    r = ring;
-    head = 0;
-    room = kFifo;
-    stage_v = 0;
-    stage_n = 0;
-  }
-  AVR_FI void publish() {
-    flush();
-    st_volatile(&sh->fifo_head[r], head);
-  }
-#ifdef AVR_PROFILE
-  uint64_t wait_cycles = 0;
-#endif
-  // STAGED: single ops are staged in a VGPR (lane k = k-th op) and stored 64 at a time (fewer
-  // instructions per op on the producer; measured 1 % faster for the decompress walker, 2 %
-  // slower for the compress walker, whose consumer then waits in bursts)
-  uint32_t stage_v, stage_n;
-  AVR_FI void flush() {
-    if (STAGED && stage_n) {
-      const uint32_t k = stage_n;
-      stage_n = 0;
-      push_v_raw(stage_v, k);
-    }
-  }
-  AVR_FI void push_v(uint32_t op_v, uint32_t n) {
-    flush();
-    push_v_raw(op_v, n);
-  }
-  // a staged run of ops on either ring kind (stage, then flush_stage before any other push)
-  AVR_FI void stage(uint32_t op) {
-    stage_v = __lane_id() == stage_n ? op : stage_v;
-    if (++stage_n == 64) flush_stage();
-  }
-  AVR_FI void flush_stage() {
-    if (stage_n) {
-      const uint32_t k = stage_n;
-      stage_n = 0;
-      push_v_raw(stage_v, k);
-    }
-  }
-  AVR_FI void push(uint32_t op) {
-    if (STAGED) {
-#ifdef AVR_WL_PUSH
-      stage_v = (uint32_t)avr_llvm_writelane((int)op, (int)stage_n, (int)stage_v);
-#else
-      stage_v = __lane_id() == stage_n ? op : stage_v;
-#endif
-      if (++stage_n == 64) flush();
-      return;
-    }
-    if (room == 0) {
-      st_volatile(&sh->fifo_head[r], head);
-#ifdef AVR_PROFILE
-      const uint64_t tw = PROF_T();
-#endif
-      WD_T0;
-      for (;;) {
-        const uint32_t used = head - ld_volatile(&sh->fifo_tail[r]);
-        WD_CHECK(used <= (uint32_t)kFifo, WD_RING, head, used, (uint32_t)r);
-        if (used < (uint32_t)kFifo) { room = kFifo - used; break; }
-        WD_POLL(WD_PUSH, head, used, sh->qnext);
-        __builtin_amdgcn_s_sleep(1);
-      }
-#ifdef AVR_PROFILE
-      wait_cycles += PROF_T() - tw;
-#endif
-    }
-    sh->fifo[r][head & (kFifo - 1)] = op;
-    head++;
-    room--;
-    if ((head & 31) == 0) st_volatile(&sh->fifo_head[r], head);
-  }
-  // n <= 64 ops at once, op k in lane k (one vector store)
-  AVR_FI void push_v_raw(uint32_t op_v, uint32_t n) {
-    if (room < n) {
-      st_volatile(&sh->fifo_head[r], head);
-#ifdef AVR_PROFILE
-      const uint64_t tw = PROF_T();
-#endif
-      WD_T0;
-      for (;;) {
-        const uint32_t used = head - ld_volatile(&sh->fifo_tail[r]);
-        WD_CHECK(used <= (uint32_t)kFifo, WD_RING, head, used, (uint32_t)r);
-        if (used + n <= (uint32_t)kFifo) { room = kFifo - used; break; }
-        WD_POLL(WD_PUSHV, head, used, sh->qnext);
-        __builtin_amdgcn_s_sleep(1);
-      }
-#ifdef AVR_PROFILE
-      wait_cycles += PROF_T() - tw;
-#endif
-    }
-    if (__lane_id() < n) sh->fifo[r][(head + __lane_id()) & (kFifo - 1)] = op_v;
-    const uint32_t h0 = head;
-    head += n;
-    room -= n;
-    if ((h0 ^ head) & ~31u) st_volatile(&sh->fifo_head[r], head);
-  }
-};
-// Consumer end: wait for a batch, load it one entry per lane.  Returns the batch size.
-AVR_FI uint32_t ring_take(Shared* sh, int r, uint32_t tail, uint32_t* op_v, uint64_t* waited) {
-  uint32_t head;
-#ifdef AVR_PROFILE
-  const uint64_t tw = PROF_T();
-#endif
-  WD_T0;
-  for (;;) {
-    head = ld_volatile(&sh->fifo_head[r]);
-    if (head != tail) break;
-    WD_POLL(WD_TAKE, head, tail, sh->qnext);
-    __builtin_amdgcn_s_sleep(1);
-  }
-  WD_CHECK(head - tail <= (uint32_t)kFifo, WD_RING, head, tail, (uint32_t)r | 0x100u);
-#ifdef AVR_PROFILE
-  *waited += PROF_T() - tw;
-#endif
-  const uint32_t n = min(head - tail, 64u);
-  const uint32_t lane = __lane_id();
-  *op_v = lane < n ? sh->fifo[r][(tail + lane) & (kFifo - 1)] : 0u;
-  return n;
-}
-AVR_FI void ring_retire(Shared* sh, int r, uint32_t tail) { st_volatile(&sh->fifo_tail[r], tail); }
-
-// SIG / NZ estimators: probe the LDS hash table (see kEtabBits).  Returns the estimator and in
-// *slot where est_store writes it back (0: the HBM table).  Called by a whole wave.
-AVR_FI uint32_t est_load(Shared* sh, const uint16_t* est_g, uint32_t idx, uint32_t* slot, bool claim = false) {
-  const uint32_t p = (idx * kEstKeyMul) & ((1u << 19) - 1);
-  const uint32_t home = p >> 7, tag = p & 127;
-  const uint32_t lane = __lane_id();
-  const uint32_t ent = sh->etab[home + lane];
-  const uint64_t hit = __ballot((ent >> 16) == (0x8000u | lane << 7 | tag));
-#ifdef AVR_PROFILE_EST   // with AVR_PROFILE: estimator lookups that go to HBM (scripts/diag_est.py)
-  if (lane == 0) atomicAdd(&avr_prof[22], 1ull);
-  if (lane == 0 && !hit && !__ballot(ent == 0)) atomicAdd(&avr_prof[23], 1ull);
-#endif
-  if (hit) {
-    // the entry's upper half is the slot's tag word already
-    const uint32_t j = (uint32_t)__builtin_ctzll(hit);
-    const uint32_t ej = __builtin_amdgcn_readlane(ent, j);
-    *slot = (ej & 0xffff0000u) | (home + j);
-    return ej & 0xffff;
-  }
-  const uint64_t free_v = __ballot(ent == 0);
-  if (free_v) {
-    const uint32_t j = (uint32_t)__builtin_ctzll(free_v);
-    *slot = (0x8000u | j << 7 | tag) << 16 | (home + j);
-    // a caller that defers its store claims the slot now (a later key of the window must not take it)
-    if (claim && lane == j) sh->etab[home + j] = *slot & 0xffff0000u;
-    return 0;
-  }
-  // HBM: slot 1 marks the entry's first store (to be logged), 0 a stored one
-  const uint32_t raw = __builtin_amdgcn_readfirstlane(est_g[idx]);
-  *slot = __builtin_amdgcn_readfirstlane((raw >> 15 & 1u) ^ 1u);   // a scalar, like the LDS slots
-  return raw & (kEstWritten - 1);
-}
-AVR_FI void est_store(Shared* sh, uint16_t* est_g, uint32_t idx, uint32_t slot, uint32_t e) {
-  if (slot >> 31) {
-    sh->etab[slot & 0xffff] = (slot & 0xffff0000u) | e;
-  } else if (__lane_id() == 0) {
-    est_g[idx] = (uint16_t)(e | kEstWritten);
-    if (slot) {
-      const uint32_t n = sh->elog_n;
-      sh->elog_n = n + 1;
-      uint32_t* lg = (uint32_t*)(est_g + kEstLog);
-      if (n < (uint32_t)kEstLogCap) lg[n] = idx;
-      *(uint32_t*)(est_g + kEstLogN) = n < (uint32_t)kEstLogCap ? n + 1 : kEstLogOverflow;
-    }
-  }
-}
-// Lane-parallel lookup of each lane's key in the first four slots of its window: true (with the
-// estimator and its slot) when found there.  A key found stays where it is, so a hit is final;
-// a miss (new key, deeper or HBM-resident one) goes through est_load.
-AVR_FI bool est_probe4(const Shared* sh, uint32_t idx, uint32_t* e, uint32_t* slot) {
-  const uint32_t p = (idx * kEstKeyMul) & ((1u << 19) - 1);
-  const uint32_t home = p >> 7, t0 = 0x8000u | (p & 127);
-  const uint32_t s0 = sh->etab[home], s1 = sh->etab[home + 1], s2 = sh->etab[home + 2], s3 = sh->etab[home + 3];
-  // branch-free (selects): callers run it on every lane
-  const bool h0 = (s0 >> 16) == t0, h1 = (s1 >> 16) == (t0 | 1u << 7);
-  const bool h2 = (s2 >> 16) == (t0 | 2u << 7), h3 = (s3 >> 16) == (t0 | 3u << 7);
-  const uint32_t d = h0 ? 0u : h1 ? 1u : h2 ? 2u : 3u;
-  *e = (h0 ? s0 : h1 ? s1 : h2 ? s2 : s3) & 0xffff;
-  *slot = (t0 | d << 7) << 16 | (home + d);
-  return h0 | h1 | h2 | h3;
-}
-
-// A fresh model on a table the last model may have written: zero the logged entries (or the
-// whole table), reset the log.  Called by the whole workgroup; ends with a barrier.
-AVR_FI void est_table_reset(uint16_t* est_g, Shared* sh) {
-  const uint32_t n = *(volatile uint32_t*)(est_g + kEstLogN);
-  __syncthreads();   // every thread has read the count before it is reset
-  if (n == kEstLogOverflow) {
-    uint4* e4 = (uint4*)est_g;
-    for (int i = threadIdx.x; i < kEstTable / 8; i += blockDim.x) e4[i] = make_uint4(0, 0, 0, 0);
-  } else if (n) {
-    const uint32_t* lg = (const uint32_t*)(est_g + kEstLog);
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) est_g[lg[i]] = 0;
-  }
-  if (threadIdx.x == 0) {
-    *(uint32_t*)(est_g + kEstLogN) = 0;
-    sh->elog_n = 0;
-  }
-  __syncthreads();
-}
 
 // FLD: field-coded slices (PAFF, MBAFF) -- a second instantiation (kernels of their own, launched
 // only when a batch may hold such slices: kFlagFields), so that the progressive walker carries no
@@ -774,9 +162,7 @@ struct Walker {
     if constexpr (MODE == MODE_COMPRESS) {
       push(OP_FINISH | OP_RESTART);
       publish();
-      WD_T0;
       while (ld_volatile(&sh->fifo_tail[0]) != ring0.head) {
-        WD_POLL(WD_TAKE, ring0.head, 0, sh->qnext);
         __builtin_amdgcn_s_sleep(1);
       }
       for (uint32_t i = lane; i < (uint32_t)W * kMringDwords; i += 64) mring[i] = 0;
@@ -948,14 +334,9 @@ struct Walker {
   }
   // One decision of the model's coder with estimator e (recode.cpp:1435-1449).
   AVR_FI int rdec(uint32_t e) { return rd_get(rd, in, p1(e)); }
-  // CABAC state record of state byte s: VGPR table (two v_readlane) or, with AVR_CABAC_SMEM, a
-  // scalar load
+  // CABAC state record of state byte s: VGPR table (two v_readlane)
   AVR_FI CabacRec crec(uint32_t s) const {
-#ifdef AVR_CABAC_SMEM
-    return rec_of(((cu64*)G->hot.cabac)[s]);
-#else
     return vtab_rec(vt, s);
-#endif
   }
   AVR_FI void publish() {
     if (RM && gmode) return;
@@ -2373,7 +1754,6 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
     if (MODE == MODE_COMPRESS || MODE == MODE_DECOMPRESS) {
       w.publish();
       if (!RM) w.update_prio();
-      QTRACE(4, (uint32_t)w.mbs_done);
     }
     // MBAFF: end_of_slice_flag follows the bottom macroblock of a pair only (7.3.4)
     const int eos = (!(FLD && w.mbaff) || (w.pst & Walker<MODE, RM, FLD, P32, SPL>::PST_BOT)) ? w.terminate(SE_EOS) : 0;
@@ -2524,891 +1904,6 @@ AVR_FI void walker_slice(Walker<MODE, RM, FLD, P32, SPL>& w, const avr_slice_des
     res->bins = w.bins;
     res->mbs = (uint32_t)w.mbs_done;
   }
-}
-
-AVR_FI uint32_t vgpr_zero() {
-  uint32_t z;
-  asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-  return z;
-}
-// The modeler wave (compress): the estimator recurrences (recode.cpp:816-820, 1030-1047),
-// lane-parallel over each batch of ring-0 ops (lane j = op j):
-//  1. every lane loads its op's estimator at once: per-context ones from Shared::est, SIG/NZ
-//     ones by probing the first four slots of the key's window in the LDS hash table; keys not
-//     resolved there (new keys, deep or HBM-resident ones) go through est_load one key at a time,
-//     a new key claiming its slot immediately;
-//  2. a scalar loop walks the batch key by key (ballot of equal keys) and, within a key, op by op
-//     in order: the recurrence runs in a scalar register and each op's estimator before its update
-//     goes into its lane of the output vector -- no memory access on this chain;
-//  3. the last op of each key writes the estimator back (lane-parallel), and the whole batch
-//     goes to ring 1 as one vector store.
-// Ops of one key stay in order, different keys are independent, so this equals processing the
-// ops one by one.
-// lane L of v := x (x, L wave-uniform)
-AVR_FI uint32_t writelane(uint32_t v, uint32_t L, uint32_t x) { return __lane_id() == L ? x : v; }
-// SPL: a batch that holds OP_RESTART (the walker's cut, the batch's last op) ends with a fresh model:
-// the HBM table's logged entries, the LDS hash and the per-context estimators cleared
-template <bool SPL = false>
-AVR_FI void model_slice(Shared* sh, uint16_t* est_g) {
-  uint32_t tail = 0, head1 = 0, tail1 = 0;
-  uint64_t waited = 0;
-  uint32_t prio = 0;
-  const uint32_t lane = __lane_id();
-#ifdef AVR_PROFILE
-  uint64_t out_wait = 0;
-  const uint64_t t_start = PROF_T();
-#endif
-  for (bool done = false; !done;) {
-    uint32_t op_v;
-    const uint32_t n = ring_take(sh, 0, tail, &op_v, &waited);
-    follow_prio(sh, &prio);
-    asm volatile("; MARK_MODEL_BEGIN");
-    const bool live = lane < n;
-    const bool ctrl = (op_v & (OP_END | OP_FINISH)) != 0;
-    const bool est_op = live && !ctrl;
-    if (__ballot(live && (op_v & OP_END))) done = true;
-    const uint32_t idx = (op_v >> 3) & 0x7ffffu;
-    const bool cache = (op_v & OPM_CACHE) != 0;
-    // ---- 1. loads
-    uint32_t e_v = 0, slot_v = 0;
-    bool resolved = true;
-    if (est_op && !cache) e_v = sh->est[idx];
-    if (est_op && cache) resolved = est_probe4(sh, idx, &e_v, &slot_v);
-    // keys the short probe did not find: one at a time through the wave-wide probe
-    uint64_t slow = __ballot(est_op && !resolved);
-    while (slow) {
-      const uint32_t l = (uint32_t)__builtin_ctzll(slow);
-      const uint32_t idx_l = __builtin_amdgcn_readlane(idx, l);
-      uint32_t slot;
-      const uint32_t e = est_load(sh, est_g, idx_l, &slot);
-      if (slot >> 31) {
-        if (lane == 0) sh->etab[slot & 0xffff] = (slot & 0xffff0000u) | e;   // claim / keep the slot
-        wave_sync();
-      }
-      const uint64_t same = __ballot(est_op && cache && idx == idx_l);
-      if ((same >> lane) & 1) { e_v = e; slot_v = slot; }
-      slow &= ~same;
-    }
-    // ---- 2. the recurrences, key by key, ops in order
-    const uint32_t key_v = (op_v >> 1) & 0xfffffdu;            // cache bit + index (bin, threshold excluded)
-    const uint64_t bins_m = __ballot(op_v & 1), thr_m = __ballot(op_v & OPM_THR50);
-    // billing class of op j: significance map (threshold 0x50), nnz bits (the other SIG/NZ
-    // estimators), or anything else
-    const uint64_t nz_m = __ballot(cache && !(op_v & OPM_THR50));
-    auto cls_of = [&](uint32_t j) -> uint32_t { return ((thr_m >> j) & 1) ? 1u : ((nz_m >> j) & 1) ? 2u : 0u; };
-    uint32_t out_v = op_v;                                     // control ops pass through
-    uint32_t fin_v = 0;
-    uint64_t last_m = 0;
-    uint64_t todo = __ballot(est_op);
-    while (todo) {
-      const uint32_t l = (uint32_t)__builtin_ctzll(todo);
-      const uint32_t k = __builtin_amdgcn_readlane(key_v, l);
-      uint64_t m = __ballot(key_v == k) & todo;
-      todo &= ~m;
-      uint32_t e = __builtin_amdgcn_readlane(e_v, l);
-      uint32_t j = l;
-      for (;;) {
-        const uint32_t b = (uint32_t)(bins_m >> j) & 1u;
-        out_v = writelane(out_v, j, op_recode((int)b, e) | cls_of(j) << OPC_SHIFT_C);
-        e = est_update(e, (int)b, ((thr_m >> j) & 1) ? 0x50u : 0x60u);
-        m &= m - 1;
-        if (!m) break;
-        j = (uint32_t)__builtin_ctzll(m);
-      }
-      fin_v = writelane(fin_v, j, e);
-      last_m |= 1ull << j;
-    }
-    // ---- 3. write-back by the last op of each key
-    const bool is_last = (last_m >> lane) & 1;
-    if (is_last && !cache) sh->est[idx] = (uint16_t)fin_v;
-    if (is_last && cache && (slot_v >> 31)) sh->etab[slot_v & 0xffff] = (slot_v & 0xffff0000u) | fin_v;
-    const bool hbm = is_last && cache && !(slot_v >> 31);
-    if (__ballot(hbm)) {
-      if (hbm) est_g[idx] = (uint16_t)(fin_v | kEstWritten);
-      const uint64_t first = __ballot(hbm && slot_v == 1);
-      if (first) {   // append first stores to the table's write log (est_store)
-        const uint32_t base = __builtin_amdgcn_readfirstlane(sh->elog_n);
-        const uint32_t cnt = (uint32_t)__builtin_popcountll(first);
-        const uint32_t pos = base + (uint32_t)__builtin_popcountll(first & ((1ull << lane) - 1));
-        uint32_t* lg = (uint32_t*)(est_g + kEstLog);
-        if (((first >> lane) & 1) && pos < (uint32_t)kEstLogCap) lg[pos] = idx;
-        if (lane == 0) {
-          sh->elog_n = base + cnt;
-          *(uint32_t*)(est_g + kEstLogN) = base + cnt <= (uint32_t)kEstLogCap ? base + cnt : kEstLogOverflow;
-        }
-      }
-    }
-    asm volatile("; MARK_MODEL_END");
-    // ---- the batch to ring 1 (room for n entries), then retire it from ring 0
-    if (head1 + n - tail1 > (uint32_t)kFifo) {
-#ifdef AVR_PROFILE
-      const uint64_t tw = PROF_T();
-#endif
-      WD_T0;
-      for (;;) {
-        tail1 = ld_volatile(&sh->fifo_tail[1]);
-        if (head1 + n - tail1 <= (uint32_t)kFifo) break;
-        WD_POLL(WD_ROOM1, head1, tail1, sh->qnext);
-        __builtin_amdgcn_s_sleep(1);
-      }
-#ifdef AVR_PROFILE
-      out_wait += PROF_T() - tw;
-#endif
-    }
-    if (live) sh->fifo[1][(head1 + lane) & (kFifo - 1)] = out_v;
-    head1 += n;
-    st_volatile(&sh->fifo_head[1], head1);
-    if constexpr (SPL) {
-      if (__ballot(live && (op_v & OP_RESTART))) {
-        const uint32_t nl = *(volatile uint32_t*)(est_g + kEstLogN);
-        if (nl == kEstLogOverflow) {
-          uint4* e4 = (uint4*)est_g;
-          for (uint32_t i = lane; i < (uint32_t)kEstTable / 8; i += 64) e4[i] = make_uint4(0, 0, 0, 0);
-        } else {
-          const uint32_t* lg = (const uint32_t*)(est_g + kEstLog);
-          for (uint32_t i = lane; i < nl; i += 64) est_g[lg[i]] = 0;
-        }
-        if (lane == 0) {
-          *(uint32_t*)(est_g + kEstLogN) = 0;
-          sh->elog_n = 0;
-        }
-        for (uint32_t i = lane; i < (uint32_t)kEstDefault + 2; i += 64) sh->est[i] = 0;
-        for (uint32_t i = lane; i < (uint32_t)kEtabSize + 64; i += 64) sh->etab[i] = 0;
-        __threadfence_block();
-        wave_sync();
-      }
-    }
-    tail += n;
-    ring_retire(sh, 0, tail);
-  }
-#ifdef AVR_PROFILE
-  if (__lane_id() == 0) {
-    atomicAdd(&avr_prof[17], (unsigned long long)waited);
-    atomicAdd(&avr_prof[18], (unsigned long long)out_wait);
-    atomicAdd(&avr_prof[20], (unsigned long long)(PROF_T() - t_start));
-  }
-#endif
-}
-
-// The coder wave: compress retires ring 1 (arithmetic_code<uint64_t,uint8_t>::encoder::put /
-// finish, recode.cpp:1074, 1092-1094), gathering each op's reciprocal record with its lane;
-// decompress retires ring 0 (cabac::encoder::put / put_bypass / put_terminate,
-// recode.cpp:1443-1474, cabac_code.h:33-67).
-// SEQ: the reference model's per-file kernels (one slice chain per CU, where the coder can hold the
-// walker up): the level / mvd prefixes on one context with the state in a register, and the map
-// loops unswitched by block kind.  The slice batch keeps the plain loops (measured: the variants
-// cost the batch 0.3-0.8 % and gain R-mode 1-2 %, profiles/r04o_coder2_ab.log, r04q_crunmvd_ab.log).
-// SPL (decompress): a piece after a cut starts the re-encoder from the seam record; a piece that ends
-// at a cut (seam_end) writes its pending bytes out at the end instead of a flush (the oracle's
-// avr_ce_seam_flush): the bytes of the arithmetic's low up to the next piece's first byte
-// SPL (compress): every OP_FINISH ends a piece's stream -- its length goes to piece_end[k] and a fresh
-// encoder starts the next piece's
-template <int MODE, bool P32, bool SEQ = false, bool SPL = false>
-AVR_FI void coder_slice(Shared* sh, const HotTables* T, const avr_slice_desc* d, uint8_t* out, uint32_t flags,
-                        const SeamRec* seam = nullptr, bool seam_end = false, uint32_t* piece_end = nullptr) {
-  uint32_t pieces = 0;
-  const bool billing = (flags & kFlagBill) != 0;
-  uint32_t bill[6] = {0, 0, 0, 0, 0, 0};
-  uint32_t bill_pend = 0;
-  CabacBill cbill;
-  cb_init(cbill);
-  OutStream o;
-  o.g = out + d->out_offset;
-  o.cap = d->out_capacity;
-  o.n = 0;
-  o.last = 0;
-  typename std::conditional<P32, PEncoder, RecodedEncoder>::type re;   // see Walker::rd
-  CabacEncoder ce;
-  VTab vt;
-  if (MODE == MODE_COMPRESS) {
-    re_init(re);
-    // Keep the coder's interval in VGPRs: every wave of the CU shares one scalar unit, and the
-    // walker wave (the critical path) is scalar-bound; 64-bit multiply-adds are also cheaper on
-    // the vector unit (v_mad_u64_u32).  A value the compiler cannot prove uniform stays vector.
-#ifndef AVR_CODER_SALU
-    const uint32_t z = vgpr_zero();
-    re.range += z;
-    re.low += z;
-#endif
-  } else {
-    ce_init(ce);
-    if constexpr (SPL) {
-      if (seam) {
-        ce.low = seam->ce_low;
-        ce.range = seam->ce_range;
-        ce.queue = seam->ce_queue;
-        ce.outstanding = seam->ce_outstanding;
-        ce.cache = seam->ce_cache;
-        ce.have_cache = 1;
-      }
-    }
-    vtab_load(vt, T);
-  }
-  const int r = MODE == MODE_COMPRESS ? 1 : 0;
-  uint32_t gt1 = 0, eq1 = 0;   // decompress: level counters of the block in progress (op_level)
-  uint32_t mpos = 0;           // decompress: first position of the next op_map segment
-  const uint32_t numc = d->chroma_array_type == 2 ? 2u : 1u;   // chroma DC: NumC8x8
-  uint32_t tail = 0;
-  uint64_t waited = 0;
-#ifdef AVR_PROFILE
-  const uint64_t t_start = PROF_T();
-#endif
-  uint32_t prio = 0;
-  for (bool done = false; !done;) {
-    uint32_t op_v;
-    const uint32_t n = ring_take(sh, r, tail, &op_v, &waited);
-    follow_prio(sh, &prio);
-    if (MODE == MODE_COMPRESS) {
-      const uint32_t tot_v = (op_v >> 8) & 127;
-      const uint64_t m_v = !P32 ? T->div[tot_v][0] : T->rcp32[tot_v];
-      const uint32_t s_v = !P32 ? (uint32_t)T->div[tot_v][1] : 0u;
-      // r1 of op j: the reference coder's exact quotient, or the P-format rule (avr_engine.h)
-      auto r1_of = [&](uint32_t j, uint32_t op) {
-        if constexpr (!P32) {
-          const uint64_t m = readlane64(m_v, j);
-          const uint32_t shift = __builtin_amdgcn_readlane(s_v, j);
-          return (__umul64hi(re.range, m) >> shift) * ((op >> 1) & 127);
-        } else {
-          return __umulhi(re.range, __builtin_amdgcn_readlane((uint32_t)m_v, j)) * ((op >> 1) & 127);
-        }
-      };
-      asm volatile("; MARK_CODER_BEGIN");
-      // control ops (FINISH, END: once per slice) located up front, so the put loop has no checks
-      uint64_t ctrl = __ballot(__lane_id() < n && (op_v & (OP_END | OP_FINISH)));
-      for (uint32_t j = 0;;) {
-        const uint32_t stop = ctrl ? (uint32_t)__builtin_ctzll(ctrl) : n;
-        if (billing) {
-          for (; j < stop; j++) {
-            const uint32_t op = __builtin_amdgcn_readlane(op_v, j);
-            const uint32_t bytes = re_put_billed(re, o, op & 1, r1_of(j, op), &bill_pend);
-            const int c = op_class_pip_c((op >> OPC_SHIFT_C) & 3);
-            if (bytes) bill[c] += bytes;
-          }
-        } else {
-          for (; j < stop; j++) {
-            const uint32_t op = __builtin_amdgcn_readlane(op_v, j);
-            re_put(re, o, op & 1, r1_of(j, op));
-          }
-        }
-        if (j >= n) break;
-        const uint32_t op = __builtin_amdgcn_readlane(op_v, j);
-        if (op & OP_END) { done = true; break; }
-        re_finish(re, o);
-        if constexpr (SPL) {
-          if (piece_end && __lane_id() == 0) piece_end[pieces] = out_total(o);
-          pieces++;
-          re_init(re);
-#ifndef AVR_CODER_SALU
-          const uint32_t z = vgpr_zero();
-          re.range += z;
-          re.low += z;
-#endif
-        }
-        ctrl &= ctrl - 1;
-        j++;
-      }
-      asm volatile("; MARK_CODER_END");
-    } else {
-      // billing: the generic coder's emission counts beside the re-encode, bin by bin
-      auto run = [&](auto BILL) {
-        constexpr bool bl = decltype(BILL)::value;
-        auto put_dec = [&](int b, uint32_t ctx, uint32_t cls) {
-          uint8_t* stp = &sh->state[ctx];
-          if constexpr (bl) {
-            const uint32_t st = *stp;
-            const uint32_t bytes = cb_decision(cbill, b, st, vtab_rec(vt, st));
-            if (bytes) bill[op_class_pip_d(cls)] += bytes;
-          }
-          ce_decision_v(ce, o, b, stp, vt);
-        };
-        // n ones then (if zero) a zero on one context, class 0 (level / mvd prefixes)
-        auto put_run = [&](uint32_t ctx, uint32_t n, bool zero) {
-          uint8_t* stp = &sh->state[ctx];
-          uint32_t st = *stp;
-          for (uint32_t k = 0; k < n + (zero ? 1u : 0u); k++) {
-            const int b = k < n;
-            const CabacRec r = vtab_rec(vt, st);
-            if constexpr (bl) {
-              const uint32_t bytes = cb_decision(cbill, b, st, r);
-              if (bytes) bill[0] += bytes;
-            }
-            uint32_t ns;
-            ce_encode(ce, o, b, st, r, &ns);
-            st = ns;
-          }
-          *stp = (uint8_t)st;
-        };
-        auto put_byp = [&](int b, uint32_t cls) {
-          if constexpr (bl) {
-            const uint32_t bytes = cb_bypass(cbill, b);
-            if (bytes) bill[op_class_pip_d(cls)] += bytes;
-          }
-          ce_bypass(ce, o, b);
-        };
-        for (uint32_t j = 0; j < n; j++) {
-          const uint32_t op = __builtin_amdgcn_readlane(op_v, j);
-          if (op & OP_END) { done = true; break; }
-          const int b = op & 1;
-          const uint32_t kind = (op >> 1) & 3;
-          const uint32_t cls = (op >> OPC_SHIFT_D) & 3;
-          if (kind == OPK_DECISION) {
-            put_dec(b, (op >> 3) & 1023, cls);
-          } else if (kind == OPK_BYPASS) {
-            put_byp(b, cls);
-          } else if (kind == OPK_MACRO) {
-            const uint32_t sub = (op >> 3) & 3, cat = (op >> 5) & 15;
-            if (sub == 0) {   // op_map: significant / last_significant_coeff_flag of one segment
-              const uint32_t npos = ((op >> 9) & 15) + 1, ended = (op >> 13) & 1;
-              const uint32_t mask = op >> 14, lastq = ended ? npos - 1 : 16u;
-              const uint32_t sb = (uint32_t)T->sig_base[cat], lb = (uint32_t)T->last_base[cat];
-              // one loop per block kind (K: 0 4x4-class, 1 chroma DC, 2 8x8), as the walker's
-              auto seg_loop = [&](auto K) {
-                constexpr int k = decltype(K)::value;
-                for (uint32_t q = 0; q < npos; q++) {
-                  const uint32_t p = mpos + q;
-                  uint32_t sc, lc;
-                  if constexpr (k == 2) {
-                    sc = T->sig8x8[p];
-                    lc = T->last8x8[p];
-                  } else if constexpr (k == 1) {
-                    sc = lc = min(p / numc, 2u);
-                  } else {
-                    sc = lc = p;
-                  }
-                  const int sig = (mask >> q) & 1;
-                  put_dec(sig, sb + sc, 1);
-                  if (sig) put_dec(q == lastq, lb + lc, 2);
-                }
-              };
-              if constexpr (!SEQ) {
-                const bool c8 = cat == 5 || cat == 9 || cat == 13;
-                for (uint32_t q = 0; q < npos; q++) {
-                  const uint32_t p = mpos + q;
-                  uint32_t sc, lc;
-                  if (c8) {
-                    sc = T->sig8x8[p];
-                    lc = T->last8x8[p];
-                  } else if (cat == 3) {
-                    sc = lc = min(p / numc, 2u);
-                  } else {
-                    sc = lc = p;
-                  }
-                  const int sig = (mask >> q) & 1;
-                  put_dec(sig, sb + sc, 1);
-                  if (sig) put_dec(q == lastq, lb + lc, 2);
-                }
-              } else if (cat == 5 || cat == 9 || cat == 13) {
-                seg_loop(std::integral_constant<int, 2>());
-              } else if (cat == 3) {
-                seg_loop(std::integral_constant<int, 1>());
-              } else {
-                seg_loop(std::integral_constant<int, 0>());
-              }
-              if (npos != 16 || ended) {   // the map's last segment: its block's levels follow
-                mpos = 0;
-                gt1 = eq1 = 0;
-              } else {
-                mpos += 16;
-              }
-            } else if (sub == 1) {   // op_level: coeff_abs_level_minus1 prefix (+ sign)
-              const uint32_t sg = (op >> 9) & 1, absl = (op >> 10) & 15;
-              const uint32_t ab = (uint32_t)T->abs_base[cat];
-              put_dec(absl > 1, ab + (gt1 ? 0u : min(4u, 1 + eq1)), 0);
-              if (absl > 1) {
-                const uint32_t c1 = ab + 5 + min(4u - (cat == 3), gt1);
-                if constexpr (SEQ) {
-                  put_run(c1, absl - 2, absl < 15);   // one context: its state stays in a register
-                } else {
-                  for (uint32_t a = 2; a < 15; a++) {
-                    const int more = a < absl;
-                    put_dec(more, c1, 0);
-                    if (!more) break;
-                  }
-                }
-              }
-              if (absl < 15) put_byp((int)sg, 0);
-              if (absl == 1) eq1++;
-              else gt1++;
-            } else {   // op_mvd: mvd_lX[][][comp] prefix (+ sign), 9.3.3.1.1.7 / 9.3.3.1.2
-              const uint32_t base = (op & 32) ? 47u : 40u, sg = (op >> 8) & 1, am = (op >> 9) & 15;
-              put_dec(am > 0, base + ((op >> 6) & 3), 0);
-              if (am > 0) {
-                // bins m = 1, 2, 3 on contexts base + 3, 4, 5, then m = 4 .. 8 on base + 6
-                uint32_t m = 1;
-                for (; m < 4; m++) {
-                  const int more = m < am;
-                  put_dec(more, base + m + 2, 0);
-                  if (!more) break;
-                }
-                if (m == 4) {
-                  if constexpr (SEQ) {
-                    put_run(base + 6, min(am, 9u) - 4, am < 9);
-                  } else {
-                    for (; m < 9; m++) {
-                      const int more = m < am;
-                      put_dec(more, base + 6, 0);
-                      if (!more) break;
-                    }
-                  }
-                }
-                if (am < 9) put_byp((int)sg, 0);
-              }
-            }
-          } else {
-            if constexpr (bl) {
-              const uint32_t bytes = cb_terminate(cbill, b);
-              if (bytes) bill[op_class_pip_d(cls)] += bytes;
-            }
-            ce_terminate(ce, o, b);
-          }
-        }
-      };
-      if (billing) run(std::true_type());
-      else run(std::false_type());
-    }
-    tail += n;
-    ring_retire(sh, r, tail);
-  }
-#ifdef AVR_PROFILE
-  if (__lane_id() == 0) {
-    atomicAdd(&avr_prof[19], (unsigned long long)waited);
-    atomicAdd(&avr_prof[21], (unsigned long long)(PROF_T() - t_start));
-  }
-#endif
-  if constexpr (SPL) {
-    if (MODE == MODE_DECOMPRESS && seam_end) {
-      const uint32_t carry = ce.low >> (ce.queue + 18);
-      if (ce.have_cache) {
-        if (ce.cache + carry > 0xff) ce.err = 1;
-        out_byte(o, ce.cache + carry);
-      } else if (carry) {
-        ce.err = 1;
-      }
-      if (ce.outstanding) out_repeat(o, (0xff + carry) & 0xff, ce.outstanding);
-    }
-  }
-  if (__lane_id() == 0) {
-    sh->c_err = MODE == MODE_COMPRESS ? re.err : ce.err;
-    sh->c_len = out_total(o);
-    sh->c_last = o.last;
-    for (int i = 0; i < 6; i++) sh->bill[i] = bill[i];
-  }
-}
-
-// Combine the two waves' results (after a workgroup barrier), with run_slice_inline's semantics.
-// seam_end: a piece that ends at a cut (its last byte is not the slice's)
-template <int MODE>
-AVR_FI void finish_slice(const Shared* sh, const avr_slice_desc* d, avr_slice_result* res, bool seam_end = false) {
-  int status = sh->p_status;
-  if (sh->c_err) status = AVR_SLICE_CODER;
-  if (MODE == MODE_COMPRESS && !status && !sh->p_stop_ok) status = AVR_SLICE_NO_STOP;
-  uint32_t len = sh->c_len;
-  if (len > d->out_capacity) {   // nothing past the capacity was written: report what was
-    status = AVR_SLICE_OVERFLOW;
-    len = d->out_capacity;
-  }
-  if (MODE == MODE_DECOMPRESS && !status && len && sh->c_last == 0x80 && !seam_end) len--;  // recode.cpp:1503-1505
-  res->out_len = len;
-  res->status = status;
-  for (int i = 0; i < 6; i++) res->bill[i] = sh->bill[i];
-}
-
-// Single-wave slice (the generator: CABAC encode inline, no coder wave).
-template <int MODE, bool RM, bool FLD, bool P32, bool SPL>
-AVR_FI void run_slice_inline(Walker<MODE, RM, FLD, P32, SPL>& w, const avr_slice_desc* d, const uint8_t* in, uint8_t* out,
-                             avr_slice_result* res) {
-  begin_slice(w, d, in, out);
-  profile_slice(w);
-  w.rc_writeback();
-  w.mc_store();
-  int status = w.err;
-  if (!status && !w.finished) status = AVR_SLICE_NO_END;
-  if (MODE == MODE_GENERATE && w.ce.err) status = AVR_SLICE_CODER;
-  if (out_overflow(w.out)) status = AVR_SLICE_OVERFLOW;
-  if (__lane_id() == 0) {
-    res->out_len = out_total(w.out);
-    res->status = status;
-    res->bins = w.bins;
-    res->mbs = (uint32_t)w.mbs_done;
-    for (int i = 0; i < 6; i++) res->bill[i] = 0;
-  }
-}
-
-// Copy the per-bin lookup tables into this workgroup's LDS (16 B per thread per step).
-AVR_FI void load_hot_tables(Shared* sh, const EngineTables* G) {
-  const uint4* src = (const uint4*)&G->hot;
-  uint4* dst = (uint4*)&sh->tab;
-  for (int i = threadIdx.x; i < (int)(sizeof(HotTables) / 16); i += blockDim.x) dst[i] = src[i];
-  __syncthreads();
-}
-
-// Threads per workgroup: two waves (walker + coder) for compress / decompress, one for generate.
-template <int MODE>
-constexpr int slice_threads() {
-  return MODE == MODE_GENERATE || MODE == MODE_TRACE ? 64 : MODE == MODE_COMPRESS ? 192 : 128;
-}
-
-// One slice of a parallel launch on this workgroup (every thread): the hot tables are in LDS
-// already; est_g is the slice's estimator scratch; cell = the walker's CU-board cell (kNoCell:
-// register one).
-// MG: the launch may keep the model row in global scratch (the persistent kernel, which every wide
-// launch uses); the resident kernel's row is always in LDS (a constant: no branch at its accesses).
-template <int MODE, bool FLD, bool P32, bool MG, bool SPL = false>
-AVR_FI void parallel_slice(uint8_t* smem, const EngineTables* G, const avr_slice_desc* descs, int s, const uint8_t* in,
-                           uint8_t* out, avr_slice_result* res, uint16_t* est_g, uint32_t flags, uint32_t cell,
-                           uint32_t qiter = 0, const SplitArgs* sp = nullptr) {
-  const avr_slice_desc* d = &descs[s];
-  Walker<MODE, false, FLD, P32, SPL> w;
-  w.sh = (Shared*)smem;
-  w.ring = (typename Walker<MODE, false, FLD, P32, SPL>::ERec*)(smem + sizeof(Shared));
-  bool seam_end = false;
-  uint32_t* piece_end = nullptr;
-  if constexpr (SPL) {
-    const PieceCtl c = sp->ctl[s];
-    w.seam = c.seam >= 0 ? (const SeamRec*)(sp->recs + (size_t)c.seam * sp->rec_stride) : nullptr;
-    w.piece_mbs = c.n_mbs;
-    w.cut = 0;
-    seam_end = c.n_mbs != 0;
-    piece_end = MODE == MODE_COMPRESS && c.snap >= 0 && sp->piece_end ? sp->piece_end + c.snap : nullptr;
-    w.snap = MODE == MODE_COMPRESS && c.snap >= 0 ? sp->recs + (size_t)c.snap * sp->rec_stride : nullptr;
-    w.snap_cap = c.snap_cap;
-    w.snap_n = 0;
-    w.snap_last = 0;
-    w.snap_q = 0;
-    w.split_bits = sp->split_bits;
-    w.rec_stride = sp->rec_stride;
-    w.snap_count = sp->snap_n ? sp->snap_n + s : nullptr;
-  }
-  w.mring_global = MG && !FLD && (flags & kFlagMringGlobal);
-  w.mring = w.mring_global ? (uint32_t*)(est_g + kEstMring)
-                           : (uint32_t*)(smem + sizeof(Shared) + (size_t)(flags >> kFlagRingShift) * sizeof(EdgeCore));
-  w.prio_cell = cell;
-  w.T = &w.sh->tab;
-  w.G = G;
-  w.frames = nullptr;
-  w.cur_off = 0;
-  w.prev_off = -1;
-  w.gmode = false;
-  w.gsink = nullptr;
-  w.gcount = 0;
-  w.est_g = est_g;
-  w.ring_cols = flags >> kFlagRingShift;
-  if (!d->coded) {
-    if (threadIdx.x == 0) {
-      res[s].out_len = 0;
-      res[s].status = 1;
-      res[s].bins = 0;
-      res[s].mbs = 0;
-      for (int i = 0; i < 6; i++) res[s].bill[i] = 0;
-    }
-    return;
-  }
-  // fresh model for this slice: undo the last model's stores to the HBM estimator table
-  if (MODE == MODE_COMPRESS || MODE == MODE_DECOMPRESS) est_table_reset(w.est_g, w.sh);
-  if (MG) QTRACE(threadIdx.x >> 6, qiter << 8 | 2);
-  w.d = d;
-  w.W = d->mb_width;
-  if ((MODE == MODE_COMPRESS || MODE == MODE_DECOMPRESS) && threadIdx.x == 0) w.sh->prio = 0;   // before init_slice_state's barrier
-  init_slice_state(w, G);
-  if (MG) QTRACE(threadIdx.x >> 6, qiter << 8 | 3);
-  if (MODE == MODE_GENERATE || MODE == MODE_TRACE) {
-    run_slice_inline(w, d, in, out, &res[s]);
-    return;
-  }
-  const int wave = threadIdx.x >> 6;
-  AVR_PLACE(s, wave);
-  if (wave == 0) {
-    AVR_PLACE_T(s, 0);
-    walker_slice(w, d, in, &res[s]);
-    AVR_PLACE_T(s, 1);
-  }
-  else if (MODE == MODE_COMPRESS && wave == 1) model_slice<SPL>(w.sh, w.est_g);
-  else if constexpr (SPL) coder_slice<MODE, P32, false, true>(w.sh, w.T, d, out, flags, w.seam, seam_end, piece_end);
-  else coder_slice<MODE, P32>(w.sh, w.T, d, out, flags);
-  if (MG) QTRACE(wave, qiter << 8 | 4);
-  __syncthreads();
-  if (MG) QTRACE(wave, qiter << 8 | 5);
-  if (threadIdx.x == 0) finish_slice<MODE>(w.sh, d, &res[s], seam_end);
-}
-
-// The long-slice split's launches (avr_kernels.h SplitArgs): progressive frame slices and pieces of
-// the parallel model on arithmetic_code<uint64_t, uint8_t>, the model row in LDS; each workgroup
-// takes descriptors blockIdx.x, blockIdx.x + gridDim.x, ... (a grid of at most the resident slots:
-// one estimator scratch per workgroup).  Compress: whole long slices in a single walk, each cut as
-// it is walked -- the cut records taken (PieceCtl::snap) and the model started afresh at every cut;
-// or pieces (seam >= 0: started from a record, n_mbs > 0: stopped at the next cut).  Decompress: the
-// pieces, from records the host wrote (the container's seams).
-template <int MODE>
-__global__ __launch_bounds__(192, 4) void slices_split_kernel(const EngineTables* G, const avr_slice_desc* descs, int n,
-                                                             const uint8_t* in, uint8_t* out, avr_slice_result* res,
-                                                             uint16_t* est_scratch, SplitArgs sp, uint32_t flags) {
-  extern __shared__ __align__(16) uint8_t smem[];
-  uint32_t cell = kNoCell;
-  bool loaded = false;
-  for (int s = blockIdx.x; s < n; s += gridDim.x) {
-    __syncthreads();   // the previous descriptor's finish_slice has read the workgroup's LDS
-    if (!loaded) {
-      load_hot_tables((Shared*)smem, G);
-      loaded = true;
-      if (threadIdx.x < 64) cell = cu_cell();
-    }
-    parallel_slice<MODE, false, false, false, true>(smem, G, descs, s, in, out, res,
-                                                    est_scratch + (size_t)blockIdx.x * kEstGlobal, flags, cell, 0, &sp);
-  }
-}
-
-// FLD = false: the progressive frames of the batch; FLD = true: its field pictures and MBAFF frames
-// (a second launch over the same batch: each kernel leaves the other's slices alone).
-//
-// Two ways to run a batch:
-//  - qhead == nullptr: workgroup b runs slice order[b] (the CU grouping of schedule_kernel) or b,
-//    with the estimator scratch of that slice -- a batch that is resident all at once;
-//  - qhead != nullptr (a batch larger than the chip holds at once): a persistent grid of about one
-//    workgroup per resident slot; each workgroup takes the next entry of the queue `order` (the
-//    slices sorted largest first, queue_order_kernel) by an atomic on *qhead until the queue is
-//    empty, with one estimator scratch per workgroup (est_table_reset undoes the previous slice's
-//    stores).  Every workgroup leaves when it draws past the end, so the grid always drains.
-//    Largest first is LPT: the batch ends on small slices instead of on a large one started late,
-//    and there are no launch boundaries inside the batch to wait at.
-template <int MODE, bool FLD, bool P32 = false>
-__global__ __launch_bounds__(192, 4) void slices_parallel_kernel(const EngineTables* G, const avr_slice_desc* descs, int n,
-                                                                const uint8_t* in, uint8_t* out, avr_slice_result* res,
-                                                                uint16_t* est_scratch, const int* order,
-                                                                uint32_t flags) {
-  extern __shared__ __align__(16) uint8_t smem[];
-  if ((int)blockIdx.x >= n) return;
-  const int s = order ? order[blockIdx.x] : (int)blockIdx.x;   // CU grouping (schedule_kernel)
-  if ((descs[s].structure != AVR_STRUCT_FRAME) != FLD) return;
-  load_hot_tables((Shared*)smem, G);
-  parallel_slice<MODE, FLD, P32, false>(smem, G, descs, s, in, out, res, est_scratch + (size_t)s * kEstGlobal, flags,
-                                        kNoCell);
-}
-
-// The persistent variant (a kernel of its own: the loop's state would change the resident
-// kernel's register allocation): about one workgroup per resident slot, each taking the next entry
-// of the largest-first queue by an atomic on *qhead until the queue is empty.
-template <int MODE, bool FLD, bool P32 = false>
-__global__ __launch_bounds__(192, 4) void slices_queue_kernel(const EngineTables* G, const avr_slice_desc* descs, int n,
-                                                             const uint8_t* in, uint8_t* out, avr_slice_result* res,
-                                                             uint16_t* est_scratch, const int* queue, uint32_t* qhead,
-                                                             uint32_t flags) {
-  extern __shared__ __align__(16) uint8_t smem[];
-  Shared* sh = (Shared*)smem;
-  // the hot tables and the walker wave's CU-board cell are set up at the first slice this
-  // workgroup takes (a field-kernel workgroup that finds no field slice does neither).  The other
-  // order (-DAVR_QUEUE_EAGER) hangs the first queue launch of a process in its
-  // uninstrumented build only: every instrumented build of it (bounded waits with invariant checks,
-  // host-mapped progress records) runs clean and sees no invariant violated, so the hang follows
-  // that build's code generation, not an ordering rule of the protocol below.
-  uint32_t cell = kNoCell;
-  bool loaded = false;
-  uint32_t qiter = 0;   // slices this workgroup drew (queue trace builds)
-#ifdef AVR_WATCHDOG
-  if ((threadIdx.x & 63) == 0) sh->wd_epoch[threadIdx.x >> 6] = 0;
-  uint32_t wd_prev_k = 0xffffffffu;
-#endif
-#ifdef AVR_QUEUE_EAGER   // experiment builds: the round-5 order that hung (r05c: 1, r05e: 2)
-  load_hot_tables(sh, G);
-  loaded = true;
-  if ((MODE == MODE_COMPRESS || MODE == MODE_DECOMPRESS) && threadIdx.x < 64) {
-    cell = cu_cell();
-#if AVR_QUEUE_EAGER == 1
-    if (__lane_id() == 0) *(volatile __attribute__((address_space(3))) uint32_t*)&sh->qcell = cell;
-#endif
-  }
-#endif
-  for (;;) {
-    if (threadIdx.x == 0) *(volatile __attribute__((address_space(3))) uint32_t*)&sh->qnext = atomicAdd(qhead, 1u);
-#ifdef AVR_WATCHDOG
-    if ((threadIdx.x & 63) == 0) sh->wd_epoch[threadIdx.x >> 6]++;
-#endif
-    __syncthreads();
-    const uint32_t k = __builtin_amdgcn_readfirstlane(*(volatile __attribute__((address_space(3))) uint32_t*)&sh->qnext);
-#ifdef AVR_WATCHDOG
-    if (threadIdx.x == 0)
-      for (uint32_t v = 1; v < blockDim.x / 64; v++)
-        WD_CHECK(sh->wd_epoch[v] == sh->wd_epoch[0], WD_EPOCH, sh->wd_epoch[0], sh->wd_epoch[v], k);
-    WD_CHECK(wd_prev_k == 0xffffffffu || k > wd_prev_k, WD_QORDER, wd_prev_k, k, k);
-    wd_prev_k = k;
-#endif
-    __syncthreads();   // every thread has its entry before thread 0 draws again
-    if (k >= (uint32_t)n) break;
-    const int s = queue[k];
-    if ((descs[s].structure != AVR_STRUCT_FRAME) != FLD) continue;
-    if (!loaded) {
-      load_hot_tables(sh, G);
-      loaded = true;
-      if ((MODE == MODE_COMPRESS || MODE == MODE_DECOMPRESS) && threadIdx.x < 64) cell = cu_cell();
-    }
-#if defined(AVR_QUEUE_EAGER) && AVR_QUEUE_EAGER == 1
-    cell = __builtin_amdgcn_readfirstlane(*(volatile __attribute__((address_space(3))) uint32_t*)&sh->qcell);
-#endif
-    WD_CHECK(cell == kNoCell || cell < 4u * kCuIds, WD_CELL, cell, threadIdx.x, k);
-#ifdef AVR_QTRACE
-    qiter++;
-    if (threadIdx.x == 0) QTRACE1(3, k);
-    QTRACE(threadIdx.x >> 6, qiter << 8 | 1);
-#endif
-    parallel_slice<MODE, FLD, P32, true>(smem, G, descs, s, in, out, res, est_scratch + (size_t)blockIdx.x * kEstGlobal,
-                                         flags, cell, qiter);
-  }
-  QTRACE1(threadIdx.x >> 6, qiter << 8 | 6);
-}
-
-// Host side of the parallel launches (instantiated in each kernel TU, avr_k_*.hip, with that TU's
-// own CU board): the progressive kernel over the batch, then -- when the batch may hold field
-// pictures / MBAFF frames -- the field-capable kernel over the same batch (its workgroups for
-// progressive slices return at once).  The board starts empty on every launch (cu_cell's slot
-// counter must not carry a previous launch's residue).  q.head: the persistent queue launch
-// (slices_parallel_kernel) over q.grid workgroups, q.head[0] for the progressive kernel and
-// q.head[1] for the field one (both zero on entry).  q.lane (FieldLane): the field kernel runs on a
-// stream of its own beside the progressive one, so a mixed batch takes the longer of the two
-// kernels instead of their sum.  The two kernels share the board (it ranks the slices of a CU
-// whichever kernel walks them; one reset before both) and touch disjoint slices; their persistent
-// workgroups take disjoint estimator scratches (the field kernel's after the q.grid progressive ones).
-struct QueueLaunch {
-  uint32_t* head = nullptr;
-  int grid = 0, grid_fld = 0;   // persistent grids of the progressive and the field kernel
-  size_t lds_fld = 0;           // LDS of the field kernel (0: the progressive kernel's)
-  const FieldLane* lane = nullptr;
-};
-template <int MODE, bool P32>
-inline hipError_t launch_parallel(const EngineTables* T, const avr_slice_desc* descs, int n, size_t lds,
-                                  const uint8_t* in, uint8_t* out, avr_slice_result* res, uint16_t* est,
-                                  const int* order, uint32_t flags, hipStream_t stream, QueueLaunch q = QueueLaunch()) {
-  const size_t lds_fld = q.lds_fld ? q.lds_fld : lds;
-  const bool fields = (flags & kFlagFields) != 0;
-  const bool side = fields && q.lane && q.lane->stream;
-  if (hipError_t e = reset_cu_board(stream); e != hipSuccess) return e;
-  hipStream_t fs = stream;
-  if (side) {
-    fs = q.lane->stream;
-    if (hipError_t e = hipEventRecord(q.lane->fork, stream); e != hipSuccess) return e;
-    if (hipError_t e = hipStreamWaitEvent(fs, q.lane->fork, 0); e != hipSuccess) return e;
-  }
-  if (q.head)
-    hipLaunchKernelGGL((slices_queue_kernel<MODE, false, P32>), dim3(q.grid), dim3(slice_threads<MODE>()), lds, stream,
-                       T, descs, n, in, out, res, est, order, q.head, flags);
-  else
-    hipLaunchKernelGGL((slices_parallel_kernel<MODE, false, P32>), dim3(n), dim3(slice_threads<MODE>()), lds, stream,
-                       T, descs, n, in, out, res, est, order, flags);
-  if (fields) {
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    if (!side)
-      if (hipError_t e = reset_cu_board(stream); e != hipSuccess) return e;
-    // beside the progressive kernel, the persistent field workgroups take the scratches after its grid
-    uint16_t* est_f = side && q.head ? est + (size_t)q.grid * kEstGlobal : est;
-    if (q.head)
-      hipLaunchKernelGGL((slices_queue_kernel<MODE, true, P32>), dim3(q.grid_fld), dim3(slice_threads<MODE>()), lds_fld,
-                         fs, T, descs, n, in, out, res, est_f, order, q.head + 1, flags & ~kFlagMringGlobal);
-    else
-      hipLaunchKernelGGL((slices_parallel_kernel<MODE, true, P32>), dim3(n), dim3(slice_threads<MODE>()), lds_fld,
-                         fs, T, descs, n, in, out, res, est_f, order, flags & ~kFlagMringGlobal);
-    if (side) {
-      if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-      if (hipError_t e = hipEventRecord(q.lane->join, fs); e != hipSuccess) return e;
-      if (hipError_t e = hipStreamWaitEvent(stream, q.lane->join, 0); e != hipSuccess) return e;
-    }
-  }
-  return hipGetLastError();
-}
-
-// Reference model: one workgroup (walker + coder wave) walks every slice of a file in file order
-// with persistent estimators and frame metadata.  Several files at once: workgroup f walks file f,
-// the slices [file_first[f], file_first[f + 1]) (file_first == nullptr: one file, all n slices),
-// with its own estimator table (est_g + f kEstGlobal), frames (frames + f frame_stride) and
-// frame_meta[f] -- files share nothing, as separate runs of the reference would not.
-// FLD = true when the files may hold field pictures or MBAFF frames (the field-capable walker
-// also walks progressive slices); FLD = false refuses such a slice (status -21)
-template <int MODE, bool FLD>
-__global__ __launch_bounds__(192) void slices_sequential_kernel(const EngineTables* G, const avr_slice_desc* descs, int n,
-                                                                  const uint8_t* in, uint8_t* out,
-                                                                  avr_slice_result* res, uint16_t* est_g,
-                                                                  uint8_t* frames, int* frame_meta,
-                                                                  const int* file_first, uint64_t frame_stride,
-                                                                  uint32_t flags) {
-  extern __shared__ __align__(16) uint8_t smem[];
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int file = (int)blockIdx.x;
-  const int s_begin = file_first ? file_first[file] : 0;
-  const int s_end = file_first ? file_first[file + 1] : n;
-  est_g += (size_t)file * kEstGlobal;
-  frames += (size_t)file * frame_stride;
-  frame_meta += file;
-  Walker<MODE, true, FLD> w;
-  w.sh = (Shared*)smem;
-  w.ring = (typename Walker<MODE, true, FLD>::ERec*)(smem + sizeof(Shared));
-  w.mring = nullptr;   // the reference model reads its neighbours' model bytes from the frame
-  w.mring_global = false;
-  load_hot_tables(w.sh, G);
-  w.T = &w.sh->tab;
-  w.G = G;
-  w.est_g = est_g;
-  w.frames = frames;
-  w.ring_cols = flags >> kFlagRingShift;
-  // fresh global model
-  {
-    uint4* e4 = (uint4*)est_g;
-    for (int i = tid; i < kEstGlobal / 8; i += nt) e4[i] = make_uint4(0, 0, 0, 0);
-    if (tid == 0) {
-      w.sh->elog_n = 0;
-      w.sh->prio = 0;
-    }
-    for (int i = tid; i < kEstDefault + 2; i += nt) w.sh->est[i] = 0;
-    for (int i = tid; i < kEtabSize + 64; i += nt) w.sh->etab[i] = 0;
-  }
-  // frame_meta: [0] cur_frame.  Frame ids / sizes of the two frames, as scalars (no private arrays).
-  int cur = 0, fid0 = 0, fid1 = 0, fw0 = 0, fw1 = 0, fh0 = 0, fh1 = 0;
-  __syncthreads();
-  for (int s = s_begin; s < s_end; s++) {
-    const avr_slice_desc* d = &descs[s];
-    const int W = d->mb_width, H = d->mb_height;
-    // update_frame_spec (recode.cpp:824-843)
-    const int fwc = cur ? fw1 : fw0, fhc = cur ? fh1 : fh0, fidc = cur ? fid1 : fid0;
-    if (fwc != W || fhc != H || !(fidc == d->picture_id && fwc && fhc)) {
-      cur = 1 - cur;
-      const int fwn = cur ? fw1 : fw0, fhn = cur ? fh1 : fh0;   // the new current frame
-      const int fwo = cur ? fw0 : fw1, fho = cur ? fh0 : fh1;   // the other one
-      const bool reinit_other = (fwn != W || fhn != H) && (fwo != W || fho != H);
-      // fresh/cleared current frame; a dimension change also clears the other one
-      uint32_t* f32 = (uint32_t*)(frames + (size_t)cur * W * H * 52);
-      for (int i = tid; i < W * H * 13; i += nt) f32[i] = 0;
-      if (reinit_other) {
-        uint32_t* o32 = (uint32_t*)(frames + (size_t)(1 - cur) * W * H * 52);
-        for (int i = tid; i < W * H * 13; i += nt) o32[i] = 0;
-        if (cur) { fw0 = W; fh0 = H; } else { fw1 = W; fh1 = H; }
-      }
-      if (cur) { fw1 = W; fh1 = H; fid1 = d->picture_id; } else { fw0 = W; fh0 = H; fid0 = d->picture_id; }
-      __threadfence_block();
-      __syncthreads();
-    }
-    if (!d->coded || (!FLD && d->structure != AVR_STRUCT_FRAME)) {
-      if (tid == 0) {
-        res[s].out_len = 0;
-        res[s].status = d->coded ? -21 : 1;
-        res[s].bins = 0;
-        res[s].mbs = 0;
-      for (int i = 0; i < 6; i++) res[s].bill[i] = 0;
-      }
-      continue;
-    }
-    w.cur_off = (int64_t)cur * W * H * 52;
-    w.prev_off = (int64_t)(1 - cur) * W * H * 52;
-    w.gmode = false;
-    w.gsink = nullptr;
-    w.gcount = 0;
-    w.d = d;
-    w.W = W;
-    init_slice_state(w, G);
-    const int wave = tid >> 6;
-    if (wave == 0) walker_slice(w, d, in, &res[s]);
-    else if (MODE == MODE_COMPRESS && wave == 1) model_slice(w.sh, w.est_g);
-    else coder_slice<MODE, false, true>(w.sh, w.T, d, out, flags);
-    __syncthreads();
-    if (tid == 0) finish_slice<MODE>(w.sh, d, &res[s]);
-    __syncthreads();
-  }
-  if (tid == 0) frame_meta[0] = cur;
 }
 
 }  // namespace avr

@@ -774,7 +774,7 @@ static void decode_mb_layer(walker_t *w) {
   }
 }
 
-/* The upper row's bottom edges as the device walkers keep them (avr_walker.h EdgeCore, one per column;
+/* The upper row's bottom edges as the device walkers keep them (avr_slice_lds.h EdgeCore, one per column;
  * zero where that macroblock is not in the slice): the fields the CABAC context selection of the
  * row below reads (9.3.3.1.1), AVR_EDGE_BYTES each. */
 static void edge_row(const walker_t *w, int y, uint8_t *out) {

@@ -3,11 +3,11 @@ walker's instructions per bin by role).  Input: device assembly with line tables
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -g -fPIC --cuda-device-only -S \\
       avrecode_amd/csrc/avr_k_decompress.hip -o /tmp/dec_g.s
-  python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --anchor 1562 1596
+  python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --anchor 943 977
   python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --loop 4887
 
 Each instruction carries the inlining chain of its .loc comment; its role is the first frame of the
-chain that falls in a known range of avr_walker.h / avr_engine.h (ROLES below).  --anchor LINE CALLER
+chain that falls in a known range of avr_walker.h / avr_slice_lds.h / avr_engine.h (ROLES below).  --anchor LINE CALLER
 lists the innermost loops holding an instruction inlined from LINE through CALLER; --loop HDR prints
 that loop's blocks (not those of loops nested in it) with their roles and the per-role sums.  The
 code generation only: which blocks a bin runs is read off the listing."""
@@ -16,19 +16,19 @@ import collections
 import re
 import sys
 
-W, E = "avr_walker.h", "avr_engine.h"
+W, L, E = "avr_walker.h", "avr_slice_lds.h", "avr_engine.h"
 # (file, first line, last line, role): the decompress walker's map, level and bin helpers
 ROLES = [
     (E, 392, 396, "est_update"), (E, 535, 573, "decision"), (E, 60, 110, "decision"),
-    (W, 562, 591, "est_lookup"), (W, 609, 620, "est_lookup"),
-    (W, 592, 605, "est_store"), (W, 1562, 1567, "est_store"), (W, 1585, 1588, "est_store"),
-    (W, 912, 933, "decision"), (W, 935, 950, "decision"), (W, 420, 425, "decision"),
-    (W, 432, 500, "op_emit"), (W, 258, 275, "op_emit"), (W, 960, 979, "op_emit"),
-    (W, 1569, 1570, "op_emit"), (W, 1578, 1583, "op_emit"), (W, 1589, 1592, "op_emit"), (W, 1658, 1660, "op_emit"),
-    (W, 1545, 1557, "context"), (W, 1649, 1649, "context"), (W, 1653, 1653, "context"),
-    (W, 1544, 1544, "bookkeeping"), (W, 1568, 1568, "bookkeeping"), (W, 1571, 1577, "bookkeeping"),
-    (W, 1647, 1647, "bookkeeping"), (W, 1650, 1657, "bookkeeping"), (W, 1668, 1669, "bookkeeping"),
-    (W, 354, 360, "sync"),
+    (L, 409, 438, "est_lookup"), (L, 456, 467, "est_lookup"),
+    (L, 439, 452, "est_store"), (W, 943, 948, "est_store"), (W, 966, 969, "est_store"),
+    (W, 298, 319, "decision"), (W, 321, 336, "decision"), (L, 280, 285, "decision"),
+    (L, 292, 353, "op_emit"), (L, 186, 194, "op_emit"), (W, 341, 360, "op_emit"),
+    (W, 950, 951, "op_emit"), (W, 959, 964, "op_emit"), (W, 970, 973, "op_emit"), (W, 1039, 1041, "op_emit"),
+    (W, 926, 938, "context"), (W, 1030, 1030, "context"), (W, 1034, 1034, "context"),
+    (W, 925, 925, "bookkeeping"), (W, 949, 949, "bookkeeping"), (W, 952, 958, "bookkeeping"),
+    (W, 1028, 1028, "bookkeeping"), (W, 1031, 1038, "bookkeeping"), (W, 1049, 1050, "bookkeeping"),
+    (L, 214, 220, "sync"),
 ]
 
 

@@ -87,7 +87,7 @@ def test_table_check_detects_a_wrong_entry():
 
 def test_upper_neighbours_read_only_the_kept_model_row_dwords():
     """The parallel model's walkers keep, per macroblock column, only the model bytes an upper
-    neighbour lookup can reach (avr_walker.h kMringUsed: mnnz dwords 2, 3, 6, 7, 10, 11, 12).
+    neighbour lookup can reach (avr_slice_lds.h kMringUsed: mnnz dwords 2, 3, 6, 7, 10, 11, 12).
     Pinned by the reference's own answer: every upper neighbour recode.cpp:233-471 returns in the
     macroblock above (tests/golden/geometry.json) lies in those dwords."""
     kept = {2, 3, 6, 7, 10, 11, 12}
