@@ -538,8 +538,9 @@ struct RecodedDecoder {
   uint32_t next;        // next byte index
 };
 __device__ __forceinline__ void rd_consume(RecodedDecoder& d, InStream& in) {
-  // the byte comes from LDS in a vector register: move it to a scalar one so that low stays a
-  // scalar register (otherwise every bin pays vector<->scalar transfers on low)
+  // this decoder's interval is scalar (the sequential kernels' and the compress-side users'
+  // choice; the slice batch's decompress walker uses VDecoder below): the byte comes from LDS in
+  // a vector register and moves to a scalar one, so that low stays a scalar register
   uint32_t b = __builtin_amdgcn_readfirstlane(in_byte(in, d.next++));
   uint32_t digit = ((d.next_digit & 1) << 7) | (b >> 1);
   d.next_digit = b;
@@ -570,6 +571,54 @@ __device__ __forceinline__ int rd_get(RecodedDecoder& d, InStream& in, uint64_t 
     if (hi32(d.range) < (1u << 23)) rd_consume(d, in);
   }
   return bin;
+}
+
+// The same decoder with its interval on the vector unit (the slice batch's decompress walker).
+// range and d = low - range are wave-uniform values held in VGPRs for the whole slice: the
+// reciprocal product is v_mad_u64_u32 work there (half the scalar unit's multiply count) and the
+// outcome of a decision is the lane mask of one vector compare -- all ones or all zeros -- which
+// the selects take as it is and the scalar side reads as a branch condition (wave_all).  Nothing
+// of the interval crosses to the scalar unit per decision.
+// d instead of low: low - r0 = d + r1 is one 64-bit add (no borrow chain through VCC), the bin-1
+// outcome (low -= r0, range = r1) leaves d as it was and the bin-0 outcome (range = r0) makes
+// d = low - r0, the sum just formed.  low < range <= 2^63, so d is in [-2^63, -1] and
+// low' = (low << 8) | digit, range' = range << 8 is d' = (d << 8) | digit.
+struct VDecoder {
+  uint64_t d, range;    // VGPRs (made opaque to the uniformity analysis in rd_init)
+  uint32_t next_digit;  // last aligned digit read, as in_byte returned it (a VGPR)
+  uint32_t next;        // next byte index (scalar)
+};
+// a condition on wave-uniform VGPR values as a scalar one: the compare's mask, tested as a whole
+__device__ __forceinline__ bool wave_all(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0; }
+__device__ __forceinline__ uint32_t vhi32(uint64_t x) { return (uint32_t)(x >> 32); }
+__device__ __forceinline__ void rd_consume(VDecoder& d, InStream& in) {
+  const uint32_t b = in_byte(in, d.next++);
+  const uint32_t digit = ((d.next_digit << 7) & 0x80) | (b >> 1);
+  d.next_digit = b;
+  d.d = (d.d << 8) | digit;
+  d.range <<= 8;
+}
+__device__ __forceinline__ void rd_init(VDecoder& d, InStream& in) {
+  RecodedDecoder s;
+  rd_init(s, in);
+  uint32_t z;
+  asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+  d.d = s.low - s.range + z;
+  d.range = s.range + z;
+  d.next_digit = s.next_digit;
+  d.next = s.next;
+}
+__device__ __forceinline__ int rd_get(VDecoder& d, InStream& in, uint64_t r1) {
+  const uint64_t sum = d.d + r1;                 // low - r0
+  const bool c = (int32_t)vhi32(sum) >= 0;       // low >= r0 (see rd_get above)
+  const uint64_t mask = __builtin_amdgcn_ballot_w64(c);   // the decision, for the scalar side
+  d.d = c ? d.d : sum;
+  d.range = c ? r1 : d.range - r1;
+  if (wave_all(vhi32(d.range) < (1u << 19))) {   // one or two digits, as above
+    rd_consume(d, in);
+    if (wave_all(vhi32(d.range) < (1u << 23))) rd_consume(d, in);
+  }
+  return mask != 0;
 }
 
 // ------------------------------------------------------------ P-format coder (u32 / u8 digits)

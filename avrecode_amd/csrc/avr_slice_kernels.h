@@ -8,8 +8,8 @@
 namespace avr {
 
 // Single-wave slice (the generator: CABAC encode inline, no coder wave).
-template <int MODE, bool RM, bool FLD, bool P32, bool SPL>
-AVR_FI void run_slice_inline(Walker<MODE, RM, FLD, P32, SPL>& w, const avr_slice_desc* d, const uint8_t* in, uint8_t* out,
+template <int MODE, bool RM, bool FLD, bool P32, bool SPL, bool SRD>
+AVR_FI void run_slice_inline(Walker<MODE, RM, FLD, P32, SPL, SRD>& w, const avr_slice_desc* d, const uint8_t* in, uint8_t* out,
                              avr_slice_result* res) {
   begin_slice(w, d, in, out);
   profile_slice(w);
@@ -52,9 +52,11 @@ AVR_FI void parallel_slice(uint8_t* smem, const EngineTables* G, const avr_slice
                            uint8_t* out, avr_slice_result* res, uint16_t* est_g, uint32_t flags, uint32_t cell,
                            const SplitArgs* sp = nullptr) {
   const avr_slice_desc* d = &descs[s];
-  Walker<MODE, false, FLD, P32, SPL> w;
+  // MG is the persistent queue kernel: its walker keeps the scalar recoded decoder (Walker SRD)
+  typedef Walker<MODE, false, FLD, P32, SPL, MG> WalkerT;
+  WalkerT w;
   w.sh = (Shared*)smem;
-  w.ring = (typename Walker<MODE, false, FLD, P32, SPL>::ERec*)(smem + sizeof(Shared));
+  w.ring = (typename WalkerT::ERec*)(smem + sizeof(Shared));
   bool seam_end = false;
   uint32_t* piece_end = nullptr;
   if constexpr (SPL) {

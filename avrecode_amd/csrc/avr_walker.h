@@ -32,7 +32,9 @@ namespace avr {
 
 // SPL: the long-slice split's kernels (slices_split_kernel): a piece may start from a seam record
 // and stop after n macroblocks, and compress takes the cut records (avr_kernels.h SeamRec)
-template <int MODE, bool RM, bool FLD = false, bool P32 = false, bool SPL = false>
+// SRD: keep the recoded decoder's interval scalar (RecodedDecoder) where VD below would choose
+// VDecoder: the persistent queue kernel, whose registers have no room for it
+template <int MODE, bool RM, bool FLD = false, bool P32 = false, bool SPL = false, bool SRD = false>
 struct Walker {
   static constexpr bool DEC = MODE == MODE_COMPRESS || MODE == MODE_TRACE;  // CABAC decoding side
   const HotTables* T;     // LDS copy
@@ -61,7 +63,11 @@ struct Walker {
   // the model's decisions go through the reference's arithmetic_code<uint64_t, uint8_t> (both
   // models' default containers); P32 = the parallel model's optional 32-bit coder (avr_engine.h,
   // PDecoder; container tag avrecode-amd:P32)
-  typename std::conditional<P32, PDecoder, RecodedDecoder>::type rd;
+  // VD: the slice batch's resident and split kernels (frame and field walkers) keep that
+  // decoder's interval in VGPRs (avr_engine.h, VDecoder); the sequential kernels, built for a lone
+  // wave's latency with another scheduler, and the queue kernel (SRD) keep the scalar one
+  static constexpr bool VD = MODE == MODE_DECOMPRESS && !P32 && !RM && !SRD;
+  typename std::conditional<P32, PDecoder, typename std::conditional<VD, VDecoder, RecodedDecoder>::type>::type rd;
   uint64_t rng;
   // slice state
   int W, H, mb_x, mb_y, slice_type, is_b, cat_, t8mode;
@@ -1566,8 +1572,8 @@ struct Walker {
 };
 
 // ---------------------------------------------------------------------------------------
-template <int MODE, bool RM, bool FLD, bool P32, bool SPL>
-AVR_FI void init_slice_state(Walker<MODE, RM, FLD, P32, SPL>& w, const EngineTables* T) {
+template <int MODE, bool RM, bool FLD, bool P32, bool SPL, bool SRD>
+AVR_FI void init_slice_state(Walker<MODE, RM, FLD, P32, SPL, SRD>& w, const EngineTables* T) {
   const int lane = threadIdx.x, nt = blockDim.x;  // every wave of the workgroup takes part
   const avr_slice_desc* d = w.d;
   // cabac contexts: 9.3.1.1
@@ -1608,7 +1614,7 @@ AVR_FI void init_slice_state(Walker<MODE, RM, FLD, P32, SPL>& w, const EngineTab
     if (!w.mring_global)
       for (int i = lane; i < w.W * kMringDwords; i += nt) w.mring[i] = 0;
   } else {
-    for (int i = lane; i < cols * (int)sizeof(typename Walker<MODE, RM, FLD, P32, SPL>::ERec) / 4; i += nt) ring32[i] = 0;
+    for (int i = lane; i < cols * (int)sizeof(typename Walker<MODE, RM, FLD, P32, SPL, SRD>::ERec) / 4; i += nt) ring32[i] = 0;
   }
   if (lane < 2) {
     w.sh->fifo_head[lane] = 0;
@@ -1617,8 +1623,8 @@ AVR_FI void init_slice_state(Walker<MODE, RM, FLD, P32, SPL>& w, const EngineTab
   __syncthreads();
 }
 
-template <int MODE, bool RM, bool FLD, bool P32, bool SPL>
-AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
+template <int MODE, bool RM, bool FLD, bool P32, bool SPL, bool SRD>
+AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w) {
   const avr_slice_desc* d = w.d;
   w.W = d->mb_width;
   // a field picture is a picture of half the frame's rows (d->mb_height is the frame's)
@@ -1677,7 +1683,7 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
       // the upper neighbour's flags + cbp: the first dword of its edge record
       w.tf = *(const uint32_t*)&w.ring[w.mb_x];
       w.top_ok = (w.tf & F_DEC) != 0;
-    } else if (!(w.pst & Walker<MODE, RM, FLD, P32, SPL>::PST_BOT)) {
+    } else if (!(w.pst & Walker<MODE, RM, FLD, P32, SPL, SRD>::PST_BOT)) {
       w.mbaff_pair_start();
     }
     w.cf = 0;
@@ -1731,7 +1737,7 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
         }
         w.lf = w.cf;
       } else {   // the pair edge of this macroblock; the pair's records move left after its bottom
-        const int bot = (w.pst & Walker<MODE, RM, FLD, P32, SPL>::PST_BOT) != 0;
+        const int bot = (w.pst & Walker<MODE, RM, FLD, P32, SPL, SRD>::PST_BOT) != 0;
         uint32_t* e32 = (uint32_t*)&w.pair_edge(bot)[w.mb_x];
         if (lane < 23) e32[lane] = lane == 0 ? (w.cf & 0xffff017fu) : ev;
         uint32_t* pr = (uint32_t*)w.pair_rec();
@@ -1756,7 +1762,7 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
       if (!RM) w.update_prio();
     }
     // MBAFF: end_of_slice_flag follows the bottom macroblock of a pair only (7.3.4)
-    const int eos = (!(FLD && w.mbaff) || (w.pst & Walker<MODE, RM, FLD, P32, SPL>::PST_BOT)) ? w.terminate(SE_EOS) : 0;
+    const int eos = (!(FLD && w.mbaff) || (w.pst & Walker<MODE, RM, FLD, P32, SPL, SRD>::PST_BOT)) ? w.terminate(SE_EOS) : 0;
     SPROF_ENDW(7, ps7);
     if (eos) break;
     if constexpr (SPL) {   // the piece ends at the next cut (its last macroblock's end_of_slice_flag was 0)
@@ -1766,13 +1772,13 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
         break;
       }
     }
-    if (Walker<MODE, RM, FLD, P32, SPL>::DEC && w.in.limit && w.cd.next > w.in.limit + 8) { w.err = AVR_SLICE_OVERREAD; break; }
+    if (Walker<MODE, RM, FLD, P32, SPL, SRD>::DEC && w.in.limit && w.cd.next > w.in.limit + 8) { w.err = AVR_SLICE_OVERREAD; break; }
     // a parallel-model decoder reads at most 8 bytes past its stream (the recoded decoder's 63-bit
     // window; P32: 4): a damaged stream is stopped within a macroblock of running off its end
     if (MODE == MODE_DECOMPRESS && !RM && w.in.limit && w.rd.next > w.in.limit + 16) { w.err = AVR_SLICE_OVERREAD; break; }
     addr++;
-    if ((FLD && w.mbaff) && !(w.pst & Walker<MODE, RM, FLD, P32, SPL>::PST_BOT)) {
-      w.pst |= Walker<MODE, RM, FLD, P32, SPL>::PST_BOT;
+    if ((FLD && w.mbaff) && !(w.pst & Walker<MODE, RM, FLD, P32, SPL, SRD>::PST_BOT)) {
+      w.pst |= Walker<MODE, RM, FLD, P32, SPL, SRD>::PST_BOT;
       w.my++;
       continue;
     }
@@ -1791,8 +1797,8 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
 // Run f on the walker instantiation of the slice's structure: w itself for a progressive frame,
 // a field-capable copy (FLD = true, set up from w) for field pictures and MBAFF frames.
 // --------------------------------------------------------------------------- kernel bodies
-template <int MODE, bool RM, bool FLD, bool P32, bool SPL>
-AVR_FI void begin_slice(Walker<MODE, RM, FLD, P32, SPL>& w, const avr_slice_desc* d, const uint8_t* in, uint8_t* out) {
+template <int MODE, bool RM, bool FLD, bool P32, bool SPL, bool SRD>
+AVR_FI void begin_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w, const avr_slice_desc* d, const uint8_t* in, uint8_t* out) {
   w.d = d;
   w.in.g = in + d->payload_offset;
   w.in.limit = MODE == MODE_GENERATE ? 0 : d->read_limit;
@@ -1841,8 +1847,8 @@ AVR_FI void begin_slice(Walker<MODE, RM, FLD, P32, SPL>& w, const avr_slice_desc
 #endif
 }
 
-template <int MODE, bool RM, bool FLD, bool P32, bool SPL>
-AVR_FI void profile_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
+template <int MODE, bool RM, bool FLD, bool P32, bool SPL, bool SRD>
+AVR_FI void profile_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w) {
 #ifdef AVR_PROFILE
   w.bins = 0;
   const uint64_t t0 = PROF_T();
@@ -1864,8 +1870,8 @@ AVR_FI void profile_slice(Walker<MODE, RM, FLD, P32, SPL>& w) {
 
 // The walker wave of a pipelined slice: parse + model, one op per bin into the ring, OP_END at
 // the end whatever happened.  Leaves its status in LDS for finish_slice.
-template <int MODE, bool RM, bool FLD, bool P32, bool SPL>
-AVR_FI void walker_slice(Walker<MODE, RM, FLD, P32, SPL>& w, const avr_slice_desc* d, const uint8_t* in, avr_slice_result* res) {
+template <int MODE, bool RM, bool FLD, bool P32, bool SPL, bool SRD>
+AVR_FI void walker_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w, const avr_slice_desc* d, const uint8_t* in, avr_slice_result* res) {
   begin_slice(w, d, in, nullptr);
   profile_slice(w);
   if constexpr (SPL) {

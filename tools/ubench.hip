@@ -100,6 +100,40 @@ __global__ void k_branch_taken(uint64_t* out, uint32_t seed) {
   uint64_t t1 = clk();
   if (threadIdx.x == 0) { out[blockIdx.x * 2] = t1 - t0; out[blockIdx.x * 2 + 1] = x; }
 }
+// dependent v_mad_u64_u32 (one VGPR and one SGPR factor, the 64-bit accumulator carried): the
+// recoded decoder's reciprocal product on the vector unit
+__global__ void k_vmad(uint64_t* out, uint32_t seed) {
+  uint64_t x = seed + threadIdx.x;
+  const uint32_t a = threadIdx.x | 0x10001u;
+  uint64_t t0 = clk();
+  for (int i = 0; i < N; i++) {
+    asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0\n v_mad_u64_u32 %0, vcc, %1, %2, %0\n"
+                 "v_mad_u64_u32 %0, vcc, %1, %2, %0\n v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(x) : "v"(a), "s"(seed) : "vcc");
+  }
+  uint64_t t1 = clk();
+  if (threadIdx.x == 0) { out[blockIdx.x * 2] = t1 - t0; out[blockIdx.x * 2 + 1] = x; }
+}
+// a vector compare whose lane mask feeds a scalar branch (the VGPR decoder's outcome), not taken
+__global__ void k_vcc_branch(uint64_t* out, uint32_t seed) {
+  uint32_t x = seed + threadIdx.x;
+  uint64_t t0 = clk();
+  for (int i = 0; i < N; i++) {
+    asm volatile("v_cmp_eq_u32 vcc, 0x12345, %0\n s_cbranch_vccnz 1f\n v_add_u32 %0, %0, 1\n1:\n" : "+v"(x) :: "vcc");
+  }
+  uint64_t t1 = clk();
+  if (threadIdx.x == 0) { out[blockIdx.x * 2] = t1 - t0; out[blockIdx.x * 2 + 1] = x; }
+}
+// the same outcome as a 0/1 VGPR moved to the scalar unit first (what the VGPR decoder avoids)
+__global__ void k_rfl_branch(uint64_t* out, uint32_t seed) {
+  uint32_t x = seed + threadIdx.x;
+  uint64_t t0 = clk();
+  for (int i = 0; i < N; i++) {
+    asm volatile("v_cmp_eq_u32 vcc, 0x12345, %0\n v_cndmask_b32 v0, 0, 1, vcc\n s_nop 0\n v_readfirstlane_b32 s0, v0\n"
+                 "s_cmp_lg_u32 s0, 0\n s_cbranch_scc1 1f\n v_add_u32 %0, %0, 1\n1:\n" : "+v"(x) :: "vcc", "v0", "s0", "scc");
+  }
+  uint64_t t1 = clk();
+  if (threadIdx.x == 0) { out[blockIdx.x * 2] = t1 - t0; out[blockIdx.x * 2 + 1] = x; }
+}
 static uint32_t* g_tab;
 static void k_sload_launch(uint64_t* d, uint32_t seed, int blocks) {
   hipLaunchKernelGGL(k_sload, dim3(blocks), dim3(64), 0, 0, d, seed, g_tab);
@@ -112,7 +146,8 @@ int main() {
   struct K { const char* name; void (*f)(uint64_t*, uint32_t); int per; } ks[] = {
     {"salu dep (4 ops/iter)", k_salu, 4}, {"salu 4 indep chains", k_salu_indep, 4}, {"valu dep (4 ops/iter)", k_valu, 4},
     {"lds dep read + readfirstlane", k_lds, 1}, {"v_readlane dep", k_readlane, 1}, {"valu->readfirstlane->salu", k_valu_to_salu, 1},
-    {"s_cmp+s_cbranch(not taken)+s_add", k_branch, 3}, {"s_cmp+s_cbranch(taken)+s_add", k_branch_taken, 3}};
+    {"s_cmp+s_cbranch(not taken)+s_add", k_branch, 3}, {"s_cmp+s_cbranch(taken)+s_add", k_branch_taken, 3}, {"v_mad_u64_u32 dep (4 ops/iter)", k_vmad, 4},
+    {"v_cmp+s_cbranch_vccnz+v_add", k_vcc_branch, 3}, {"v_cmp+cndmask+readfirstlane+s_cmp+branch+v_add", k_rfl_branch, 6}};
   setvbuf(stdout, nullptr, _IONBF, 0);
   {
     uint32_t ht[256];
