@@ -16,6 +16,19 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+// Branch-layout hints for the walkers' hot loops: the rare side of a per-bin branch (a refill, a
+// flush, a fallback, an error) goes out of line, so that the common path falls through instead of
+// jumping over it (a taken branch costs a lone wave about twice a not-taken one).
+// -DAVR_NO_LAYOUT_HINTS makes them plain conditions for a translation unit (a kernel family whose
+// measurements or register figures lose with them).
+#ifdef AVR_NO_LAYOUT_HINTS
+#define AVR_LIKELY(x) (x)
+#define AVR_UNLIKELY(x) (x)
+#else
+#define AVR_LIKELY(x) (__builtin_expect(!!(x), 1))
+#define AVR_UNLIKELY(x) (__builtin_expect(!!(x), 0))
+#endif
+
 namespace avr {
 
 constexpr int kStage = 1024;  // bytes per LDS staging window
@@ -185,7 +198,7 @@ struct CabacDecoder {
 };
 
 __device__ __forceinline__ void cd_refill(CabacDecoder& d, InStream& in) {
-  if (d.k < 8) {
+  if (AVR_UNLIKELY(d.k < 8)) {   // once per 16 bits
     d.low = (d.low << 16) | (in_be32(in, d.next) >> 16);
     d.next += 2;
     d.k += 16;
@@ -566,9 +579,9 @@ __device__ __forceinline__ int rd_get(RecodedDecoder& d, InStream& in, uint64_t 
   // below min_range (2^51) the encoder shifts until range >= 2^55 (re_put).  A decision starts
   // from range >= 2^51 and both outcomes keep at least range / 97 > 2^44 (pos, neg >= 1,
   // pos + neg <= 97), never 0: one or two digits, straight-line instead of a loop
-  if (hi32(d.range) < (1u << 19)) {
+  if (AVR_UNLIKELY(hi32(d.range) < (1u << 19))) {
     rd_consume(d, in);
-    if (hi32(d.range) < (1u << 23)) rd_consume(d, in);
+    if (AVR_UNLIKELY(hi32(d.range) < (1u << 23))) rd_consume(d, in);
   }
   return bin;
 }
@@ -614,9 +627,9 @@ __device__ __forceinline__ int rd_get(VDecoder& d, InStream& in, uint64_t r1) {
   const uint64_t mask = __builtin_amdgcn_ballot_w64(c);   // the decision, for the scalar side
   d.d = c ? d.d : sum;
   d.range = c ? r1 : d.range - r1;
-  if (wave_all(vhi32(d.range) < (1u << 19))) {   // one or two digits, as above
+  if (AVR_UNLIKELY(wave_all(vhi32(d.range) < (1u << 19)))) {   // one or two digits, as above
     rd_consume(d, in);
-    if (wave_all(vhi32(d.range) < (1u << 23))) rd_consume(d, in);
+    if (AVR_UNLIKELY(wave_all(vhi32(d.range) < (1u << 23)))) rd_consume(d, in);
   }
   return mask != 0;
 }

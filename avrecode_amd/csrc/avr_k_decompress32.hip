@@ -1,6 +1,9 @@
 // parallel slice kernel, MODE_DECOMPRESS, P32 coder: the parallel model's optional 32-bit container coder
 // (avr_engine.h PEncoder / PDecoder, tag avrecode-amd:P32; one translation unit per kernel, see
 // avr_walker.h).
+// The layout hints (avr_engine.h) are off here: with them the persistent field kernel of this unit
+// went from 16 to 17 VGPR spills.
+#define AVR_NO_LAYOUT_HINTS
 #include "avr_slice_kernels.h"
 
 namespace avr {

@@ -1,4 +1,7 @@
 // sequential slice kernel, MODE_DECOMPRESS (one translation unit per kernel: see avr_walker.h).
+// the layout hints (avr_engine.h) are off here: this kernel family's A/B (the reference model's
+// whole-file decompress) has not been run with them
+#define AVR_NO_LAYOUT_HINTS
 #include "avr_prof.h"
 #include "avr_slice_kernels.h"
 

@@ -1,4 +1,6 @@
 // parallel slice kernel, MODE_TRACE (decode-only bin trace for the hooks layer) (one translation unit per kernel: see avr_walker.h).
+// the layout hints (avr_engine.h) are off here: no A/B of this unit's kernels has been run with them
+#define AVR_NO_LAYOUT_HINTS
 #include "avr_prof.h"
 #include "avr_slice_kernels.h"
 

@@ -92,6 +92,12 @@ hipError_t launch_parallel_compress(const EngineTables* T, const avr_slice_desc*
                                     const int* order, uint32_t flags, hipStream_t stream,
                                     uint32_t* qhead = nullptr, int qgrid = 0, int qgrid_fld = 0,
                                     size_t lds_fld = 0, const FieldLane* lane = nullptr);
+// the persistent queue launches of launch_parallel_compress (qhead != nullptr), a unit of their own
+// (avr_k_compress_queue.hip): built without the layout hints, which cost these kernels a VGPR spill
+hipError_t launch_queue_compress(const EngineTables* T, const avr_slice_desc* descs, int n, size_t lds,
+                                 const uint8_t* in, uint8_t* out, avr_slice_result* res, uint16_t* est,
+                                 const int* order, uint32_t flags, hipStream_t stream, uint32_t* qhead, int qgrid,
+                                 int qgrid_fld, size_t lds_fld, const FieldLane* lane);
 hipError_t launch_parallel_decompress(const EngineTables* T, const avr_slice_desc* descs, int n, size_t lds,
                                       const uint8_t* in, uint8_t* out, avr_slice_result* res, uint16_t* est,
                                       const int* order, uint32_t flags, hipStream_t stream,

@@ -231,13 +231,18 @@ struct QueueLaunch {
   size_t lds_fld = 0;           // LDS of the field kernel (0: the progressive kernel's)
   const FieldLane* lane = nullptr;
 };
-template <int MODE, bool P32>
+// KINDS: the kernels a unit instantiates -- both, or the resident ones only with the persistent ones
+// in a unit of their own (a unit is what the layout hints' switch covers, avr_engine.h); a launch of
+// the kind the unit does not hold is refused.
+enum { kLaunchBoth = 0, kLaunchResident = 1, kLaunchQueue = 2 };
+template <int MODE, bool P32, int KINDS = kLaunchBoth>
 inline hipError_t launch_parallel(const EngineTables* T, const avr_slice_desc* descs, int n, size_t lds,
                                   const uint8_t* in, uint8_t* out, avr_slice_result* res, uint16_t* est,
                                   const int* order, uint32_t flags, hipStream_t stream, QueueLaunch q = QueueLaunch()) {
   const size_t lds_fld = q.lds_fld ? q.lds_fld : lds;
   const bool fields = (flags & kFlagFields) != 0;
   const bool side = fields && q.lane && q.lane->stream;
+  if ((KINDS == kLaunchResident && q.head) || (KINDS == kLaunchQueue && !q.head)) return hipErrorInvalidValue;
   if (hipError_t e = reset_cu_board(stream); e != hipSuccess) return e;
   hipStream_t fs = stream;
   if (side) {
@@ -245,24 +250,30 @@ inline hipError_t launch_parallel(const EngineTables* T, const avr_slice_desc* d
     if (hipError_t e = hipEventRecord(q.lane->fork, stream); e != hipSuccess) return e;
     if (hipError_t e = hipStreamWaitEvent(fs, q.lane->fork, 0); e != hipSuccess) return e;
   }
-  if (q.head)
-    hipLaunchKernelGGL((slices_queue_kernel<MODE, false, P32>), dim3(q.grid), dim3(slice_threads<MODE>()), lds, stream,
-                       T, descs, n, in, out, res, est, order, q.head, flags);
-  else
-    hipLaunchKernelGGL((slices_parallel_kernel<MODE, false, P32>), dim3(n), dim3(slice_threads<MODE>()), lds, stream,
-                       T, descs, n, in, out, res, est, order, flags);
+  if (q.head) {
+    if constexpr (KINDS != kLaunchResident)
+      hipLaunchKernelGGL((slices_queue_kernel<MODE, false, P32>), dim3(q.grid), dim3(slice_threads<MODE>()), lds, stream,
+                         T, descs, n, in, out, res, est, order, q.head, flags);
+  } else {
+    if constexpr (KINDS != kLaunchQueue)
+      hipLaunchKernelGGL((slices_parallel_kernel<MODE, false, P32>), dim3(n), dim3(slice_threads<MODE>()), lds, stream,
+                         T, descs, n, in, out, res, est, order, flags);
+  }
   if (fields) {
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     if (!side)
       if (hipError_t e = reset_cu_board(stream); e != hipSuccess) return e;
     // beside the progressive kernel, the persistent field workgroups take the scratches after its grid
     uint16_t* est_f = side && q.head ? est + (size_t)q.grid * kEstGlobal : est;
-    if (q.head)
-      hipLaunchKernelGGL((slices_queue_kernel<MODE, true, P32>), dim3(q.grid_fld), dim3(slice_threads<MODE>()), lds_fld,
-                         fs, T, descs, n, in, out, res, est_f, order, q.head + 1, flags & ~kFlagMringGlobal);
-    else
-      hipLaunchKernelGGL((slices_parallel_kernel<MODE, true, P32>), dim3(n), dim3(slice_threads<MODE>()), lds_fld,
-                         fs, T, descs, n, in, out, res, est_f, order, flags & ~kFlagMringGlobal);
+    if (q.head) {
+      if constexpr (KINDS != kLaunchResident)
+        hipLaunchKernelGGL((slices_queue_kernel<MODE, true, P32>), dim3(q.grid_fld), dim3(slice_threads<MODE>()), lds_fld,
+                           fs, T, descs, n, in, out, res, est_f, order, q.head + 1, flags & ~kFlagMringGlobal);
+    } else {
+      if constexpr (KINDS != kLaunchQueue)
+        hipLaunchKernelGGL((slices_parallel_kernel<MODE, true, P32>), dim3(n), dim3(slice_threads<MODE>()), lds_fld,
+                           fs, T, descs, n, in, out, res, est_f, order, flags & ~kFlagMringGlobal);
+    }
     if (side) {
       if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
       if (hipError_t e = hipEventRecord(q.lane->join, fs); e != hipSuccess) return e;

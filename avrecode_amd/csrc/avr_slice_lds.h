@@ -326,7 +326,7 @@ struct RingOutT {
   // a staged run of ops on either ring kind (stage, then flush_stage before any other push)
   AVR_FI void stage(uint32_t op) {
     stage_v = __lane_id() == stage_n ? op : stage_v;
-    if (++stage_n == 64) flush_stage();
+    if (AVR_UNLIKELY(++stage_n == 64)) flush_stage();
   }
   AVR_FI void flush_stage() {
     if (stage_n) {
@@ -338,10 +338,10 @@ struct RingOutT {
   AVR_FI void push(uint32_t op) {
     if (STAGED) {
       stage_v = __lane_id() == stage_n ? op : stage_v;
-      if (++stage_n == 64) flush();
+      if (AVR_UNLIKELY(++stage_n == 64)) flush();
       return;
     }
-    if (room == 0) {
+    if (AVR_UNLIKELY(room == 0)) {
       st_volatile(&sh->fifo_head[r], head);
 #ifdef AVR_PROFILE
       const uint64_t tw = PROF_T();
@@ -358,11 +358,11 @@ struct RingOutT {
     sh->fifo[r][head & (kFifo - 1)] = op;
     head++;
     room--;
-    if ((head & 31) == 0) st_volatile(&sh->fifo_head[r], head);
+    if (AVR_UNLIKELY((head & 31) == 0)) st_volatile(&sh->fifo_head[r], head);
   }
   // n <= 64 ops at once, op k in lane k (one vector store)
   AVR_FI void push_v_raw(uint32_t op_v, uint32_t n) {
-    if (room < n) {
+    if (AVR_UNLIKELY(room < n)) {
       st_volatile(&sh->fifo_head[r], head);
 #ifdef AVR_PROFILE
       const uint64_t tw = PROF_T();
@@ -416,7 +416,7 @@ AVR_FI uint32_t est_load(Shared* sh, const uint16_t* est_g, uint32_t idx, uint32
   if (lane == 0) atomicAdd(&avr_prof[22], 1ull);
   if (lane == 0 && !hit && !__ballot(ent == 0)) atomicAdd(&avr_prof[23], 1ull);
 #endif
-  if (hit) {
+  if (AVR_LIKELY(hit != 0)) {
     // the entry's upper half is the slot's tag word already
     const uint32_t j = (uint32_t)__builtin_ctzll(hit);
     const uint32_t ej = __builtin_amdgcn_readlane(ent, j);
@@ -424,7 +424,7 @@ AVR_FI uint32_t est_load(Shared* sh, const uint16_t* est_g, uint32_t idx, uint32
     return ej & 0xffff;
   }
   const uint64_t free_v = __ballot(ent == 0);
-  if (free_v) {
+  if (AVR_LIKELY(free_v != 0)) {   // of the misses: a new key (the HBM table holds 0.4 % of lookups)
     const uint32_t j = (uint32_t)__builtin_ctzll(free_v);
     *slot = (0x8000u | j << 7 | tag) << 16 | (home + j);
     // a caller that defers its store claims the slot now (a later key of the window must not take it)
@@ -437,7 +437,7 @@ AVR_FI uint32_t est_load(Shared* sh, const uint16_t* est_g, uint32_t idx, uint32
   return raw & (kEstWritten - 1);
 }
 AVR_FI void est_store(Shared* sh, uint16_t* est_g, uint32_t idx, uint32_t slot, uint32_t e) {
-  if (slot >> 31) {
+  if (AVR_LIKELY(slot >> 31)) {
     sh->etab[slot & 0xffff] = (slot & 0xffff0000u) | e;
   } else if (__lane_id() == 0) {
     est_g[idx] = (uint16_t)(e | kEstWritten);

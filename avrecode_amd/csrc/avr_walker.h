@@ -24,6 +24,14 @@
 
 #include "avr_slice_lds.h"
 
+// The rare exits of the macroblock loop and of the block list (used where MODE is a template
+// parameter): hinted in the decompress walkers only.  With them the batch decompress kernel measured
+// 1.4 % faster and the compress kernel 1.6 % slower than without.  Macros, not functions:
+// __builtin_expect has to stand in the branch's own condition.  They read the template parameter MODE
+// of the scope they are used in and are this header's alone (#undef at its end).
+#define AVR_MB_LIKELY(x) (MODE == MODE_DECOMPRESS ? AVR_LIKELY(x) : (x))
+#define AVR_MB_UNLIKELY(x) (MODE == MODE_DECOMPRESS ? AVR_UNLIKELY(x) : (x))
+
 namespace avr {
 
 // FLD: field-coded slices (PAFF, MBAFF) -- a second instantiation (kernels of their own, launched
@@ -946,7 +954,7 @@ struct Walker {
           uint32_t e = est_load(sh, est_g, idx, &slot, defer);
           int b = rdec(e);
           const uint32_t ne = est_update(e, b, 0x50);
-          if (defer && (slot >> 31)) {
+          if (defer && AVR_LIKELY(slot >> 31)) {
             dslot_v = wlane(dslot_v, (uint32_t)pos, slot);
             de_v = wlane(de_v, (uint32_t)pos, ne);
           } else {
@@ -1005,7 +1013,7 @@ struct Walker {
 
   // residual_block_cabac() of one block; p/x4/y4 locate it in the walker's nnz grid
   AVR_FI void residual_block(int cat, int n, int max, int is_dc, int c422, int p, int pw, int x4, int y4) {
-    if (err) return;
+    if (AVR_MB_UNLIKELY(err)) return;
     MbRec& cur = sh->cur;
     int coded = 1;
     if (max != 64 || cat_ == 3) {
@@ -1199,7 +1207,7 @@ struct Walker {
             }
     }
     PROF_BEGIN(t2);
-    for (int j = 0; j < nb && !err; j++) {
+    for (int j = 0; j < nb && AVR_MB_LIKELY(!err); j++) {
       const uint32_t b = sh->blk[j];
       residual_block(b & 15, (b >> 4) & 63, (b >> 10) & 127, (b >> 17) & 1, (b >> 18) & 1, (b >> 19) & 3,
                      (b >> 21) & 7, (b >> 24) & 3, (b >> 26) & 3);
@@ -1673,9 +1681,9 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w) {
     w.edge_src = (uint32_t)src;
   }
   for (;;) {
-    if (addr >= npic) { w.err = AVR_SLICE_BAD_MB_ADDR; break; }
+    if (AVR_MB_UNLIKELY(addr >= npic)) { w.err = AVR_SLICE_BAD_MB_ADDR; break; }
     if constexpr (SPL && MODE == MODE_COMPRESS) {
-      if (w.snap && w.mb_x == 0 && w.mbs_done > 0) w.seam_cut(addr);
+      if (AVR_MB_UNLIKELY(w.snap && w.mb_x == 0 && w.mbs_done > 0)) w.seam_cut(addr);
     }
     PROF_BEGINW(ps0);
     if (!(FLD && w.mbaff)) {
@@ -1701,7 +1709,7 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w) {
     w.decode_mb();
     PROF_ENDW(1, t1);
     PROF_BEGINW(t7);
-    if (w.err) break;
+    if (AVR_MB_UNLIKELY(w.err)) break;
     w.cf |= F_DEC;
     w.mbs_done++;
     w.last_mb = addr + 1 >= npic;
@@ -1764,18 +1772,18 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w) {
     // MBAFF: end_of_slice_flag follows the bottom macroblock of a pair only (7.3.4)
     const int eos = (!(FLD && w.mbaff) || (w.pst & Walker<MODE, RM, FLD, P32, SPL, SRD>::PST_BOT)) ? w.terminate(SE_EOS) : 0;
     SPROF_ENDW(7, ps7);
-    if (eos) break;
+    if (AVR_MB_UNLIKELY(eos)) break;
     if constexpr (SPL) {   // the piece ends at the next cut (its last macroblock's end_of_slice_flag was 0)
-      if (w.piece_mbs && (uint32_t)w.mbs_done >= w.piece_mbs) {
+      if (AVR_MB_UNLIKELY(w.piece_mbs && (uint32_t)w.mbs_done >= w.piece_mbs)) {
         w.finished = 1;
         w.cut = 1;
         break;
       }
     }
-    if (Walker<MODE, RM, FLD, P32, SPL, SRD>::DEC && w.in.limit && w.cd.next > w.in.limit + 8) { w.err = AVR_SLICE_OVERREAD; break; }
+    if (Walker<MODE, RM, FLD, P32, SPL, SRD>::DEC && AVR_MB_UNLIKELY(w.in.limit && w.cd.next > w.in.limit + 8)) { w.err = AVR_SLICE_OVERREAD; break; }
     // a parallel-model decoder reads at most 8 bytes past its stream (the recoded decoder's 63-bit
     // window; P32: 4): a damaged stream is stopped within a macroblock of running off its end
-    if (MODE == MODE_DECOMPRESS && !RM && w.in.limit && w.rd.next > w.in.limit + 16) { w.err = AVR_SLICE_OVERREAD; break; }
+    if (MODE == MODE_DECOMPRESS && !RM && AVR_MB_UNLIKELY(w.in.limit && w.rd.next > w.in.limit + 16)) { w.err = AVR_SLICE_OVERREAD; break; }
     addr++;
     if ((FLD && w.mbaff) && !(w.pst & Walker<MODE, RM, FLD, P32, SPL, SRD>::PST_BOT)) {
       w.pst |= Walker<MODE, RM, FLD, P32, SPL, SRD>::PST_BOT;
@@ -1913,3 +1921,6 @@ AVR_FI void walker_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w, const avr_slic
 }
 
 }  // namespace avr
+
+#undef AVR_MB_LIKELY
+#undef AVR_MB_UNLIKELY

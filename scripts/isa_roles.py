@@ -5,15 +5,25 @@ walker's instructions per bin by role).  Input: device assembly with line tables
       avrecode_amd/csrc/avr_k_decompress.hip -o /tmp/dec_g.s
   python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --anchor LINE CALLER
   python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --loop 4887
+  python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --edges 4887
+  python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --path 4887,4889,4893,4887
 
 (LINE: avr_walker.h's line of `int b = rdec(e);` in sig_map's decompress map_loop, CALLER: the line
-of the map_loop(...<int, 0>) call below it; --csrc DIR when the listing is of another tree's sources.)
+of the map_loop(...<int, 0>) call below it; --csrc DIR when the listing is of another tree's sources.
+The compress kernel, 'slices_parallel_kernelILi0ELb0ELb0E' of avr_k_compress.hip, the same way: LINE
+the `if (rdecide(sc)) {` of sig_map's first map_loop, or the `int b = rdecide(32 + i0);` of
+residual_block's staged level loop with CALLER 0 -- any caller.)
 
 Each instruction carries the inlining chain of its .loc comment; its role is the first frame of the
 chain that falls in a known range of avr_walker.h / avr_slice_lds.h / avr_engine.h (ROLES below).  --anchor LINE CALLER
 lists the innermost loops holding an instruction inlined from LINE through CALLER; --loop HDR prints
-that loop's blocks (not those of loops nested in it) with their roles and the per-role sums.  The
-code generation only: which blocks a bin runs is read off the listing."""
+that loop's blocks (not those of loops nested in it) with their roles and the per-role sums.
+--edges HDR prints the layout of that loop: its blocks in listing order, each with its branch
+instructions, their targets, and the block it falls through to, so that the branches a path takes can
+be told from those it merely passes; --path B1,B2,... walks a stated path (block numbers, in the order
+a bin runs them) and counts its instructions, the branch instructions it executes and how many of
+them are taken.  The code generation only: which blocks a bin runs is read off the listing
+(DESIGN.md §4.3, §4.4)."""
 import argparse
 import collections
 import os
@@ -37,13 +47,21 @@ FUNCS = [
     (L, "flush_stage", "op_emit"), (L, "push", "op_emit"), (L, "push_v_raw", "op_emit"), (L, "op_map", "op_emit"),
     (L, "op_level", "op_emit"), (W, "publish", "op_emit"), (W, "push", "op_emit"), (W, "push_v", "op_emit"),
     (W, "wlane", "est_store"), (L, "wave_sync", "sync"),
+    # the compress walker: the CABAC decoding engine is its decision, model ops its emission
+    (E, "cd_decide", "decision"), (E, "cd_bypass", "decision"), (E, "cd_refill", "decision"), (E, "in_be32", "decision"),
+    (E, "vtab_rec", "decision"), (E, "cabac_lps", "decision"), (E, "cabac_next", "decision"),
+    (W, "rdecide", "decision"), (W, "crec", "decision"), (L, "op_model", "op_emit"),
 ]
 STATEMENTS = [(r"est_load\(", "est_lookup"), (r"rdec(_lane|_bypass)?\(", "decision"), (r"est_update\(", "est_update"),
-              (r"wlane\(|est_store\(|sh->etab", "est_store"), (r"push\(|mk \|=|mk = 0", "op_emit"),
+              (r"wlane\(|est_store\(|sh->etab", "est_store"), (r"rdecide\(|lbyp\(\)|cd_bypass\(", "decision"),
+              (r"push\(|mk \|=|mk = 0|ring0\.|sigmask \|=", "op_emit"),
               (r"\b(sc|lc|zo|i0|i1)\b.*=|const int idx = ", "context"), (r".", "bookkeeping")]
-# the decompress significance map's loops (the second map_loop of sig_map) and the level loop
+# the decompress significance map's loops (the second map_loop of sig_map) and the level loop, then
+# the compress side's: the first map_loop of sig_map and residual_block's staged level loop
 REGIONS = [("const uint32_t sop = opaque_u32", "auto map_loop = [&](auto K) {"),
-           ("if constexpr (MODE == MODE_DECOMPRESS && !FLD) {", None)]
+           ("if constexpr (MODE == MODE_DECOMPRESS && !FLD) {", None),
+           ("uint64_t sigmask = 0;", "auto map_loop = [&](auto K) {"),
+           ("} else if constexpr (MODE == MODE_COMPRESS && kStageLevels) {", None)]
 
 
 def block_end(lines, i):
@@ -128,8 +146,26 @@ def parse(path, kernel):
             continue
         if not s or s.startswith(".") or s.startswith(";") or cur is None:
             continue
-        cur["ins"].append((s.split()[0], chain))
+        cur["ins"].append((s.split()[0], chain, s.split(";")[0].strip()))
     return blocks
+
+
+def branches(b):
+    """(mnemonic, target block number) of the block's branch instructions, in order."""
+    out = []
+    for mn, _, text in b["ins"]:
+        if mn.startswith("s_cbranch") or mn == "s_branch":
+            m = re.search(r"\.LBB\d+_(\d+)", text)
+            out.append((mn, m.group(1) if m else "?"))
+    return out
+
+
+def fall_through(blocks, i):
+    """The block that follows in the listing, unless this one ends in an unconditional transfer."""
+    last = blocks[i]["ins"][-1][0] if blocks[i]["ins"] else ""
+    if last in ("s_branch", "s_endpgm", "s_setpc_b64") or i + 1 >= len(blocks):
+        return None
+    return blocks[i + 1]["id"]
 
 
 def main():
@@ -138,6 +174,8 @@ def main():
     ap.add_argument("kernel")
     ap.add_argument("--anchor", type=int, nargs=2)
     ap.add_argument("--loop")
+    ap.add_argument("--edges", metavar="HDR", help="the loop's layout: each block's branches, targets and fall-through")
+    ap.add_argument("--path", help="B1,B2,...: instructions, branch instructions and taken branches along these blocks")
     ap.add_argument("--csrc", default=CSRC, help="the sources the listing was compiled from (default: this tree's)")
     a = ap.parse_args()
     ROLES.extend(build_roles(a.csrc))
@@ -147,9 +185,9 @@ def main():
         line, caller = a.anchor
         hits = collections.Counter()
         for b in blocks:
-            for _, ch in b["ins"]:
+            for _, ch, _ in b["ins"]:
                 ls = [l for f, l in ch if f == W]
-                if line in ls and caller in ls:
+                if line in ls and (caller in ls or not caller):
                     hits[b["hdr"]] += 1
                     break
         for h, n in hits.most_common():
@@ -159,11 +197,47 @@ def main():
         for b in blocks:
             if b["hdr"] != a.loop:
                 continue
-            c = collections.Counter(role(ch) for _, ch in b["ins"])
+            c = collections.Counter(role(ch) for _, ch, _ in b["ins"])
             tot.update(c)
-            print(f"{b['label']:14s} {len(b['ins']):3d}  " + " ".join(mn for mn, _ in b["ins"]))
+            print(f"{b['label']:14s} {len(b['ins']):3d}  " + " ".join(mn for mn, _, _ in b["ins"]))
             print(" " * 20 + ", ".join(f"{k} {v}" for k, v in c.most_common()))
         print("loop total:", dict(tot.most_common()))
+    if a.edges:
+        for i, b in enumerate(blocks):
+            if b["hdr"] != a.edges:
+                continue
+            br, ft = branches(b), fall_through(blocks, i)
+            roles = collections.Counter(role(ch) for _, ch, _ in b["ins"])
+            print(f"{b['id']:>6s} {len(b['ins']):3d}  " + ("; ".join(f"{mn} -> {t}" for mn, t in br) or "-") +
+                  f"  | falls through to {ft if ft else '(none)'}" + f"  | {roles.most_common(1)[0][0] if roles else ''}")
+    if a.path:
+        ids = a.path.split(",")
+        at = {b["id"]: i for i, b in enumerate(blocks)}
+        n_ins = n_br = n_taken = 0
+        tot = collections.Counter()
+        for k, x in enumerate(ids):
+            b = blocks[at[x]]
+            br, ft = branches(b), fall_through(blocks, at[x])
+            nxt = ids[k + 1] if k + 1 < len(ids) else None
+            if nxt is None and k and x == ids[0]:   # back at the loop's header: counted once
+                break
+            n_ins += len(b["ins"])
+            tot.update(role(ch) for _, ch, _ in b["ins"])
+            if nxt is None:
+                break
+            # the branches are executed in order until one is taken; the fall-through executes them all
+            hit = next((j for j, (_, t) in enumerate(br) if t == nxt), None)
+            if hit is None:
+                if ft != nxt:
+                    sys.exit(f"block {x} has no edge to {nxt} (branches {br}, falls through to {ft})")
+                n_br += len(br)
+                print(f"{x:>6s} -> {nxt:>6s}  falls through, past {len(br)} branch instruction(s)")
+            else:
+                n_br += hit + 1
+                n_taken += 1
+                print(f"{x:>6s} -> {nxt:>6s}  TAKEN {br[hit][0]}" + (f", past {hit} not taken" if hit else ""))
+        print(f"path: {n_ins} instructions, {n_br} branch instructions executed, {n_taken} taken")
+        print("path roles:", dict(tot.most_common()))
 
 
 if __name__ == "__main__":

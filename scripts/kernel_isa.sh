@@ -5,7 +5,7 @@ cd "$(dirname "$0")/../avrecode_amd"
 mkdir -p /tmp/avr_isa
 TUS=${@:-avr_k_compress avr_k_decompress avr_k_generate avr_k_seq_compress avr_k_seq_decompress}
 for t in $TUS; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S csrc/$t.hip -o /tmp/avr_isa/$t.s 2>/dev/null &
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC --cuda-device-only -S csrc/$t.hip -o /tmp/avr_isa/$t.s 2>/dev/null &
 done
 wait
 for t in $TUS; do
