@@ -32,6 +32,12 @@
 #define AVR_MB_LIKELY(x) (MODE == MODE_DECOMPRESS ? AVR_LIKELY(x) : (x))
 #define AVR_MB_UNLIKELY(x) (MODE == MODE_DECOMPRESS ? AVR_UNLIKELY(x) : (x))
 
+// Components of the frame walkers' block state kept in VGPR lanes (Walker::BS, 0-3; 0: the LDS
+// records).  A build knob only so that each component can be measured alone.
+#ifndef AVR_BLOCK_STATE
+#define AVR_BLOCK_STATE 3
+#endif
+
 namespace avr {
 
 // FLD: field-coded slices (PAFF, MBAFF) -- a second instantiation (kernels of their own, launched
@@ -100,6 +106,38 @@ struct Walker {
   uint32_t cf, lf, tf;
   static constexpr uint32_t CF_8X8 = 0x80;
   uint32_t edge_src;      // lane j < 23: the MbRec dword that becomes EdgeRec dword j (set per slice)
+
+  // ------------------------------------------------------------------ block state in VGPR lanes
+  // The frame walkers of the parallel model keep what a residual block needs before its first bin
+  // in VGPR lanes, so that a block starts on v_readlane instead of a chain of LDS round trips
+  // (DESIGN §4.5).  BS counts the components in use, each on top of the one before:
+  //   1  blk_v:  the macroblock's block list, lane j = record j in bitstream order (list_build)
+  //   2  nz_v / nzn_v: the parse's nnz grid and its neighbours (coded_block_flag contexts)
+  //   3  mz_v / mzl_v / mzt_v: the model's nnz (the NZ tree's neighbours), blk2_v bits 16-31
+  // (A fourth, the ctxBlockCat bases in two registers with lane = cat, measured slower in the
+  // decompress kernel and is not kept: DESIGN §4.5.)
+  // The field / MBAFF and the R-mode walkers keep the LDS records (BS = 0).  So do the persistent
+  // queue kernels (SRD) and the split kernels (SPL): with these registers their listings spill more
+  // VGPRs than without, and a spilling kernel is not shipped.
+  static constexpr int BS = (!RM && !FLD && !SPL && !SRD) ? AVR_BLOCK_STATE : 0;
+  // blk_v, lane j < nb: cat bits 0-3, n (scan8 index) 4-9, max 10-16, is_dc 17, c422 18, then the
+  // block's lane g = p * 16 + y4 * 4 + x4 of the nnz grid as x4 19-20, y4 21-22, p 23-24, and pw 25-27.
+  // blk2_v, lane j < nb: the lanes of the block's left (bits 0-5) and upper (8-13) nnz neighbour
+  // with bit 6 / 14 set when that lane is nzn_v's, not nz_v's; the block's nb_left / nb_up table
+  // bytes in bits 16-23 / 24-31 (0 for the DC blocks, n >= 48, which do not use them).
+  // residual() reads lanes j < nb only, the lanes list_build has just written.
+  uint32_t blk_v, blk2_v;
+  // nz_v, lane g < 48: MbRec::nnz[p][y4 * 4 + x4] of the current macroblock (0 at its start).  Read
+  // at g - 1 (x4 > 0) and g - 4 (y4 > 0) of a block's own g and stored by lane to sh->cur.nnz at the
+  // macroblock's end: lanes 48-63 are never touched.
+  // nzn_v, lane p * 8 + y4: what nnz_left gives for row y4 of plane p at x4 = 0; lane p * 8 + 4 + x4:
+  // what nnz_top gives for column x4 at y4 = 0 (edge_load: unavailable defaults, the plane's width
+  // and the 4:4:4 override folded in).  Lanes 0-23 are all loaded; lanes 24-63 are never read.
+  uint32_t nz_v, nzn_v;
+  // mz_v, lane n < 52: MbRec::mnnz[n] of the current macroblock; mzl_v, lane idx < 52: mnnz_left(idx);
+  // mzt_v, lane idx < 52: mnnz_top(idx) -- the upper macroblock's kept model bytes (kMringUsed; the
+  // other lanes hold 0 and, like the bytes the row does not keep, are never read).  Lanes 52-63: 0.
+  uint32_t mz_v, mzl_v, mzt_v;
   int err, finished;
   uint32_t bins;
   int target_mbs, mbs_done, last_mb;
@@ -767,7 +805,8 @@ struct Walker {
   }
 
   // finished_queueing (recode.cpp:845-930): the 2/4/6 nnz bits, LSB first
-  AVR_FI int nz_bits(int cat, int n, int max, int is_dc, int c422, int count) {
+  // b2: the block's blk2_v record (BS >= 3: its nb_left / nb_up bytes)
+  AVR_FI int nz_bits(int cat, int n, int max, int is_dc, int c422, int count, uint32_t b2 = 0) {
     const int bits = max > 16 ? 6 : max > 4 ? 4 : 2;
     // the R-mode compress's count pass (rscan without a sink) needs the number of ops only: skip
     // the neighbours' frame loads (measured: R-mode compress -2 % clip, -4 % cockatoo)
@@ -776,6 +815,25 @@ struct Walker {
       return count & ((1 << bits) - 1);
     }
     int has_left, has_above, lv = 0, av = 0;
+    if constexpr (BS >= 3) {
+      // the same rules on registers: no LDS load before the probe.  A value read for a neighbour
+      // that does not exist (mb_x == 0, row 0) is 0 as in the LDS version: mzl_v / mzt_v hold 0
+      // where left_ok / top_ok fail, and has_left alone selects lb's third value.
+      if (n >= 48) {
+        has_left = mb_x > 0;
+        lv = (int)__builtin_amdgcn_readlane(mzl_v, (uint32_t)n);
+        av = (int)__builtin_amdgcn_readlane(mzt_v, (uint32_t)n);
+      } else {
+        const uint32_t L = (b2 >> 16) & 0xff, U = b2 >> 24;
+        uint32_t li = L & 63, ui = U & 63;
+        if (max >= 32) { li &= ~3u; ui &= ~3u; }
+        has_left = !(L & 128) || mb_x > 0;
+        const uint32_t lc = __builtin_amdgcn_readlane(mz_v, li), ln = __builtin_amdgcn_readlane(mzl_v, li);
+        const uint32_t uc = __builtin_amdgcn_readlane(mz_v, ui), un = __builtin_amdgcn_readlane(mzt_v, ui);
+        lv = (int)((L & 128) ? ln : lc);
+        av = (int)((U & 128) ? un : uc);   // row 0 has no top_ok: un = 0, as av must be without has_above
+      }
+    } else
     if (n >= 48) {
       has_left = mb_x > 0;
       has_above = mrow() > 0;
@@ -856,14 +914,15 @@ struct Walker {
     return so_far;
   }
 
-  AVR_FI int sig_est_index(int cat, int max, int is_dc, int c422, int zz, int nnz_m, int obs) const {
-    if (max == 64) return T->sig_est_base[cat] + (T->sig8x8[zz] * 64 + nnz_m) * 64 + obs;
+  AVR_FI int sig_est_index(int seb, int max, int is_dc, int c422, int zz, int nnz_m, int obs) const {
+    if (max == 64) return seb + (T->sig8x8[zz] * 64 + nnz_m) * 64 + obs;
     int zo = (is_dc && c422) ? (zz < 2 ? 0 : zz < 4 ? 1 : 2) : zz;
-    return T->sig_est_base[cat] + (zo * 16 + nnz_m) * 16 + obs;
+    return seb + (zo * 16 + nnz_m) * 16 + obs;
   }
 
-  // significance map of one residual block; returns the coefficient count
-  AVR_FI int sig_map(int cat, int n, int max, int is_dc, int c422) {
+  // significance map of one residual block; returns the coefficient count (b2: the block's blk2_v
+  // record, see BS)
+  AVR_FI int sig_map(int cat, int n, int max, int is_dc, int c422, uint32_t b2 = 0) {
     const int numc8x8 = cat_ == 2 ? 2 : 1;
     const int sb = T->sig_base[cat], lb = T->last_base[cat], seb = (int)opaque_u32((uint32_t)T->sig_est_base[cat]);
     const int bits = max > 16 ? 6 : max > 4 ? 4 : 2;
@@ -904,7 +963,7 @@ struct Walker {
       if (MODE == MODE_COMPRESS) {
         // model: nnz first (recode.cpp:1208-1221), then the buffered map (1244-1255)
         PROF_BEGIN(t4);
-        nz_bits(cat, n, max, is_dc, c422, cnt);
+        nz_bits(cat, n, max, is_dc, c422, cnt, b2);
         PROF_END(4, t4);
         PROF_BEGIN(t5);
         const int nnz_m = cnt & mask;
@@ -912,13 +971,13 @@ struct Walker {
         const int zz = (int)__lane_id();
         const int b = (int)((sigmask >> zz) & 1);
         const int obs = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sigmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sigmask, 0u));
-        const int idx = sig_est_index(cat, max, is_dc, c422, zz, nnz_m, obs);
+        const int idx = sig_est_index(seb, max, is_dc, c422, zz, nnz_m, obs);
         push_v(op_model(b, OPM_CACHE | OPM_THR50, idx), (uint32_t)end + 1);
         PROF_END(5, t5);
       }
     } else if (MODE == MODE_DECOMPRESS) {
       PROF_BEGIN(t4);
-      const int nnz_m = nz_bits(cat, n, max, is_dc, c422, 0);   // recode.cpp:1476-1486
+      const int nnz_m = nz_bits(cat, n, max, is_dc, c422, 0, b2);   // recode.cpp:1476-1486
       PROF_END(4, t4);
       PROF_BEGIN(t3);
       int pos;
@@ -1012,7 +1071,8 @@ struct Walker {
   }
 
   // residual_block_cabac() of one block; p/x4/y4 locate it in the walker's nnz grid
-  AVR_FI void residual_block(int cat, int n, int max, int is_dc, int c422, int p, int pw, int x4, int y4) {
+  // (b2: the block's blk2_v record, BS >= 2)
+  AVR_FI void residual_block(int cat, int n, int max, int is_dc, int c422, int p, int pw, int x4, int y4, uint32_t b2 = 0) {
     if (AVR_MB_UNLIKELY(err)) return;
     MbRec& cur = sh->cur;
     int coded = 1;
@@ -1022,6 +1082,13 @@ struct Walker {
         int bit = cat == 3 ? (0x40 << (n - 49)) : (0x100 << (n - 48));
         nza = (nb_cbp_left() & bit) != 0;
         nzb = (nb_cbp_top() & bit) != 0;
+      } else if constexpr (BS >= 2) {
+        // both registers at the neighbour's lane, then the one the record names
+        const uint32_t ll = b2 & 63, tl = (b2 >> 8) & 63;
+        const uint32_t lc = __builtin_amdgcn_readlane(nz_v, ll), ln = __builtin_amdgcn_readlane(nzn_v, ll);
+        const uint32_t tc = __builtin_amdgcn_readlane(nz_v, tl), tn = __builtin_amdgcn_readlane(nzn_v, tl);
+        nza = ((b2 & 0x40) ? ln : lc) > 0;
+        nzb = ((b2 & 0x4000) ? tn : tc) > 0;
       } else {
         nza = nnz_left(p, pw, x4, y4) > 0;
         nzb = nnz_top(p, x4, y4) > 0;
@@ -1032,7 +1099,7 @@ struct Walker {
     int cnt = 0;
     if (coded) {
       rc_select(cat);
-      cnt = sig_map(cat, n, max, is_dc, c422);
+      cnt = sig_map(cat, n, max, is_dc, c422, b2);
       // coeff_abs_level_minus1 + sign, reverse scan order
       const int ab = (int)opaque_u32((uint32_t)T->abs_base[cat]);   // scalar: the coder ops' base
       int gt1 = 0, eq1 = 0;
@@ -1130,11 +1197,24 @@ struct Walker {
         else gt1++;
       }
       PROF_END(6, t6);
-      cur.mnnz[n] = (uint8_t)cnt;             // end_coding_type recount (recode.cpp:935-947)
+      // end_coding_type recount (recode.cpp:935-947)
+      if constexpr (BS >= 3) mz_v = wlane(mz_v, (uint32_t)n, (uint32_t)cnt);
+      else cur.mnnz[n] = (uint8_t)cnt;
       if (max > 32) cf |= CF_8X8;
     }
     if (is_dc) {
       if (cnt) cf |= (uint32_t)(cat == 3 ? (0x40 << (n - 49)) : (0x100 << (n - 48))) << 16;
+    } else if constexpr (BS >= 2) {
+      // an uncoded block leaves its lanes at the macroblock's initial 0 (each block is coded once)
+      if (cnt) {
+        const uint32_t g = (uint32_t)(p * 16 + y4 * 4 + x4);
+        nz_v = wlane(nz_v, g, (uint32_t)cnt);
+        if (max == 64) {
+          nz_v = wlane(nz_v, g + 1, (uint32_t)cnt);
+          nz_v = wlane(nz_v, g + 4, (uint32_t)cnt);
+          nz_v = wlane(nz_v, g + 5, (uint32_t)cnt);
+        }
+      }
     } else if (max == 64) {
       cur.nnz[p][y4 * 4 + x4] = cur.nnz[p][y4 * 4 + x4 + 1] = (uint8_t)cnt;
       cur.nnz[p][y4 * 4 + 4 + x4] = cur.nnz[p][y4 * 4 + 4 + x4 + 1] = (uint8_t)cnt;
@@ -1188,7 +1268,124 @@ struct Walker {
     return nb;
   }
 
+  // BS >= 1: the same list, record j computed by lane j (blk_v / blk2_v; returns the block count).
+  // Per luma-like plane (plane 0, or 0-2 in 4:4:4) the list holds np records: Intra16x16 its DC
+  // block and, with cbp & 15, its 16 AC blocks; else one 8x8 block (F_T8) or four 4x4 blocks per set
+  // bit of cbp & 15.  Then, 4:2:0 / 4:2:2: two chroma DC blocks (cbp & 0x30) and 2 x 4 or 2 x 8 chroma
+  // AC blocks (cbp & 0x20).  A block's position in its plane is blk_pos's: with i = n & 15 the c_scan8
+  // entries give x4 = (i & 1) | (i >> 1 & 2), y4 = (i >> 1 & 1) | (i >> 2 & 2) in every plane.
+  AVR_FI int list_build(int i16, int cbp) {
+    const int j = (int)__lane_id();
+    const int t8 = (cf & F_T8) != 0, m4 = cbp & 15;
+    const int np = i16 ? (m4 ? 17 : 1) : __builtin_popcount((uint32_t)m4) << (t8 ? 0 : 2);
+    const int nluma = cat_ == 3 ? 3 * np : np;
+    const int c422 = cat_ == 2, chroma = cat_ == 1 || cat_ == 2;
+    const int ndc = (chroma && (cbp & 0x30)) ? 2 : 0, per = c422 ? 8 : 4;
+    const int nac = (chroma && (cbp & 0x20)) ? 2 * per : 0;
+    // a luma-like lane
+    const int p = (j >= np) + (j >= 2 * np), k = j - p * np;
+    const int cat_dc = p == 0 ? 0 : p == 1 ? 6 : 10;
+    int cat, i, max, is_dc = 0;
+    if (i16) {
+      is_dc = k == 0;
+      i = is_dc ? 0 : k - 1;
+      cat = cat_dc + !is_dc;
+      max = is_dc ? 16 : 15;
+    } else {
+      const int q = t8 ? k : k >> 2;   // the block's 8x8 is the q-th set bit of cbp & 15
+      int i8 = 0;
+      for (int b = 1; b < 4; b++)
+        if (((m4 >> b) & 1) && __builtin_popcount((uint32_t)(m4 & ((1 << b) - 1))) == q) i8 = b;
+      i = 4 * i8 + (t8 ? 0 : (k & 3));
+      cat = t8 ? (p == 0 ? 5 : p == 1 ? 9 : 13) : cat_dc + 2;
+      max = t8 ? 64 : 16;
+    }
+    int n = is_dc ? 48 + p : 16 * p + i, pl = p, pw = 4, dc422 = 0;
+    // a chroma lane
+    if (j >= nluma) {
+      const int jc = j - nluma;
+      if (jc < ndc) {
+        cat = 3; n = 49 + jc; max = per; is_dc = 1; dc422 = c422; pl = 1 + jc; i = 0;
+      } else {
+        const int ja = jc - ndc, c = ja >= per, jp = ja - c * per;
+        i = (jp & 3) + 8 * (jp >> 2);   // 4:2:2: the plane's second 8x8 is blocks 8-11
+        cat = 4; n = 16 + 16 * c + i; max = 15; is_dc = 0; pl = 1 + c;
+      }
+      pw = 2;
+    }
+    const int x4 = (i & 1) | ((i >> 1) & 2), y4 = ((i >> 1) & 1) | ((i >> 2) & 2);
+    blk_v = (uint32_t)cat | (uint32_t)n << 4 | (uint32_t)max << 10 | (uint32_t)is_dc << 17 | (uint32_t)dc422 << 18 |
+            (uint32_t)x4 << 19 | (uint32_t)y4 << 21 | (uint32_t)pl << 23 | (uint32_t)pw << 25;
+    if constexpr (BS >= 2) {
+      const int g = pl * 16 + y4 * 4 + x4;
+      const uint32_t l = x4 > 0 ? (uint32_t)(g - 1) : 0x40u | (uint32_t)(pl * 8 + y4);
+      const uint32_t u = y4 > 0 ? (uint32_t)(g - 4) : 0x40u | (uint32_t)(pl * 8 + 4 + x4);
+      uint32_t v = l | u << 8;
+      if constexpr (BS >= 3) {
+        const int nt = n < 48 ? n : 0;   // the DC blocks do not use the tables (48 entries)
+        const uint32_t tb = (uint32_t)T->nb_left[nt] << 16 | (uint32_t)T->nb_up[nt] << 24;
+        v |= n < 48 ? tb : 0u;
+      }
+      blk2_v = v;
+    }
+    return nluma + ndc + nac;
+  }
+
+  // BS >= 2: the neighbours of the macroblock's nnz grids, once per macroblock.  Called at the entry
+  // of residual(), after the macroblock's transform_size_8x8_flag is known (both of the macroblock
+  // layer's places for it precede residual()): nnz_override depends on the current F_T8.  Everything
+  // else read here (sh->left, ring[mb_x], the model row, lf / tf, left_ok / top_ok) was final at the
+  // macroblock's start; a macroblock without residual() needs none of it.
+  AVR_FI void edge_load() {
+    const uint32_t L = __lane_id();
+    {
+      const uint32_t pl = (L >> 3) < 3 ? L >> 3 : 2, r = L & 7;   // lanes >= 24: plane 2 again, never read
+      const int dflt = (cf & F_INTRA) ? 64 : 0;
+      const int pwp = (pl && (cat_ == 1 || cat_ == 2)) ? 2 : 4;
+      int ov_l = 0, ov_t = 0;
+      const int has_ov_l = nnz_override(lf, &ov_l), has_ov_t = nnz_override(tf, &ov_t);
+      const int lval = sh->left.nnz[pl][(r & 3) * 4 + pwp - 1], tval = ring[mb_x].nnz[pl][r & 3];
+      const int lres = !left_ok ? dflt : has_ov_l ? ov_l : lval;
+      const int tres = !top_ok ? dflt : has_ov_t ? ov_t : tval;
+      nzn_v = (uint32_t)(r < 4 ? lres : tres);
+    }
+    if constexpr (BS >= 3) {
+      const uint32_t idx = L < 52 ? L : 51;
+      const uint32_t lval = sh->left.mnnz[idx];
+      mzl_v = (left_ok && L < 52) ? lval : 0u;
+      // the upper macroblock's model bytes (mnnz_top): the kept dwords of the column's row
+      const bool kept = L < 52 && ((kMringUsed >> (L >> 2)) & 1);
+      const uint32_t at = (uint32_t)mb_x * (kMringDwords * 4) + mring_dword(idx >> 2) * 4 + (idx & 3);
+      uint32_t tval = 0;
+      if (kept && top_ok) {
+        if (mring_global) {
+          if (tf & kEdgeMringNz) tval = ((const __attribute__((address_space(1))) uint8_t*)mring)[at];
+        } else {
+          tval = ((const __attribute__((address_space(3))) uint8_t*)mring)[at];
+        }
+      }
+      mzt_v = tval;
+    }
+  }
+
   AVR_FI void residual(int i16, int cbp) {
+    if constexpr (BS >= 1) {
+      const int nb = list_build(i16, cbp);
+      if constexpr (BS >= 2) edge_load();
+      PROF_BEGIN(t2);
+      for (int j = 0; j < nb && AVR_MB_LIKELY(!err); j++) {
+        const uint32_t b = __builtin_amdgcn_readlane(blk_v, (uint32_t)j);
+        const uint32_t b2 = BS >= 2 ? __builtin_amdgcn_readlane(blk2_v, (uint32_t)j) : 0u;
+        // BS >= 2: residual_block needs the block's grid lane g only, passed whole as x4
+        if constexpr (BS >= 2)
+          residual_block(b & 15, (b >> 4) & 63, (b >> 10) & 127, (b >> 17) & 1, (b >> 18) & 1, 0, 0, (b >> 19) & 63, 0, b2);
+        else
+          residual_block(b & 15, (b >> 4) & 63, (b >> 10) & 127, (b >> 17) & 1, (b >> 18) & 1, (b >> 23) & 3,
+                         (b >> 25) & 7, (b >> 19) & 3, (b >> 21) & 3);
+      }
+      PROF_END(2, t2);
+      return;
+    }
     int nb = list_luma(0, 0, i16, cbp);
     if (cat_ == 3) {
       nb = list_luma(nb, 1, i16, cbp);
@@ -1701,6 +1898,9 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w) {
       if (lane < (int)sizeof(MbRec) / 4) c32[lane] = (lane == 29 || lane == 30) ? 0xffffffffu : 0u;
       wave_sync();
     }
+    // the grids of the record that live in registers start from zero like the record
+    if constexpr (Walker<MODE, RM, FLD, P32, SPL, SRD>::BS >= 2) w.nz_v = 0;
+    if constexpr (Walker<MODE, RM, FLD, P32, SPL, SRD>::BS >= 3) w.mz_v = 0;
     SPROF_ENDW(0, ps0);
 #ifdef AVR_PROFILE
     w.sprofb[0]++;   // sub-section 0 counts macroblocks
@@ -1715,6 +1915,13 @@ AVR_FI void walk_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w) {
     w.last_mb = addr + 1 >= npic;
     // publish: bottom edge to the ring, full record to `left`, model bytes to the frame (RM) --
     // two lane-parallel LDS reads of the record (whole, and the edge's dwords), then the stores
+    // (BS >= 2: first the grids kept in registers into the record, one byte per lane)
+    if constexpr (Walker<MODE, RM, FLD, P32, SPL, SRD>::BS >= 2) {
+      if (lane < 48) ((uint8_t*)w.sh->cur.nnz)[lane] = (uint8_t)w.nz_v;
+    }
+    if constexpr (Walker<MODE, RM, FLD, P32, SPL, SRD>::BS >= 3) {
+      if (lane < 52) w.sh->cur.mnnz[lane] = (uint8_t)w.mz_v;
+    }
     wave_sync();
     {
       const uint32_t* c32 = (const uint32_t*)&w.sh->cur;
@@ -1827,6 +2034,7 @@ AVR_FI void begin_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w, const avr_slice
   else w.sig8_v = w.T->sig8x8[__lane_id()];
   w.top_pending = 0;
   w.last8_v = w.T->last8x8[__lane_id()];
+  w.blk_v = w.blk2_v = w.nz_v = w.nzn_v = w.mz_v = w.mzl_v = w.mzt_v = 0;
   if (MODE == MODE_DECOMPRESS) w.byp_e = w.sh->est[1024];
   w.mc_load();
   if (!RM && (MODE == MODE_COMPRESS || MODE == MODE_DECOMPRESS)) {

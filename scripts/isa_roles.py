@@ -7,6 +7,7 @@ walker's instructions per bin by role).  Input: device assembly with line tables
   python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --loop 4887
   python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --edges 4887
   python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --path 4887,4889,4893,4887
+  python scripts/isa_roles.py /tmp/dec_g.s 'slices_parallel_kernelILi1ELb0ELb0E' --static
 
 (LINE: avr_walker.h's line of `int b = rdec(e);` in sig_map's decompress map_loop, CALLER: the line
 of the map_loop(...<int, 0>) call below it; --csrc DIR when the listing is of another tree's sources.
@@ -62,6 +63,34 @@ REGIONS = [("const uint32_t sop = opaque_u32", "auto map_loop = [&](auto K) {"),
            ("if constexpr (MODE == MODE_DECOMPRESS && !FLD) {", None),
            ("uint64_t sigmask = 0;", "auto map_loop = [&](auto K) {"),
            ("} else if constexpr (MODE == MODE_COMPRESS && kStageLevels) {", None)]
+# The per-block and per-macroblock code around those loops, for --static: helpers that
+# belong to one role whole, and the statements of residual_block, nz_bits, sig_map's head, residual()
+# and the macroblock loop of walk_slice by their text.  They come after the per-bin roles above, so
+# a line of a per-bin region keeps its per-bin role.
+BLOCK_FUNCS = [
+    (W, "push_block", "blk:list_build"), (W, "list_luma", "blk:list_build"), (W, "blk_pos", "blk:list_build"),
+    (W, "list_build", "blk:list_build"), (W, "edge_load", "mb:edge_load"),
+    (W, "nnz_left", "blk:cbf_neighbours"), (W, "nnz_top", "blk:cbf_neighbours"), (W, "nnz_override", "blk:cbf_neighbours"),
+    (W, "nb_cbp_left", "blk:cbf_neighbours"), (W, "nb_cbp_top", "blk:cbf_neighbours"),
+    (W, "mnnz_left", "blk:nz_neighbours"), (W, "mnnz_top", "blk:nz_neighbours"), (W, "mnnz_prev", "blk:nz_neighbours"),
+    (W, "rc_select", "blk:rc_select"), (W, "rc_writeback", "blk:rc_select"), (W, "rc_addr", "blk:rc_select"),
+]
+BLOCK_STATEMENTS = [
+    (r"sh->blk\[|readlane\(blk2?_v|residual_block\(|\(b >> ", "blk:block_record"),
+    (r"cur\.nnz\[|nz_v = wlane|cur\.mnnz\[n\]|mz_v = wlane|const uint32_t g = ", "blk:nnz_store"),
+    (r"nz_v|nzn_v|nza|nzb|int bit = ", "blk:cbf_neighbours"),
+    (r"mz_v|mzl_v|mzt_v|nb_left|nb_up|\b(li|ui|lv|av|has_left|has_above|pv)\b", "blk:nz_neighbours"),
+    (r"T->(sig_base|last_base|abs_base|cbf_base|sig_est_base)", "blk:category_bases"),
+    (r"c32\[lane\] = |w\.nz_v = 0|w\.mz_v = 0", "mb:clear"),
+    (r"list_build\(|list_luma\(|push_block\(", "blk:list_build"),
+    (r"edge_load\(", "mb:edge_load"),
+    (r".", "blk:other"),
+]
+BLOCK_REGIONS = [("AVR_FI void residual_block(", None), ("AVR_FI int nz_bits(", None), ("AVR_FI int sig_map(", None),
+                 ("AVR_FI void residual(int i16, int cbp) {", None)]
+# (first line's marker, last line's marker, role) in walk_slice's macroblock loop
+MB_REGIONS = [("// clear the current record (one dword per lane", "SPROF_ENDW(0, ps0);", "mb:clear"),
+              ("// publish: bottom edge to the ring, full record to `left`", "PROF_ENDW(7, t7);", "mb:publish")]
 
 
 def block_end(lines, i):
@@ -100,6 +129,23 @@ def build_roles(csrc):
             if text in ("", "{", "}", "};"):
                 continue
             roles.append((W, k + 1, k + 1, next(r for p, r in STATEMENTS if re.search(p, text))))
+    # the per-block and per-macroblock roles: after the per-bin ones (role() takes the first match)
+    for f, name, r in BLOCK_FUNCS:
+        pat = re.compile(r"^\s*AVR_FI\b[^=]*\b" + name + r"\s*\(")
+        for i, line in enumerate(src[f]):
+            if pat.match(line):
+                roles.append((f, i + 1, block_end(src[f], i) + 1, r))
+    for first, last, r in MB_REGIONS:
+        i = next(k for k, l in enumerate(lines) if first in l)
+        j = next(k for k in range(i, len(lines)) if last in lines[k])
+        roles.append((W, i + 1, j + 1, r))
+    for first, _ in BLOCK_REGIONS:
+        i = next(k for k, l in enumerate(lines) if first in l)
+        for k in range(i, block_end(lines, i) + 1):
+            text = lines[k].split("//")[0].strip()
+            if text in ("", "{", "}", "};"):
+                continue
+            roles.append((W, k + 1, k + 1, next(r for p, r in BLOCK_STATEMENTS if re.search(p, text))))
     return roles
 
 
@@ -174,6 +220,7 @@ def main():
     ap.add_argument("kernel")
     ap.add_argument("--anchor", type=int, nargs=2)
     ap.add_argument("--loop")
+    ap.add_argument("--static", action="store_true", help="the whole kernel's instructions, LDS accesses and LDS waits by role")
     ap.add_argument("--edges", metavar="HDR", help="the loop's layout: each block's branches, targets and fall-through")
     ap.add_argument("--path", help="B1,B2,...: instructions, branch instructions and taken branches along these blocks")
     ap.add_argument("--csrc", default=CSRC, help="the sources the listing was compiled from (default: this tree's)")
@@ -181,6 +228,20 @@ def main():
     ROLES.extend(build_roles(a.csrc))
     blocks = parse(a.asm, a.kernel)
     print(f"{len(blocks)} blocks, {sum(len(b['ins']) for b in blocks)} instructions", file=sys.stderr)
+    if a.static:
+        # every instruction of the kernel once, by role: the per-block and per-macroblock code is
+        # inlined at one site each, so its static count is what one block / macroblock can execute
+        # at the most (all branches of the role together); LDS = ds_* instructions, waits = s_waitcnt
+        # with an lgkmcnt operand
+        tot, lds, waits = collections.Counter(), collections.Counter(), collections.Counter()
+        for b in blocks:
+            for mn, ch, text in b["ins"]:
+                r = role(ch)
+                tot[r] += 1
+                lds[r] += mn.startswith("ds_")
+                waits[r] += mn == "s_waitcnt" and "lgkmcnt" in text
+        for r in sorted(tot, key=lambda r: (not r.startswith(("blk:", "mb:")), r)):
+            print(f"{r:22s} {tot[r]:6d} instructions {lds[r]:4d} LDS {waits[r]:4d} lgkmcnt waits")
     if a.anchor:
         line, caller = a.anchor
         hits = collections.Counter()
