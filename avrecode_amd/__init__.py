@@ -24,7 +24,8 @@ __all__ = [
     "SLICE_DESC", "PIECE", "KEEP_ALL",
     "SLICE_RESULT", "SynthParams", "lib", "parse_stream", "assemble_container", "neighbor_tables",
     "plan_decompress", "splice_container", "container_model", "source_sha", "library_path", "EXPORTED_SYMBOLS",
-    "seams_of_container", "SPLIT_SLOT", "SplitPlan", "split_plan", "seams_build",
+    "seams_of_container", "SPLIT_SLOT", "SplitPlan", "split_plan", "seams_build", "escape_payload",
+    "ASSEMBLE_ESCAPED",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -38,6 +39,7 @@ MODEL_PARALLEL = 1
 MODEL_PARALLEL32 = 2
 MODEL_CHAINED = 3   # the reference model in chains of CHAIN_SLICES coded slices ("avrecode-amd:R16")
 CHAIN_SLICES = 16
+ASSEMBLE_ESCAPED = 1   # avr_assemble_container_opts' flag: the second search of Context.recode_escaped
 SPLIT_BYTES_DEFAULT = 98304   # the parallel model's long-slice split (Context.split_bytes), unless AVR_SPLIT_BYTES
 MODEL_NAMES = {MODEL_REFERENCE: "R", MODEL_PARALLEL: "P", MODEL_PARALLEL32: "P32", MODEL_CHAINED: "C"}
 
@@ -64,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "avr_dec_plan_load_pieces", "avr_dec_plan_units", "avr_dec_plan_recs", "avr_decompress_pieces", "avr_pack_pieces",
     "avr_split_plan", "avr_seams_build", "avr_assemble_container_seams", "avr_assemble_container_seams_parsed",
     "avr_compress_split_slices", "avr_stage_pieces", "avr_verify_units",
+    "avr_set_recode_escaped", "avr_get_recode_escaped", "avr_escape_payload", "avr_assemble_container_opts",
 )
 
 # avr_slice_desc / avr_slice_result (include/avrecode.h), C layout
@@ -237,6 +240,11 @@ def lib() -> ctypes.CDLL:
     L.avr_splice_container.argtypes = [vp, sz, i32, vp, vp, sz, vp, vp, pp, psz]
     L.avr_last_phase_times.argtypes = [vp, vp]
     L.avr_set_split_bytes.argtypes = [vp, sz]
+    L.avr_set_recode_escaped.argtypes = [vp, i32]
+    L.avr_get_recode_escaped.argtypes = [vp]
+    L.avr_escape_payload.argtypes = [vp, sz, vp, sz, psz]
+    L.avr_assemble_container_opts.argtypes = [vp, sz, i32, vp, i32, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp,
+                                              ctypes.c_uint32, pp, psz]
     L.avr_get_split_bytes.argtypes = [vp]
     L.avr_get_split_bytes.restype = sz
     for name in EXPORTED_SYMBOLS:   # fails here, not at first use, when the build is stale
@@ -580,7 +588,7 @@ def seams_build(descs, arena, res, slots, cuts, piece_end, recs, rec_stride: int
 
 def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, lens: np.ndarray,
                        model: int = MODEL_PARALLEL, ps: "ParsedStream | None" = None, as_array: bool = False,
-                       out: "np.ndarray | None" = None, seams=None):
+                       out: "np.ndarray | None" = None, seams=None, escaped: bool = False):
     """Recoded container from per-slice outputs gathered from the ranks (avr_assemble_container; with ps =
     parse_stream(data) already in hand, avr_assemble_container_parsed: no second parse).  recoded:
     bytes or a uint8 array.  model: the model / coder the outputs were made with (PARALLEL, PARALLEL32,
@@ -590,8 +598,12 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
     returns the view of it that holds the container.  seams: (blob, offsets, lens) -- slice k's
     Block field 16 is blob[offsets[k] : offsets[k] + lens[k]], length 0 for none -- or a list of one
     bytes object per slice (b"" for none): the container of a split compress
-    (avr_assemble_container_seams; MODEL_PARALLEL only, not with out).  Host only."""
+    (avr_assemble_container_seams; MODEL_PARALLEL only, not with out).  escaped: the second search of
+    Context.recode_escaped (avr_assemble_container_opts with ASSEMBLE_ESCAPED; the parallel models
+    only, not with out), so that the result is what ctx.compress writes with the option on.  Host only."""
     L = lib()
+    if escaped and out is not None:
+        raise ValueError("assemble_container: escaped cannot be combined with out")
     p, n, keep = _buf(data)
     st = np.ascontiguousarray(status, dtype=np.int32)
     of = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -612,7 +624,16 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
         if len(so) != len(st) or len(sl) != len(st) or len(of) != len(st) or len(ln) != len(st):
             raise ValueError("assemble_container: status / offsets / lens / seams need one entry per slice")
         sp, sn, keep3 = _buf(sb)
-        if ps is not None:
+        if escaped:
+            dd = np.ascontiguousarray(ps.descs) if ps is not None else None
+            if dd is not None and len(dd) != len(st):
+                raise ValueError("assemble_container: status / offsets / lens need one entry per parsed slice")
+            r = L.avr_assemble_container_opts(p, n, model, dd.ctypes.data if dd is not None else None, len(st),
+                                              ps.arena.ctypes.data if ps is not None else None,
+                                              ps.arena.nbytes if ps is not None else 0, st.ctypes.data, rp, rn,
+                                              of.ctypes.data, ln.ctypes.data, sp, sn, so.ctypes.data, sl.ctypes.data,
+                                              ASSEMBLE_ESCAPED, ctypes.byref(res), ctypes.byref(olen))
+        elif ps is not None:
             dd = np.ascontiguousarray(ps.descs)
             if len(dd) != len(st):
                 raise ValueError("assemble_container: status / offsets / lens need one entry per parsed slice")
@@ -639,7 +660,16 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
         if r != AVR_OK:
             raise AvrError(r, f"avr_assemble_container_into failed (container {olen.value} B, buffer {out.nbytes} B)")
         return out[:olen.value]
-    if ps is not None:
+    if escaped:
+        dd = np.ascontiguousarray(ps.descs) if ps is not None else None
+        if len(of) != len(st) or len(ln) != len(st) or (dd is not None and len(dd) != len(st)):
+            raise ValueError("assemble_container: status / offsets / lens need one entry per parsed slice")
+        r = L.avr_assemble_container_opts(p, n, model, dd.ctypes.data if dd is not None else None, len(st),
+                                          ps.arena.ctypes.data if ps is not None else None,
+                                          ps.arena.nbytes if ps is not None else 0, st.ctypes.data, rp, rn,
+                                          of.ctypes.data, ln.ctypes.data, None, 0, None, None, ASSEMBLE_ESCAPED,
+                                          ctypes.byref(res), ctypes.byref(olen))
+    elif ps is not None:
         dd = np.ascontiguousarray(ps.descs)
         if len(dd) != len(st) or len(of) != len(st) or len(ln) != len(st):
             raise ValueError("assemble_container: status / offsets / lens need one entry per parsed slice")
@@ -711,6 +741,19 @@ def describe_container(avrc) -> tuple[dict, bytes]:
     return json.loads(text), _take(out, olen.value)
 
 
+def escape_payload(payload) -> bytes:
+    """escape(payload): H.264 7.4.1 from a clean state, the library's own (avr_escape_payload) -- a
+    03 before any byte <= 3 that follows two zero bytes since the last insertion.  Host only."""
+    L = lib()
+    p, n, keep = _buf(payload)
+    out = np.empty(n + n // 2 + 1, dtype=np.uint8)
+    olen = ctypes.c_size_t()
+    r = L.avr_escape_payload(p, n, out.ctypes.data, out.nbytes, ctypes.byref(olen))
+    if r != AVR_OK:
+        raise AvrError(r, "avr_escape_payload failed")
+    return out[:olen.value].tobytes()
+
+
 def neighbor_tables(ctx=None) -> tuple[bytes, bytes]:
     """(nb_left[48], nb_up[48]): the model's neighbour geometry as the kernels use it
     (avr_neighbor_tables).  ctx None: the host-built table (no GPU); a Context: its device copy."""
@@ -764,6 +807,17 @@ class Context:
     @split_bytes.setter
     def split_bytes(self, v: int):
         self._check(lib().avr_set_split_bytes(self._h, int(v)), "avr_set_split_bytes")
+
+    @property
+    def recode_escaped(self) -> bool:
+        """Re-code slices whose NAL unit carries emulation-prevention bytes (avr_set_recode_escaped;
+        default off, or the environment's AVR_RECODE_ESCAPED): read by compress / roundtrip of the
+        parallel models, whose containers then carry Block field 17 and an "E" tag."""
+        return bool(lib().avr_get_recode_escaped(self._h))
+
+    @recode_escaped.setter
+    def recode_escaped(self, on: bool):
+        self._check(lib().avr_set_recode_escaped(self._h, 1 if on else 0), "avr_set_recode_escaped")
 
     # ------------------------------------------------------------------ whole files
     def compress(self, data, model: int = MODEL_REFERENCE) -> bytes:

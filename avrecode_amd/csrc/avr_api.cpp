@@ -689,7 +689,11 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
                  : cand_of[f][i] <= -2   ? so[-2 - cand_of[f][i]].status == 0
                                          : false;
   }
-  parallel_files(nf, [&](int f) { found[f] = segment(in[f], in_len[f], pf[f], ok[f]); });
+  // the parallel models' option (avr_set_recode_escaped): a slice the search misses is searched
+  // once more by its escaped payload, and kept with Block field 17
+  const bool escaped = parallel_model(model) && c->recode_escaped;
+  std::vector<std::vector<uint32_t>> escapes(nf);
+  parallel_files(nf, [&](int f) { found[f] = segment(in[f], in_len[f], pf[f], ok[f], escaped ? &escapes[f] : nullptr); });
   // 3) reference model: the coded slices of every file in file order, estimators per file; a
   //    slice that fails there is demoted to skip_coded and its file's pass repeated
   std::vector<std::vector<std::vector<uint8_t>>> recoded(nf);
@@ -783,7 +787,7 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
     std::vector<std::pair<const uint8_t*, size_t>> blobs(pf[f].slices.size(), {nullptr, 0});
     for (size_t i = 0; i < pf[f].slices.size(); i++) blobs[i] = {recoded[f][i].data(), recoded[f][i].size()};
     st[f] = emit_container(in[f], in_len[f], views_of(pf[f]), found[f], blobs, model, &out[f], &out_len[f], nullptr, 0,
-                           &seams_of[f]);
+                           &seams_of[f], escaped ? &escapes[f] : nullptr);
   });
   for (int f = 0; f < nf; f++) {
     if (status) status[f] = st[f];
@@ -1265,6 +1269,7 @@ int avr_create(int device, avr_ctx** out) {
     const char* e = getenv("AVR_SPLIT_BYTES");
     c->split_bytes = e ? (size_t)strtoull(e, nullptr, 10) : kSplitBytesDefault;
   }
+  if (const char* e = getenv("AVR_RECODE_ESCAPED")) c->recode_escaped = strtol(e, nullptr, 10) != 0;
   if (const char* e = getenv("AVR_FIELD_LANE"); !e || strcmp(e, "0") != 0) {
     if (hipStreamCreateWithFlags(&c->fld_stream, hipStreamNonBlocking) != hipSuccess) return AVR_ERR_DEVICE;
     for (auto& ev : c->fld_ev)
@@ -1298,6 +1303,13 @@ int avr_set_split_bytes(avr_ctx* c, size_t bytes) {
   return AVR_OK;
 }
 size_t avr_get_split_bytes(const avr_ctx* c) { return c ? c->split_bytes : 0; }
+
+int avr_set_recode_escaped(avr_ctx* c, int on) {
+  if (!c) return AVR_ERR_INVALID_ARGUMENT;
+  c->recode_escaped = on != 0;
+  return AVR_OK;
+}
+int avr_get_recode_escaped(const avr_ctx* c) { return c && c->recode_escaped; }
 
 void avr_free(void* p) { free(p); }
 

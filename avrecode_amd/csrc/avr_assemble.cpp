@@ -72,7 +72,12 @@ struct TrigramIndex {
 // would scan to the end of the file for each of them (O(misses x file): minutes for a 10-minute 4K
 // stream); with the key a miss costs a binary search.  A payload without one is found in its own
 // NAL (its bytes are verbatim there), so memmem stops at most one NAL past `from`.
-const uint8_t* find_payload(const uint8_t* in, size_t n, size_t from, const uint8_t* P, size_t m, TrigramIndex* ix) {
+// `end` (<= n): the occurrence must lie within in[from, end) -- the escaped search of segment(), which
+// stops inside the slice's own NAL.
+const uint8_t* find_payload(const uint8_t* in, size_t n, size_t from, const uint8_t* P, size_t m, TrigramIndex* ix,
+                            size_t end = ~(size_t)0) {
+  end = std::min(end, n);
+  if (from > end || m > end - from) return nullptr;
   size_t j = 0;
   bool anchor = false;
   for (const uint8_t* q = P; m >= 3 && q + 2 < P + m;) {
@@ -85,7 +90,7 @@ const uint8_t* find_payload(const uint8_t* in, size_t n, size_t from, const uint
     }
     q++;
   }
-  if (!anchor) return (const uint8_t*)memmem(in + from, n - from, P, m);
+  if (!anchor) return (const uint8_t*)memmem(in + from, end - from, P, m);
   if (!ix->built) {
     const double tb = now_s();
     ix->build(in, n);
@@ -99,7 +104,7 @@ const uint8_t* find_payload(const uint8_t* in, size_t n, size_t from, const uint
     const std::vector<uint64_t>& ps = ix->pos[P[j + 2]];
     for (auto it = std::lower_bound(ps.begin(), ps.end(), (uint64_t)(from + j)); it != ps.end(); ++it) {
       const size_t q = (size_t)*it - j;
-      if (q + m > n) break;
+      if (q + m > end) break;
       if (memcmp(in + q, P, m) == 0) return in + q;
     }
     return nullptr;
@@ -108,7 +113,7 @@ const uint8_t* find_payload(const uint8_t* in, size_t n, size_t from, const uint
   for (auto it = std::lower_bound(ix->e.begin(), ix->e.end(), E{key, (uint64_t)(from + j)}); it != ix->e.end(); ++it) {
     if (it->key != key) break;
     const size_t q = (size_t)it->pos - j;
-    if (q + m > n) break;
+    if (q + m > end) break;
     if (memcmp(in + q, P, m) == 0) return in + q;
   }
   return nullptr;
@@ -153,7 +158,11 @@ struct SeamsArg {
 
 int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceView>& sv, const int32_t* status,
              const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out,
-             size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0, const SeamsArg& sa = SeamsArg()) {
+             size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0, const SeamsArg& sa = SeamsArg(),
+             uint32_t flags = 0) {
+  // the escaped second chance is the parallel models' own format
+  if ((flags & ~(uint32_t)AVR_ASSEMBLE_ESCAPED) || ((flags & AVR_ASSEMBLE_ESCAPED) && !parallel_model(model)))
+    return AVR_ERR_INVALID_ARGUMENT;
   std::vector<char> ok(sv.size(), 0);
   std::vector<std::pair<const uint8_t*, size_t>> blobs(sv.size(), {nullptr, 0}), fields;
   if (sa.p) fields.assign(sv.size(), {nullptr, 0});
@@ -171,9 +180,12 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
     }
   }
   const double t0 = now_s();
-  const std::vector<const uint8_t*> found = segment(file, n, sv, ok);
+  std::vector<uint32_t> escapes;
+  const bool esc = (flags & AVR_ASSEMBLE_ESCAPED) != 0;
+  const std::vector<const uint8_t*> found = segment(file, n, sv, ok, esc ? &escapes : nullptr);
   const double t1 = now_s();
-  const int r = emit_container(file, n, sv, found, blobs, model, out, out_len, dst, cap, sa.p ? &fields : nullptr);
+  const int r = emit_container(file, n, sv, found, blobs, model, out, out_len, dst, cap, sa.p ? &fields : nullptr,
+                               esc ? &escapes : nullptr);
   if (getenv("AVR_ASM_TIMING")) fprintf(stderr, "assemble: segment %.3f s, emit %.3f s\n", t1 - t0, now_s() - t1);
   return r;
 }
@@ -181,7 +193,7 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
 int assemble_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
                     const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
                     size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out, size_t* out_len,
-                    uint8_t* dst, size_t cap, const SeamsArg& sa = SeamsArg()) {
+                    uint8_t* dst, size_t cap, const SeamsArg& sa = SeamsArg(), uint32_t flags = 0) {
   if (!file || !out_len || n_slices < 0 || (n_slices && (!descs || !arena || !status || !offsets || !lens)) ||
       !assemblable(model) || (sa.p && n_slices && (!sa.offsets || !sa.lens)))
     return AVR_ERR_INVALID_ARGUMENT;
@@ -206,7 +218,19 @@ int assemble_parsed(const uint8_t* file, size_t n, int model, const avr_slice_de
       }
       sv[i] = {P, m, d.coded != 0, d.file_offset};
     }
-    return assemble(file, n, model, sv, status, recoded, recoded_len, offsets, lens, out, out_len, dst, cap, sa);
+    // the escaped search needs each affected slice's NAL, which a descriptor does not carry: the
+    // file is parsed here once when a coded slice's payload does not stand verbatim in it
+    bool affected = false;
+    for (int i = 0; i < n_slices && (flags & AVR_ASSEMBLE_ESCAPED); i++)
+      affected = affected || (descs[i].coded && status[i] == 0 && descs[i].file_offset == ~(uint64_t)0);
+    if (affected) {
+      ParsedFile pf;
+      if (int r = parse_file(nullptr, file, n, &pf, /*views=*/true)) return r;
+      if ((size_t)n_slices != pf.slices.size()) return AVR_ERR_INVALID_ARGUMENT;
+      for (int i = 0; i < n_slices; i++)
+        sv[i].nal_lo = pf.slices[i].nal_offset, sv[i].nal_hi = pf.slices[i].nal_offset + pf.slices[i].nal_size;
+    }
+    return assemble(file, n, model, sv, status, recoded, recoded_len, offsets, lens, out, out_len, dst, cap, sa, flags);
   });
 }
 
@@ -226,16 +250,25 @@ std::vector<SliceView> views_of(const ParsedFile& pf) {
   std::vector<SliceView> v(pf.slices.size());
   for (size_t i = 0; i < v.size(); i++)
     v[i] = {pf.slices[i].payload(), pf.slices[i].size, recodable_candidate(pf.slices[i]),
-            pf.slices[i].file_payload_offset()};
+            pf.slices[i].file_payload_offset(), pf.slices[i].nal_offset, pf.slices[i].nal_offset + pf.slices[i].nal_size};
   return v;
 }
 
 // find_next_coded_block_and_emit_literal (recode.cpp:1275-1297): slice i becomes a cabac block when
 // it is recodable (ok[i]), at least a surrogate marker long, and its payload occurs verbatim after
 // the previous coded block.  Returns the payload's position in the file per slice (null = skip).
+// With `escapes`, a slice the search misses gets a second chance (the parallel models' opt-in
+// format, Block field 17): E = escape(payload) -- 7.4.1 from a clean state -- is searched from the
+// end of the previous coded block, inside the slice's own NAL only: E holds a 00 00 03 trigram, so a
+// miss costs find_payload a binary search, and a hit anywhere else would put the surrogate where
+// the decompressor's parse does not meet this slice.  A hit makes the block stand for E: size + k
+// bytes of the file.  A NAL whose escaping is not the canonical one, or whose slice header leaves zero bytes in
+// front of the payload (the file's 03 is then not where the clean-state escape puts it), has no E in
+// it and stays skip_coded.
 std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const std::vector<SliceView>& sv,
-                                    const std::vector<char>& ok) {
+                                    const std::vector<char>& ok, std::vector<uint32_t>* escapes) {
   std::vector<const uint8_t*> found(sv.size(), nullptr);
+  if (escapes) escapes->assign(sv.size(), 0);
   TrigramIndex ix;
   // a recorded position is trusted only where the payload's bytes stand there (a payload that is a
   // view of the file at that position trivially; a copy -- rank 0's parse arena, another revision
@@ -273,12 +306,22 @@ std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const std::vect
     if (f) {
       found[i] = f;
       prev_end = (size_t)(f - in) + sv[i].size;
+    } else if (escapes && sv[i].nal_hi > sv[i].nal_lo && sv[i].nal_hi <= n) {
+      const std::vector<uint8_t> e = avr::escape(sv[i].payload, sv[i].size);
+      if (e.size() == sv[i].size) continue;
+      f = find_payload(in, n, std::max(prev_end, sv[i].nal_lo), e.data(), e.size(), &ix, sv[i].nal_hi);
+      if (f) {
+        found[i] = f;
+        (*escapes)[i] = (uint32_t)(e.size() - sv[i].size);
+        prev_end = (size_t)(f - in) + e.size();
+      }
     }
   }
   return found;
 }
-std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const ParsedFile& pf, const std::vector<char>& ok) {
-  return segment(in, n, views_of(pf), ok);
+std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const ParsedFile& pf, const std::vector<char>& ok,
+                                    std::vector<uint32_t>* escapes) {
+  return segment(in, n, views_of(pf), ok, escapes);
 }
 
 // compressor::run's block stream (recode.cpp:1115-1125, 1275-1297) as a Recoded protobuf, written
@@ -288,7 +331,8 @@ std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const ParsedFil
 int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv, const std::vector<const uint8_t*>& found,
                    const std::vector<std::pair<const uint8_t*, size_t>>& recoded, int model, uint8_t** out,
                    size_t* out_len, uint8_t* dst, size_t cap,
-                   const std::vector<std::pair<const uint8_t*, size_t>>* seams) {
+                   const std::vector<std::pair<const uint8_t*, size_t>>* seams, const std::vector<uint32_t>* escapes) {
+  bool any_escapes = false;
   std::vector<avr::PbBlock> blocks;
   blocks.reserve(2 * sv.size() + 1);
   size_t prev_end = 0;
@@ -301,7 +345,9 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
       lit.literal = in + prev_end;
       lit.literal_len = (size_t)(found[i] - (in + prev_end));
       blocks.push_back(lit);
-      prev_end = (size_t)(found[i] - in) + s.size;
+      const uint32_t k = escapes ? (*escapes)[i] : 0u;   // the block stands for size + k file bytes
+      prev_end = (size_t)(found[i] - in) + s.size + k;
+      if (k) b.has_escapes = any_escapes = true, b.escapes = k;
       b.has_size = true;
       b.size = (int64_t)s.size;
       b.has_parity = true;
@@ -325,7 +371,10 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
   lit.literal_len = n - prev_end;
   blocks.push_back(lit);
   std::vector<uint8_t> md;
-  if (const char* tag = avr::version_of_model(model)) avr::pb_put_metadata_version(&md, tag);
+  // a container without field 17 keeps the plain tag and the plain bytes
+  const char* tag = any_escapes ? avr::escaped_version_of_model(model) : avr::version_of_model(model);
+  if (any_escapes && !tag) return fail(nullptr, AVR_ERR_INVALID_ARGUMENT, "escapes on a model without the field");
+  if (tag) avr::pb_put_metadata_version(&md, tag);
   size_t total = md.size();
   for (const auto& b : blocks) total += avr::pb_block_size(b);
   if (dst && total > cap) {
@@ -353,12 +402,17 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
 
 extern "C" {
 
-int avr_assemble_container_seams(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
-                                 const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets,
-                                 const uint32_t* lens, const uint8_t* seams, size_t seams_len,
-                                 const uint64_t* seam_offsets, const uint32_t* seam_lens, uint8_t** out,
-                                 size_t* out_len) {
-  if (!file || !out || !out_len || n_slices < 0 || (n_slices && (!status || !offsets || !lens)) || !assemblable(model) ||
+int avr_assemble_container_opts(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
+                                const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
+                                size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, const uint8_t* seams,
+                                size_t seams_len, const uint64_t* seam_offsets, const uint32_t* seam_lens,
+                                uint32_t flags, uint8_t** out, size_t* out_len) {
+  if (!out) return AVR_ERR_INVALID_ARGUMENT;
+  const SeamsArg sa{seams, seams_len, seam_offsets, seam_lens};
+  if (descs || arena)
+    return assemble_parsed(file, n, model, descs, n_slices, arena, arena_len, status, recoded, recoded_len, offsets, lens,
+                           out, out_len, nullptr, 0, sa, flags);
+  if (!file || !out_len || n_slices < 0 || (n_slices && (!status || !offsets || !lens)) || !assemblable(model) ||
       (seams && n_slices && (!seam_offsets || !seam_lens)))
     return AVR_ERR_INVALID_ARGUMENT;
   return guarded(nullptr, [&]() -> int {
@@ -366,15 +420,24 @@ int avr_assemble_container_seams(const uint8_t* file, size_t n, int model, int n
     if (int r = parse_file(nullptr, file, n, &pf, /*views=*/true)) return r;
     if ((size_t)n_slices != pf.slices.size()) return AVR_ERR_INVALID_ARGUMENT;
     return assemble(file, n, model, views_of(pf), status, recoded, recoded_len, offsets, lens, out, out_len, nullptr, 0,
-                    SeamsArg{seams, seams_len, seam_offsets, seam_lens});
+                    sa, flags);
   });
+}
+
+int avr_assemble_container_seams(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
+                                 const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets,
+                                 const uint32_t* lens, const uint8_t* seams, size_t seams_len,
+                                 const uint64_t* seam_offsets, const uint32_t* seam_lens, uint8_t** out,
+                                 size_t* out_len) {
+  return avr_assemble_container_opts(file, n, model, nullptr, n_slices, nullptr, 0, status, recoded, recoded_len, offsets,
+                                     lens, seams, seams_len, seam_offsets, seam_lens, 0, out, out_len);
 }
 
 int avr_assemble_container(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
                            const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens,
                            uint8_t** out, size_t* out_len) {
-  return avr_assemble_container_seams(file, n, model, n_slices, status, recoded, recoded_len, offsets, lens, nullptr, 0,
-                                      nullptr, nullptr, out, out_len);
+  return avr_assemble_container_opts(file, n, model, nullptr, n_slices, nullptr, 0, status, recoded, recoded_len, offsets,
+                                     lens, nullptr, 0, nullptr, nullptr, 0, out, out_len);
 }
 
 int avr_assemble_container_seams_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs,
@@ -482,6 +545,17 @@ int avr_slice_payload_sizes(const uint8_t* file, size_t n, uint32_t** sizes, int
   });
 }
 
+int avr_escape_payload(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* len) {
+  if ((!src && n) || !len || (!dst && cap)) return AVR_ERR_INVALID_ARGUMENT;
+  return guarded(nullptr, [&]() -> int {
+    const std::vector<uint8_t> e = avr::escape(src, n);
+    *len = e.size();
+    if (e.size() > cap) return AVR_ERR_INVALID_ARGUMENT;
+    if (!e.empty()) memcpy(dst, e.data(), e.size());
+    return AVR_OK;
+  });
+}
+
 int avr_container_describe(const uint8_t* in, size_t n, char** json, uint8_t** reserialized, size_t* len) {
   if (!in || !json || !reserialized || !len) return AVR_ERR_INVALID_ARGUMENT;
   *json = nullptr;
@@ -513,6 +587,7 @@ int avr_container_describe(const uint8_t* in, size_t n, char** json, uint8_t** r
     if (b.has_parity) add(std::string("\"length_parity\": ") + (b.length_parity ? "true" : "false"));
     if (b.has_last_byte) add("\"last_byte\": \"" + hex((const uint8_t*)b.last_byte.data(), b.last_byte.size()) + "\"");
     if (b.has_seams) add("\"seams\": \"" + hex(b.seams, b.seams_len) + "\"");
+    if (b.has_escapes) add("\"escapes\": " + std::to_string(b.escapes));
     j += (i ? ", {" : "{") + e + "}";
     avr::pb_put_block(&o, b);
   }

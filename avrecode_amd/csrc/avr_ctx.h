@@ -51,6 +51,7 @@ struct avr_ctx : avr_host::ErrSink {
   hipStream_t split_stream = nullptr;
   DevBuf sp_in, sp_out, sp_descs, sp_res, sp_ctl, sp_recs, sp_snapn, sp_est, sp_in2, sp_out2;
   size_t split_bytes = 0;   // avr_set_split_bytes / AVR_SPLIT_BYTES (0: no split)
+  bool recode_escaped = false;   // avr_set_recode_escaped / AVR_RECODE_ESCAPED (Block field 17)
   // avr_decompress_pieces: the batch's PieceCtl array, host (alive while its upload is in flight) and device
   std::vector<avr::PieceCtl> pc_host;
   DevBuf pc_ctl;

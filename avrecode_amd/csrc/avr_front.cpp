@@ -12,15 +12,76 @@ namespace avr {
 const char* const kParallelModelTag = "avrecode-amd:P64";     // parallel model, arithmetic_code<uint64_t, uint8_t>
 const char* const kParallel32ModelTag = "avrecode-amd:P32";   // parallel model, P32 coder (avr_engine.h)
 const char* const kChainedModelTag = "avrecode-amd:R16";      // reference model in chains of 16 coded slices
+const char* const kParallelEscTag = "avrecode-amd:P64E";      // P64 with Block field 17 (escapes) somewhere
+const char* const kParallel32EscTag = "avrecode-amd:P32E";    // P32 likewise
 
 int model_of_version(const std::string& v) {
-  if (v == kParallelModelTag) return 1;
-  if (v == kParallel32ModelTag) return 2;
+  if (v == kParallelModelTag || v == kParallelEscTag) return 1;
+  if (v == kParallel32ModelTag || v == kParallel32EscTag) return 2;
   if (v == kChainedModelTag) return 3;
   return v.rfind("avrecode-amd:", 0) == 0 ? -1 : 0;
 }
 const char* version_of_model(int model) {
   return model == 1 ? kParallelModelTag : model == 2 ? kParallel32ModelTag : model == 3 ? kChainedModelTag : nullptr;
+}
+
+bool escaped_version(const std::string& v) { return v == kParallelEscTag || v == kParallel32EscTag; }
+const char* escaped_version_of_model(int model) {
+  return model == 1 ? kParallelEscTag : model == 2 ? kParallel32EscTag : nullptr;
+}
+
+// Emulation prevention removed (7.4.1): every 00 00 03 drops its 03, scanning left to right (the
+// byte after a dropped 03 starts the next match).  The 03 bytes are found by memchr and the runs
+// between them copied whole: a multi-GB stream unescapes at memory speed, not byte by byte.
+std::vector<uint8_t> unescape(const uint8_t* src, size_t n) {
+  std::vector<uint8_t> out(n);
+  size_t i = 0, o = 0;
+  while (i < n) {
+    // the first 00 00 03 at or after i: a 03 at p >= i + 2 with two zeros before it
+    size_t j = n;
+    for (size_t k = i + 2; k < n;) {
+      const uint8_t* p = (const uint8_t*)memchr(src + k, 3, n - k);
+      if (!p) break;
+      const size_t q = (size_t)(p - src);
+      if (src[q - 1] == 0 && src[q - 2] == 0) {
+        j = q - 2;
+        break;
+      }
+      k = q + 1;
+    }
+    const size_t run = (j < n ? j + 2 : n) - i;   // the bytes before the 03 (both zeros included)
+    memcpy(out.data() + o, src + i, run);
+    o += run;
+    i = j < n ? j + 3 : n;
+  }
+  out.resize(o);
+  return out;
+}
+
+// Emulation prevention inserted (7.4.1), the encoder's side of unescape(): the zero bytes are found
+// by memchr and the runs between insertions copied whole.
+std::vector<uint8_t> escape(const uint8_t* src, size_t n) {
+  std::vector<uint8_t> out;
+  out.reserve(n + n / 2 + 1);
+  size_t from = 0;   // src[from ..) is not yet written; no zero of an earlier pair lies before it
+  for (size_t i = 0; i + 2 < n;) {
+    const uint8_t* p = (const uint8_t*)memchr(src + i, 0, n - 2 - i);
+    if (!p) break;
+    i = (size_t)(p - src);
+    if (src[i + 1] != 0) {
+      i += 2;
+      continue;
+    }
+    if (src[i + 2] > 3) {
+      i += 3;
+      continue;
+    }
+    out.insert(out.end(), src + from, src + i + 2);   // ... 00 00, then the 03 before src[i + 2]
+    out.push_back(3);
+    from = i += 2;
+  }
+  out.insert(out.end(), src + from, src + n);
+  return out;
 }
 
 namespace {
@@ -78,34 +139,6 @@ void skip_scaling_list(Bits& b, int size) {
     if (next) next = (last + b.se() + 256) % 256;
     last = next ? next : last;
   }
-}
-
-// Emulation prevention removed (7.4.1): every 00 00 03 drops its 03, scanning left to right (the
-// byte after a dropped 03 starts the next match).  The 03 bytes are found by memchr and the runs
-// between them copied whole: a multi-GB stream unescapes at memory speed, not byte by byte.
-std::vector<uint8_t> unescape(const uint8_t* src, size_t n) {
-  std::vector<uint8_t> out(n);
-  size_t i = 0, o = 0;
-  while (i < n) {
-    // the first 00 00 03 at or after i: a 03 at p >= i + 2 with two zeros before it
-    size_t j = n;
-    for (size_t k = i + 2; k < n;) {
-      const uint8_t* p = (const uint8_t*)memchr(src + k, 3, n - k);
-      if (!p) break;
-      const size_t q = (size_t)(p - src);
-      if (src[q - 1] == 0 && src[q - 2] == 0) {
-        j = q - 2;
-        break;
-      }
-      k = q + 1;
-    }
-    const size_t run = (j < n ? j + 2 : n) - i;   // the bytes before the 03 (both zeros included)
-    memcpy(out.data() + o, src + i, run);
-    o += run;
-    i = j < n ? j + 3 : n;
-  }
-  out.resize(o);
-  return out;
 }
 
 // Does unescape() remove anything: is there a 00 00 03 in the n bytes at src?
@@ -682,6 +715,7 @@ void pb_put_block(std::vector<uint8_t>* o, const PbBlock& b) {
   if (b.has_parity) varint(&m, 5 << 3), varint(&m, b.length_parity ? 1 : 0);
   if (b.has_last_byte) bytes_field(&m, 6, (const uint8_t*)b.last_byte.data(), b.last_byte.size());
   if (b.has_seams) bytes_field(&m, 16, b.seams, b.seams_len);
+  if (b.has_escapes) varint(&m, 17 << 3), varint(&m, b.escapes);
   bytes_field(o, 2, m.data(), m.size());
 }
 
@@ -701,6 +735,7 @@ size_t block_inner_size(const PbBlock& b) {
   if (b.has_parity) m += varint_size(5 << 3) + 1;
   if (b.has_last_byte) m += bytes_field_size(6, b.last_byte.size());
   if (b.has_seams) m += bytes_field_size(16, b.seams_len);
+  if (b.has_escapes) m += varint_size(17 << 3) + varint_size(b.escapes);
   return m;
 }
 size_t put_varint(uint8_t* o, size_t at, uint64_t v) {
@@ -733,6 +768,7 @@ size_t pb_write_block(uint8_t* o, size_t at, const PbBlock& b, std::vector<PbCop
   if (b.has_parity) at = put_varint(o, at, 5 << 3), at = put_varint(o, at, b.length_parity ? 1 : 0);
   if (b.has_last_byte) at = put_bytes(o, at, 6, (const uint8_t*)b.last_byte.data(), b.last_byte.size(), nullptr);
   if (b.has_seams) at = put_bytes(o, at, 16, b.seams, b.seams_len, copies);
+  if (b.has_escapes) at = put_varint(o, at, 17 << 3), at = put_varint(o, at, b.escapes);
   return at;
 }
 
@@ -806,11 +842,12 @@ bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::st
       uint64_t t2, v;
       if (!rd_varint(&q, qe, &t2)) return false;
       const int f2 = (int)(t2 >> 3), w2 = (int)(t2 & 7);
-      if (w2 == 0 && (f2 == 1 || f2 == 3 || f2 == 5)) {
+      if (w2 == 0 && (f2 == 1 || f2 == 3 || f2 == 5 || f2 == 17)) {
         if (!rd_varint(&q, qe, &v)) return false;
         if (f2 == 1) b.has_size = true, b.size = (int64_t)v;
         if (f2 == 3) b.has_skip = true, b.skip_coded = v != 0;
         if (f2 == 5) b.has_parity = true, b.length_parity = v != 0;
+        if (f2 == 17) b.has_escapes = true, b.escapes = v;
       } else if (w2 == 2 && (f2 == 2 || f2 == 4 || f2 == 6 || f2 == 16)) {
         if (!rd_varint(&q, qe, &v) || (uint64_t)(qe - q) < v) return false;
         if (f2 == 2) b.has_literal = true, b.literal = q, b.literal_len = v;

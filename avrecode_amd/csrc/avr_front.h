@@ -116,6 +116,11 @@ struct PbBlock {
   bool has_seams = false;
   const uint8_t* seams = nullptr;
   size_t seams_len = 0;
+  // field 17, this library's own: the block stands for escape(payload), size + escapes file bytes
+  // (a slice whose NAL carries emulation-prevention bytes); size, length_parity and last_byte keep
+  // their meaning on the unescaped payload.  Only under the "E" tags below.
+  bool has_escapes = false;
+  uint64_t escapes = 0;
 };
 void pb_put_block(std::vector<uint8_t>* o, const PbBlock& b);
 // The same bytes written into a buffer sized beforehand: pb_block_size(b) bytes at o + at (returns
@@ -141,11 +146,22 @@ bool pb_read_version(const uint8_t* in, size_t n, std::string* version);
 extern const char* const kParallelModelTag;     // "avrecode-amd:P64"
 extern const char* const kParallel32ModelTag;   // "avrecode-amd:P32"
 extern const char* const kChainedModelTag;      // "avrecode-amd:R16"
+// a parallel-model container with at least one Block field 17 (escapes): a reader from before the
+// field refuses the tag instead of skipping the field and writing a wrong file
+extern const char* const kParallelEscTag;       // "avrecode-amd:P64E"
+extern const char* const kParallel32EscTag;     // "avrecode-amd:P32E"
 // The model a container's Metadata.version names: 0 reference (no tag, or any foreign one), 1
 // parallel / u64 coder, 2 parallel / P32 coder (AVR_MODEL_*); -1 another avrecode-amd format (the
 // round-2 "avrecode-amd:P", ...), which must be refused rather than read as a reference container.
 int model_of_version(const std::string& version);
 const char* version_of_model(int model);   // nullptr for the reference model
+bool escaped_version(const std::string& version);   // one of the two "E" tags
+const char* escaped_version_of_model(int model);    // nullptr for any but the parallel models
+
+// Emulation prevention (7.4.1) from a clean state: a 03 before any byte <= 3 that follows two zero
+// bytes since the last insertion; nothing appended after the last byte.  unescape(escape(x)) == x.
+std::vector<uint8_t> escape(const uint8_t* src, size_t n);
+std::vector<uint8_t> unescape(const uint8_t* src, size_t n);
 constexpr int kSurrogateMarkerBytes = 8;      // recode.cpp:27
 void surrogate_marker(uint64_t seq, uint8_t out[8]);
 

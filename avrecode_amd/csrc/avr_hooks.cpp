@@ -454,7 +454,13 @@ int avr_hooks_compress_begin(avr_ctx* c, const uint8_t* file, size_t n, int mode
   hs->original.assign(file, file + n);
   uint8_t* avrc = nullptr;
   size_t avrc_len = 0;
-  if (int r = avr_compress_file(c, file, n, model, &avrc, &avrc_len)) return r;
+  // a session's container never carries Block field 17: the callbacks serve the slices the plain
+  // segmentation codes
+  const int esc = avr_get_recode_escaped(c);
+  avr_set_recode_escaped(c, 0);
+  const int cr = avr_compress_file(c, file, n, model, &avrc, &avrc_len);
+  avr_set_recode_escaped(c, esc);
+  if (cr) return cr;
   hs->result.assign(avrc, avrc + avrc_len);
   free(avrc);
   std::vector<avr::PbBlock> blocks;
@@ -483,6 +489,11 @@ int avr_hooks_decompress_begin(avr_ctx* c, const uint8_t* avrc, size_t n, avr_ho
     if (int r = guarded(c, [&]() -> int {
           std::string version;
           m = avr::pb_read_version(avrc, n, &version) ? avr::model_of_version(version) : 0;
+          // the surrogate stream a session hands its caller has no form for a block that stands for
+          // escaped bytes
+          if (avr::escaped_version(version))
+            return fail(c, AVR_ERR_UNSUPPORTED, "hooks: a container with re-coded escaped slices (" + version +
+                                                    ") decompresses through the whole-file calls and the plans only");
           if (m == AVR_MODEL_PARALLEL) {
             std::vector<avr::PbBlock> blocks;
             if (avr::pb_parse(avrc, n, &blocks, &version))

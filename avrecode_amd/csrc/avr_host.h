@@ -191,16 +191,23 @@ struct SliceView {
   size_t size;
   bool candidate;
   uint64_t file_pos;   // where the payload stands verbatim in the file (the parse knows), or ~0
+  size_t nal_lo = 0, nal_hi = 0;   // the slice's own NAL in the file, [lo, hi) (0, 0: not known)
 };
 bool recodable_candidate(const avr::SliceInfo& s);
 std::vector<SliceView> views_of(const ParsedFile& pf);
+// escapes (the parallel models' opt-in second chance, AVR_ASSEMBLE_ESCAPED): a slice the search
+// does not find verbatim is searched as escape(payload) inside its own NAL; (*escapes)[i] = the
+// bytes that escape inserted when found[i] is such a hit (the block stands for size + that many
+// file bytes), else 0.  Null: today's segmentation.
 std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const std::vector<SliceView>& sv,
-                                    const std::vector<char>& ok);
-std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const ParsedFile& pf, const std::vector<char>& ok);
+                                    const std::vector<char>& ok, std::vector<uint32_t>* escapes = nullptr);
+std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const ParsedFile& pf, const std::vector<char>& ok,
+                                    std::vector<uint32_t>* escapes = nullptr);
 int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv, const std::vector<const uint8_t*>& found,
                    const std::vector<std::pair<const uint8_t*, size_t>>& recoded, int model, uint8_t** out,
                    size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0,
-                   const std::vector<std::pair<const uint8_t*, size_t>>* seams = nullptr);
+                   const std::vector<std::pair<const uint8_t*, size_t>>* seams = nullptr,
+                   const std::vector<uint32_t>* escapes = nullptr);
 
 // ------------------------------------------------------------------ avr_seams.cpp: the seams codec
 struct SeamCe {
@@ -289,7 +296,9 @@ struct DecJob {
 int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* plan, SplitPlan* sp = nullptr);
 
 // decompressor::run's output (recode.cpp:1338-1357): the literals and the regenerated slices in
-// block order, each slice patched by the last-byte rule (x264 padding correction, 1345-1356).
+// block order, each slice patched by the last-byte rule (x264 padding correction, 1345-1356), then
+// -- a block with field 17 -- escaped: the patch decides the slice's last byte and length, and both
+// can change what is inserted before that byte.
 // slice(k, &p, &len) gives plan slice k's regenerated bytes and returns its status.
 template <class Slice>
 int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>* o) {
@@ -313,6 +322,13 @@ int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>*
       const size_t n = o->size() - o0;
       if ((int)b.length_parity != (int)(n & 1)) o->push_back((uint8_t)b.last_byte[0]);
       else if (n) o->back() = (uint8_t)b.last_byte[0];
+    }
+    if (b.has_escapes) {
+      const std::vector<uint8_t> e = avr::escape(o->data() + o0, o->size() - o0);
+      if (e.size() - (o->size() - o0) != b.escapes)
+        return fail(c, AVR_ERR_FORMAT, "slice " + std::to_string(k) + ": escape count differs from the block's");
+      o->resize(o0);
+      o->insert(o->end(), e.begin(), e.end());
     }
   }
   return AVR_OK;

@@ -24,20 +24,29 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
     return fail(c, AVR_ERR_FORMAT, "unsupported container version " + version + " (expected " + avr::kParallelModelTag +
                                        " or " + avr::kParallel32ModelTag + ")");
   j->parallel = parallel_model(j->model);
+  const bool esc_tag = avr::escaped_version(version);
   // read_packet (recode.cpp:1359-1409): literals and surrogate blocks form the stream -- its layout
   // first, then one allocation, the markers, and the literal copies and 'X' fills on host threads
   uint64_t seq = 1;
   size_t total = 0;
+  // An escaped block (field 17) stands for size + escapes file bytes, and its surrogate occupies as
+  // many: the literals around it hold what places every later byte of the file -- an MP4's NAL
+  // length prefixes and its moov sample tables -- so a surrogate of `size` bytes would shift every
+  // later sample under the parse.
   for (auto& b : j->blocks) {
     if ((int)b.has_literal + (int)b.has_cabac + (int)b.has_skip != 1)
       return fail(c, AVR_ERR_FORMAT, "Invalid input block: must have exactly one type");
+    if (b.has_escapes && (!b.has_cabac || !esc_tag))
+      return fail(c, AVR_ERR_FORMAT, "escapes field on a block that is not coded, or under a tag without E");
     if (b.has_literal) {
       total += b.literal_len;
     } else if (b.has_cabac) {
       if (!b.has_size) return fail(c, AVR_ERR_FORMAT, "CABAC block requires size field.");
       if (b.size < avr::kSurrogateMarkerBytes || b.size > ((int64_t)1 << 31))
         return fail(c, AVR_ERR_FORMAT, "Invalid coded block size for surrogate: " + std::to_string(b.size));
-      total += (size_t)b.size;
+      if (b.has_escapes && (b.escapes == 0 || b.escapes > (uint64_t)b.size / 2 + 1))
+        return fail(c, AVR_ERR_FORMAT, "Invalid escapes count in coded block: " + std::to_string(b.escapes));
+      total += (size_t)b.size + (size_t)b.escapes;
     } else if (!b.skip_coded) {
       return fail(c, AVR_ERR_FORMAT, "Unknown input block type");
     }
@@ -55,9 +64,10 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
         at += b.literal_len;
       } else if (b.has_cabac) {
         avr::surrogate_marker(seq++, j->stream.data() + at);
-        fills.push_back({at + 8, nullptr, (size_t)b.size - 8});
-        if (b.size > 8) skips.push_back({at + 8, at + (size_t)b.size});
-        at += (size_t)b.size;
+        const size_t sur = (size_t)b.size + (size_t)b.escapes;   // the marker, then 'X' fill
+        fills.push_back({at + 8, nullptr, sur - 8});
+        if (sur > 8) skips.push_back({at + 8, at + sur});
+        at += sur;
       }
     }
     parallel_copies(fills, j->stream.data(), (uint8_t)'X');
@@ -80,7 +90,7 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
     if (next_coded >= j->blocks.size())
       return fail(c, AVR_ERR_FORMAT, "Coded block expected, but not recorded in the compressed data.");
     const avr::PbBlock& b = j->blocks[next_coded];
-    if ((size_t)b.size != s.size) return fail(c, AVR_ERR_FORMAT, "Invalid surrogate block size.");
+    if ((size_t)b.size + (size_t)b.escapes != s.size) return fail(c, AVR_ERR_FORMAT, "Invalid surrogate block size.");
     avr_slice_desc d = desc_from_header(s);
     if (b.has_cabac) {
       uint8_t mk[8];
@@ -210,10 +220,13 @@ struct avr_dec_plan {
 namespace {
 
 // splice_job's output laid out: the literal and regenerated-slice copies, the last-byte patches
-// (position, byte) and the total length.
+// (position, byte) and the total length.  An escaped block (field 17) is one more copy job: its
+// bytes -- regenerated, patched, then escaped -- stand in `side`, which the layout's caller keeps
+// until the copies are done.
 int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* regen, size_t regen_len,
                   const uint64_t* offsets, const uint32_t* lens, std::vector<avr::PbCopy>* copies,
-                  std::vector<std::pair<size_t, uint8_t>>* patches, size_t* total) {
+                  std::vector<std::pair<size_t, uint8_t>>* patches, std::vector<std::vector<uint8_t>>* side,
+                  size_t* total) {
   const DecJob& j = h->job;
   const int ns = (int)h->plan.descs.size();
   // every slice's regenerated bytes inside regen and within its own output capacity
@@ -235,6 +248,19 @@ int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* r
     if (k < 0) return AVR_ERR_FORMAT;          // "Not all blocks were decoded." (recode.cpp:1354)
     if (status[k]) return AVR_ERR_FORMAT;      // the slice failed to decode
     const size_t len = lens[k];
+    if (b.has_escapes) {
+      std::vector<uint8_t> p(regen + offsets[k], regen + offsets[k] + len);
+      if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {
+        if ((int)b.length_parity != (int)(len & 1)) p.push_back((uint8_t)b.last_byte[0]);
+        else if (len) p.back() = (uint8_t)b.last_byte[0];
+      }
+      std::vector<uint8_t> e = avr::escape(p.data(), p.size());
+      if (e.size() - p.size() != b.escapes) return AVR_ERR_FORMAT;   // not the count the block recorded
+      side->push_back(std::move(e));
+      copies->push_back({at, side->back().data(), side->back().size()});
+      at += side->back().size();
+      continue;
+    }
     if (len) copies->push_back({at, regen + offsets[k], len});
     size_t m = len;
     if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {   // recode.cpp:1345-1356
@@ -418,8 +444,9 @@ int avr_dec_plan_splice(const avr_dec_plan* h, const int32_t* status, const uint
   return guarded(nullptr, [&]() -> int {
     std::vector<avr::PbCopy> copies;
     std::vector<std::pair<size_t, uint8_t>> patches;
+    std::vector<std::vector<uint8_t>> side;
     size_t total = 0;
-    if (int r = splice_layout(h, status, regen, regen_len, offsets, lens, &copies, &patches, &total)) return r;
+    if (int r = splice_layout(h, status, regen, regen_len, offsets, lens, &copies, &patches, &side, &total)) return r;
     *out_len = total;
     if (total > out_cap || (total && !out)) return AVR_ERR_INVALID_ARGUMENT;
     write_splice(copies, patches, out);
@@ -472,8 +499,9 @@ int avr_splice_container(const uint8_t* avrc, size_t n, int n_slices, const int3
     if (ns != n_slices) return AVR_ERR_INVALID_ARGUMENT;
     std::vector<avr::PbCopy> copies;
     std::vector<std::pair<size_t, uint8_t>> patches;
+    std::vector<std::vector<uint8_t>> side;
     size_t total = 0;
-    if (int r = splice_layout(&h, status, regen, regen_len, offsets, lens, &copies, &patches, &total)) return r;
+    if (int r = splice_layout(&h, status, regen, regen_len, offsets, lens, &copies, &patches, &side, &total)) return r;
     uint8_t* o = host_alloc(total);
     if (!o) return AVR_ERR_OUT_OF_MEMORY;
     write_splice(copies, patches, o);

@@ -332,7 +332,8 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
 
 
 def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = None,
-                     model: int = MODEL_PARALLEL, split_bytes: int | None = None, run_range=None) -> bytes | None:
+                     model: int = MODEL_PARALLEL, split_bytes: int | None = None, run_range=None,
+                     escaped: bool = False) -> bytes | None:
     """PARALLEL-model compress of one file across all ranks; the container is returned on rank 0.
 
     Every rank parses the file (host), takes its contiguous slice range (partition), runs it on its
@@ -350,6 +351,10 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     at ctx.split_bytes = s; sharded_compress(ctx, x, split_bytes=ctx.split_bytes) is the whole-file
     container.  A slice is one rank's: the cut pieces help the decompress, a single slice's compress
     walk stays one chain.
+    escaped (pass ctx.recode_escaped): rank 0 assembles with the second search of
+    Context.recode_escaped (avr_assemble_container_opts, ASSEMBLE_ESCAPED) -- the ranks' work does not
+    change, since every candidate slice is compressed and checked anyway -- and the container is
+    byte-identical to ctx.compress(data, model) with that option on.
     run_range(part) -> compress_range's tuple replaces the device step (CPU tests)."""
     import torch
     import torch.distributed as dist
@@ -381,8 +386,9 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     st, blob, offs, lens = g
     if gs is not None:
         _, sblob, soffs, slens = gs
-        return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, seams=(sblob, soffs, slens))
-    return assemble_container(data, st, blob, offs, lens, model=model, ps=ps)
+        return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, seams=(sblob, soffs, slens),
+                                  escaped=escaped)
+    return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, escaped=escaped)
 
 
 def _gather_device(ctx, device):
@@ -471,7 +477,9 @@ def sharded_decompress(ctx, avrc: bytes, device=None, run_range=None) -> bytes |
     A container whose long slices were cut (Block field 16) goes by units instead: planned with
     pieces, partitioned by the units' re-coded bytes, each rank's units through
     decompress_units_range (run_range then gets the unit batch of subset_units and returns per-unit
-    outputs), and on rank 0 collapse_units before DecompressPlan.splice."""
+    outputs), and on rank 0 collapse_units before DecompressPlan.splice.
+    A block that stands for escaped bytes (Block field 17, Context.recode_escaped) changes neither
+    route: descriptors and units are in the unescaped domain, and rank 0's splice escapes."""
     import torch
     import torch.distributed as dist
 

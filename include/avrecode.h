@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define AVRECODE_ABI_VERSION 8  /* 8: split compress of slice batches (avr_split_plan, avr_compress_split_slices,
+#define AVRECODE_ABI_VERSION 9  /* 9: escaped slices re-coded (avr_set_recode_escaped, Block field 17, the "E" tags,
+                                 *    avr_assemble_container_opts, avr_escape_payload);
+                                 * 8: split compress of slice batches (avr_split_plan, avr_compress_split_slices,
                                  *    avr_seams_build, avr_stage_pieces, avr_verify_units, avr_assemble_container_seams);
                                  * 7: piece plans (avr_dec_plan_load_pieces, avr_decompress_pieces, avr_pack_pieces);
                                  * 6: the parallel model's long-slice split (avr_set_split_bytes, Block field 16);
@@ -101,6 +103,33 @@ void avr_free(void* p);
  * restatement (oracle/oracle_seams.c). */
 int avr_set_split_bytes(avr_ctx* ctx, size_t split_bytes);
 size_t avr_get_split_bytes(const avr_ctx* ctx);
+
+/* Slices whose NAL unit carries emulation-prevention bytes (00 00 03, H.264 7.4.1) re-coded: an
+ * option of the parallel models, off by default.  The segmentation looks for a slice's unescaped
+ * payload verbatim in the file, as the reference does (recode.cpp:1275-1297); such a slice's payload
+ * stands nowhere, so it is stored skip_coded although the device has re-coded and verified it.  With
+ * the option on, a candidate slice of status 0 that the search misses is searched once more as
+ * E = escape(payload) (avr_escape_payload), inside its own NAL and after the previous coded block;
+ * a hit makes it a coded block that stands for E's size + k file bytes and carries Block field 17
+ * ("escapes", varint k >= 1); size, length_parity and last_byte keep their meaning on the unescaped
+ * payload, and so do the q values of a field 16 on the same block.  A container with at least one
+ * field 17 is tagged "avrecode-amd:P64E" / "avrecode-amd:P32E" (same models; a reader from before
+ * ABI 9 refuses the tag instead of skipping the field and writing a wrong file); one without keeps
+ * the plain tag and the plain bytes.  The decompress regenerates the slice, applies the last-byte
+ * patch, escapes, and checks that exactly k bytes were inserted (AVR_ERR_FORMAT otherwise; also for
+ * field 17 on a block without cabac, under a tag without E, k = 0 or k > size / 2 + 1).  Every
+ * decompress call takes such containers (whole files, avr_plan_decompress, the dec plans, piece
+ * plans) except the hooks decompress session: AVR_ERR_UNSUPPORTED there.  Read by
+ * avr_compress_file(s) and avr_roundtrip_file(s) for AVR_MODEL_PARALLEL / AVR_MODEL_PARALLEL32; the
+ * reference and chained models ignore it (their bytes are pinned), and hooks compress sessions
+ * never write the field.  Default: the environment's AVR_RECODE_ESCAPED (non-zero: on), else 0. */
+int avr_set_recode_escaped(avr_ctx* ctx, int on);
+int avr_get_recode_escaped(const avr_ctx* ctx);
+/* 7.4.1 from a clean state: a 03 inserted before any byte <= 3 that follows two zero bytes since
+ * the last insertion, nothing appended after the last byte.  *len = the escaped length (at most
+ * n + n / 2); written to dst when it fits cap, else AVR_ERR_INVALID_ARGUMENT with *len still set
+ * (dst may be NULL with cap 0 to ask for the length).  Host only. */
+int avr_escape_payload(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* len);
 
 /* ------------------------------------------------------------------ whole files (host memory) */
 /* in: an MP4 (avcC) or Annex-B H.264 file.  *out: serialized Recoded protobuf (recode.proto). */
@@ -513,6 +542,20 @@ int avr_assemble_container_seams_parsed(const uint8_t* file, size_t n, int model
                                         const uint32_t* lens, const uint8_t* seams, size_t seams_len,
                                         const uint64_t* seam_offsets, const uint32_t* seam_lens, uint8_t** out,
                                         size_t* out_len);
+/* Every avr_assemble_container* above in one call, with a flags word.  descs / arena NULL: the file is
+ * parsed here (avr_assemble_container); else avr_parse_stream's (avr_assemble_container_parsed).
+ * seams as in avr_assemble_container_seams (NULL: none).  flags = 0: those calls exactly.
+ * AVR_ASSEMBLE_ESCAPED: the second search of avr_set_recode_escaped, so rank 0 of a sharded
+ * compress writes what avr_compress_file writes with the option on; with descs it parses the file
+ * once more when some coded slice's payload does not stand verbatim (a descriptor does not carry
+ * its NAL's place).  AVR_ERR_INVALID_ARGUMENT for the flag with a model that is not one of the two
+ * parallel ones, and for unknown flag bits. */
+enum { AVR_ASSEMBLE_ESCAPED = 1 };
+int avr_assemble_container_opts(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
+                                const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
+                                size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, const uint8_t* seams,
+                                size_t seams_len, const uint64_t* seam_offsets, const uint32_t* seam_lens,
+                                uint32_t flags, uint8_t** out, size_t* out_len);
 /* The two device steps that let a rank check its split slices without their bytes leaving the device
  * (all pointers device pointers, nothing synchronised).
  * avr_stage_pieces: the units' streams -- unit k's d_desc[k].payload_size bytes at d_out + d_src[k],
@@ -539,7 +582,7 @@ int avr_verify_units(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_slice
 /* Container codec check (host only): parse a Recoded protobuf (recode.proto:1-19) with the
  * library's own wire codec -- the one avr_decompress_file uses -- and return (a) its fields as JSON,
  * {"version": null | hex, "blocks": [{"size": int, "literal": hex, "skip_coded": bool, "cabac": hex,
- * "length_parity": bool, "last_byte": hex}, ...]} with only the fields present, and (b) the message
+ * "length_parity": bool, "last_byte": hex, "seams": hex, "escapes": int}, ...]} with only the fields present, and (b) the message
  * re-serialised by the library's writer (the one avr_compress_file uses; Metadata.version only).
  * Both buffers are malloc'd (avr_free).  AVR_ERR_FORMAT when the bytes are not a Recoded message. */
 int avr_container_describe(const uint8_t* in, size_t n, char** json, uint8_t** reserialized, size_t* len);
@@ -584,7 +627,11 @@ int avr_hooks_compress_begin(avr_ctx* ctx, const uint8_t* file, size_t n, int mo
  * plans it; an avr_hook_init_decoder that reaches a slice not yet regenerated regenerates it on
  * the device together with at most 31 coded slices after it, and avr_hooks_end regenerates the
  * rest for the output file.  A reference-model container is regenerated whole at begin (its
- * estimators chain across slices).  AVR_HOOKS_EAGER=1 in the environment: always whole. */
+ * estimators chain across slices).  AVR_HOOKS_EAGER=1 in the environment: always whole.
+ * A container with re-coded escaped slices (Block field 17; "avrecode-amd:P64E" / "P32E") is
+ * refused with AVR_ERR_UNSUPPORTED: *stream has no form for a block that stands for escaped bytes.
+ * It decompresses through the whole-file calls and the plans.  Compress sessions never write the
+ * field, whatever avr_set_recode_escaped says. */
 int avr_hooks_decompress_begin(avr_ctx* ctx, const uint8_t* avrc, size_t n, avr_hooks_session** out,
                                const uint8_t** stream, size_t* stream_len);
 /* Streaming compress: the caller's demuxer hands the file's bytes to the session as it reads them
