@@ -25,7 +25,7 @@ __all__ = [
     "SLICE_RESULT", "SynthParams", "lib", "parse_stream", "assemble_container", "neighbor_tables",
     "plan_decompress", "splice_container", "container_model", "source_sha", "library_path", "EXPORTED_SYMBOLS",
     "seams_of_container", "SPLIT_SLOT", "SplitPlan", "split_plan", "seams_build", "escape_payload",
-    "ASSEMBLE_ESCAPED",
+    "ASSEMBLE_ESCAPED", "ASSEMBLE_SPLIT32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +40,7 @@ MODEL_PARALLEL32 = 2
 MODEL_CHAINED = 3   # the reference model in chains of CHAIN_SLICES coded slices ("avrecode-amd:R16")
 CHAIN_SLICES = 16
 ASSEMBLE_ESCAPED = 1   # avr_assemble_container_opts' flag: the second search of Context.recode_escaped
+ASSEMBLE_SPLIT32 = 2   # and: seams fields for MODEL_PARALLEL32, under the "P32S" / "P32SE" tags (Context.split_p32)
 SPLIT_BYTES_DEFAULT = 98304   # the parallel model's long-slice split (Context.split_bytes), unless AVR_SPLIT_BYTES
 MODEL_NAMES = {MODEL_REFERENCE: "R", MODEL_PARALLEL: "P", MODEL_PARALLEL32: "P32", MODEL_CHAINED: "C"}
 
@@ -67,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "avr_split_plan", "avr_seams_build", "avr_assemble_container_seams", "avr_assemble_container_seams_parsed",
     "avr_compress_split_slices", "avr_stage_pieces", "avr_verify_units",
     "avr_set_recode_escaped", "avr_get_recode_escaped", "avr_escape_payload", "avr_assemble_container_opts",
+    "avr_set_split_p32", "avr_get_split_p32", "avr_compress_split_slices_m", "avr_decompress_pieces_m",
 )
 
 # avr_slice_desc / avr_slice_result (include/avrecode.h), C layout
@@ -241,6 +243,10 @@ def lib() -> ctypes.CDLL:
     L.avr_last_phase_times.argtypes = [vp, vp]
     L.avr_set_split_bytes.argtypes = [vp, sz]
     L.avr_set_recode_escaped.argtypes = [vp, i32]
+    L.avr_set_split_p32.argtypes = [vp, i32]
+    L.avr_get_split_p32.argtypes = [vp]
+    L.avr_decompress_pieces_m.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, i32, sz, vp, vp, vp, vp]
+    L.avr_compress_split_slices_m.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32, sz, vp, vp, vp]
     L.avr_get_recode_escaped.argtypes = [vp]
     L.avr_escape_payload.argtypes = [vp, sz, vp, sz, psz]
     L.avr_assemble_container_opts.argtypes = [vp, sz, i32, vp, i32, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp,
@@ -588,7 +594,7 @@ def seams_build(descs, arena, res, slots, cuts, piece_end, recs, rec_stride: int
 
 def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, lens: np.ndarray,
                        model: int = MODEL_PARALLEL, ps: "ParsedStream | None" = None, as_array: bool = False,
-                       out: "np.ndarray | None" = None, seams=None, escaped: bool = False):
+                       out: "np.ndarray | None" = None, seams=None, escaped: bool = False, split32: bool = False):
     """Recoded container from per-slice outputs gathered from the ranks (avr_assemble_container; with ps =
     parse_stream(data) already in hand, avr_assemble_container_parsed: no second parse).  recoded:
     bytes or a uint8 array.  model: the model / coder the outputs were made with (PARALLEL, PARALLEL32,
@@ -598,12 +604,17 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
     returns the view of it that holds the container.  seams: (blob, offsets, lens) -- slice k's
     Block field 16 is blob[offsets[k] : offsets[k] + lens[k]], length 0 for none -- or a list of one
     bytes object per slice (b"" for none): the container of a split compress
-    (avr_assemble_container_seams; MODEL_PARALLEL only, not with out).  escaped: the second search of
+    (avr_assemble_container_seams; MODEL_PARALLEL, or MODEL_PARALLEL32 with split32; not with out).
+    escaped: the second search of
     Context.recode_escaped (avr_assemble_container_opts with ASSEMBLE_ESCAPED; the parallel models
-    only, not with out), so that the result is what ctx.compress writes with the option on.  Host only."""
+    only, not with out), so that the result is what ctx.compress writes with the option on.
+    split32 (ASSEMBLE_SPLIT32; MODEL_PARALLEL32 only, not with out): seams are allowed for that model
+    and a container that holds one is tagged P32S / P32SE, what ctx.compress writes with
+    Context.split_p32 on.  Host only."""
     L = lib()
-    if escaped and out is not None:
-        raise ValueError("assemble_container: escaped cannot be combined with out")
+    flags = (ASSEMBLE_ESCAPED if escaped else 0) | (ASSEMBLE_SPLIT32 if split32 else 0)
+    if flags and out is not None:
+        raise ValueError("assemble_container: escaped / split32 cannot be combined with out")
     p, n, keep = _buf(data)
     st = np.ascontiguousarray(status, dtype=np.int32)
     of = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -624,7 +635,7 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
         if len(so) != len(st) or len(sl) != len(st) or len(of) != len(st) or len(ln) != len(st):
             raise ValueError("assemble_container: status / offsets / lens / seams need one entry per slice")
         sp, sn, keep3 = _buf(sb)
-        if escaped:
+        if flags:
             dd = np.ascontiguousarray(ps.descs) if ps is not None else None
             if dd is not None and len(dd) != len(st):
                 raise ValueError("assemble_container: status / offsets / lens need one entry per parsed slice")
@@ -632,7 +643,7 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
                                               ps.arena.ctypes.data if ps is not None else None,
                                               ps.arena.nbytes if ps is not None else 0, st.ctypes.data, rp, rn,
                                               of.ctypes.data, ln.ctypes.data, sp, sn, so.ctypes.data, sl.ctypes.data,
-                                              ASSEMBLE_ESCAPED, ctypes.byref(res), ctypes.byref(olen))
+                                              flags, ctypes.byref(res), ctypes.byref(olen))
         elif ps is not None:
             dd = np.ascontiguousarray(ps.descs)
             if len(dd) != len(st):
@@ -660,14 +671,14 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
         if r != AVR_OK:
             raise AvrError(r, f"avr_assemble_container_into failed (container {olen.value} B, buffer {out.nbytes} B)")
         return out[:olen.value]
-    if escaped:
+    if flags:
         dd = np.ascontiguousarray(ps.descs) if ps is not None else None
         if len(of) != len(st) or len(ln) != len(st) or (dd is not None and len(dd) != len(st)):
             raise ValueError("assemble_container: status / offsets / lens need one entry per parsed slice")
         r = L.avr_assemble_container_opts(p, n, model, dd.ctypes.data if dd is not None else None, len(st),
                                           ps.arena.ctypes.data if ps is not None else None,
                                           ps.arena.nbytes if ps is not None else 0, st.ctypes.data, rp, rn,
-                                          of.ctypes.data, ln.ctypes.data, None, 0, None, None, ASSEMBLE_ESCAPED,
+                                          of.ctypes.data, ln.ctypes.data, None, 0, None, None, flags,
                                           ctypes.byref(res), ctypes.byref(olen))
     elif ps is not None:
         dd = np.ascontiguousarray(ps.descs)
@@ -807,6 +818,18 @@ class Context:
     @split_bytes.setter
     def split_bytes(self, v: int):
         self._check(lib().avr_set_split_bytes(self._h, int(v)), "avr_set_split_bytes")
+
+    @property
+    def split_p32(self) -> bool:
+        """The long-slice split for MODEL_PARALLEL32 (avr_set_split_p32; default off, or the
+        environment's AVR_SPLIT_P32): with it the whole-file compress and roundtrip of that model read
+        split_bytes as MODEL_PARALLEL's do, and a container that holds a cut slice is tagged
+        avrecode-amd:P32S (P32SE with recode_escaped's field as well).  Reading needs no option."""
+        return bool(lib().avr_get_split_p32(self._h))
+
+    @split_p32.setter
+    def split_p32(self, on: bool):
+        self._check(lib().avr_set_split_p32(self._h, 1 if on else 0), "avr_set_split_p32")
 
     @property
     def recode_escaped(self) -> bool:
@@ -964,16 +987,17 @@ class Context:
         return f"{name}<{1 if decompress else 0}, false, {'true' if p32 else 'false'}>"
 
     def decompress_pieces(self, d_desc, pieces, n, max_w, max_h, d_recs, n_recs, rec_stride, d_in, d_out, d_res,
-                          stream=None):
-        """avr_decompress_pieces: a batch of pieces and whole progressive slices of MODEL_PARALLEL, one
+                          stream=None, model: int = MODEL_PARALLEL):
+        """avr_decompress_pieces_m: a batch of pieces and whole progressive slices of model
+        (MODEL_PARALLEL or MODEL_PARALLEL32: one call runs one coder), one
         workgroup per unit.  pieces: the units' PIECE array on the HOST (checked there before the
         launch); d_recs: the n_recs seam records its seam fields index, on the device."""
         pc = np.ascontiguousarray(pieces, dtype=PIECE)
         if len(pc) != n:
             raise ValueError("decompress_pieces: one PIECE per unit")
-        self._check(lib().avr_decompress_pieces(self._h, self._ptr(d_desc), pc.ctypes.data, n, max_w, max_h,
-                                                self._ptr(d_recs), n_recs, rec_stride, self._ptr(d_in),
-                                                self._ptr(d_out), self._ptr(d_res), self._stream(stream)),
+        self._check(lib().avr_decompress_pieces_m(self._h, int(model), self._ptr(d_desc), pc.ctypes.data, n, max_w,
+                                                  max_h, self._ptr(d_recs), n_recs, rec_stride, self._ptr(d_in),
+                                                  self._ptr(d_out), self._ptr(d_res), self._stream(stream)),
                     "decompress_pieces")
 
     def pack_pieces(self, d_desc, d_pieces, d_res, n, d_out, d_packed, d_offsets, d_kept, d_status, stream=None):
@@ -988,18 +1012,19 @@ class Context:
     seams_build = staticmethod(seams_build)
 
     def compress_split_slices(self, d_desc, n, max_w, max_h, d_in, d_out, d_res, slots, split_bytes, d_recs, n_recs,
-                              rec_stride, d_cuts, d_piece_end, stream=None):
-        """avr_compress_split_slices: the split walk over a batch of progressive MODEL_PARALLEL slices,
-        each cut as it is walked.  slots: split_plan's SPLIT_SLOT array on the HOST (checked there
+                              rec_stride, d_cuts, d_piece_end, stream=None, model: int = MODEL_PARALLEL):
+        """avr_compress_split_slices_m: the split walk over a batch of progressive slices re-coded with
+        model's coder (MODEL_PARALLEL or MODEL_PARALLEL32), each cut as it is walked.  slots: split_plan's SPLIT_SLOT array on the HOST (checked there
         before the launch); d_recs / d_cuts (uint32[n]) / d_piece_end (uint32[n_recs]): what the walk
         writes, on the device, the latter two zeroed on the stream first."""
         sl = np.ascontiguousarray(slots, dtype=SPLIT_SLOT)
         if len(sl) != n:
             raise ValueError("compress_split_slices: one SPLIT_SLOT per slice")
         P = self._ptr
-        self._check(lib().avr_compress_split_slices(self._h, P(d_desc), n, max_w, max_h, P(d_in), P(d_out), P(d_res),
-                                                    sl.ctypes.data, int(split_bytes), P(d_recs), n_recs, rec_stride,
-                                                    P(d_cuts), P(d_piece_end), self._stream(stream)),
+        self._check(lib().avr_compress_split_slices_m(self._h, int(model), P(d_desc), n, max_w, max_h, P(d_in),
+                                                      P(d_out), P(d_res), sl.ctypes.data, int(split_bytes),
+                                                      P(d_recs), n_recs, rec_stride, P(d_cuts), P(d_piece_end),
+                                                      self._stream(stream)),
                     "compress_split_slices")
 
     def stage_pieces(self, d_desc, d_src, n, d_out, out_len, d_arena, arena_cap, d_offsets, d_status, stream=None):

@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import KEEP_ALL, PIECE, SLICE_DESC, SLICE_RESULT, MODEL_PARALLEL, Context, ParsedStream
+from . import KEEP_ALL, PIECE, SLICE_DESC, SLICE_RESULT, MODEL_PARALLEL, MODEL_PARALLEL32, Context, ParsedStream
 
 
 def _dev_bytes(a: np.ndarray, device) -> torch.Tensor:
@@ -167,7 +167,7 @@ class UnitBatch:
     the pieces of split slices) on the device.  Buffers in unit order: d_desc, d_in (the streams),
     d_recs (the seam records), d_work (the regenerated bytes), d_res.
     decompress(): the units that are pieces -- they start at a seam, stop after n_mbs macroblocks or
-    keep only their share -- through avr_decompress_pieces, the whole slices (field, MBAFF and
+    keep only their share -- through avr_decompress_pieces_m on the model's coder, the whole slices (field, MBAFF and
     over-wide ones among them, which are never cut) through avr_decompress_slices, one launch after
     the other on the stream; the descriptor rows of each launch are gathered, and its result rows
     scattered back, by index with torch.  pack(): one avr_pack_pieces over all units."""
@@ -189,8 +189,8 @@ class UnitBatch:
     def decompress(self, model: int = MODEL_PARALLEL, stream=None):
         part, n = self.part, self.n
         idx_p, idx_r = np.flatnonzero(self.is_piece), np.flatnonzero(~self.is_piece)
-        if len(idx_p) and model != MODEL_PARALLEL:
-            raise ValueError("UnitBatch: pieces exist in MODEL_PARALLEL containers only")
+        if len(idx_p) and model not in (MODEL_PARALLEL, MODEL_PARALLEL32):
+            raise ValueError("UnitBatch: pieces exist in the parallel models' containers only")
         with torch.cuda.stream(stream) if stream is not None else _null():
             for idx, pieces in ((idx_p, True), (idx_r, False)):
                 if not len(idx):
@@ -203,7 +203,7 @@ class UnitBatch:
                 if pieces:
                     self.ctx.decompress_pieces(dd, part.pieces[idx], len(idx), int(part.descs["mb_width"][idx].max()),
                                                part.max_mb_height, self.d_recs, self.n_recs, part.rec_stride,
-                                               self.d_in, self.d_work, dr, stream)
+                                               self.d_in, self.d_work, dr, stream, model=model)
                 else:
                     self.ctx.decompress_slices(dd, len(idx), part.max_mb_width, part.max_mb_height, self.d_in,
                                                self.d_work, dr, model, stream)
@@ -230,8 +230,8 @@ class UnitBatch:
 
 class SplitBatch:
     """A rank's split candidates (split_plan of ps.descs at split_bytes: every slice of ps must be one)
-    on the device, compressed as the whole-file MODEL_PARALLEL compress compresses them: each slice
-    cut as it is walked, its pieces' streams one after the other in d_out.  roundtrip() runs, on one
+    on the device, compressed as the whole-file compress of model (MODEL_PARALLEL, or MODEL_PARALLEL32
+    with Context.split_p32) compresses them: each slice cut as it is walked, its pieces' streams one after the other in d_out.  roundtrip() runs, on one
     stream,
       compress()    avr_compress_split_slices
       read_back()   waits for it; cuts, piece ends, records and results to the host, where the unit
@@ -244,9 +244,11 @@ class SplitBatch:
     and the halves are callable one by one in that order.  recoded() / verdicts() / seams() give the
     host what a container needs."""
 
-    def __init__(self, ctx: Context, ps: ParsedStream, split_bytes: int, device=None):
+    def __init__(self, ctx: Context, ps: ParsedStream, split_bytes: int, device=None, model: int = MODEL_PARALLEL):
         from . import split_plan
-        self.ctx, self.ps, self.split_bytes = ctx, ps, int(split_bytes)
+        if model not in (MODEL_PARALLEL, MODEL_PARALLEL32):
+            raise ValueError("SplitBatch: the parallel models only")
+        self.ctx, self.ps, self.split_bytes, self.model = ctx, ps, int(split_bytes), int(model)
         self.device = dev = torch.device("cuda", ctx.device) if device is None else device
         self.n = n = len(ps.descs)
         self.plan = plan = split_plan(ps.descs, split_bytes)
@@ -273,7 +275,7 @@ class SplitBatch:
         p = self.plan
         self.ctx.compress_split_slices(self.d_desc, self.n, self.max_w, self.ps.max_mb_height, self.d_in, self.d_out,
                                        self.d_res_c, p.slots, self.split_bytes, self.d_recs, p.n_recs, p.rec_stride,
-                                       self.d_cuts, self.d_piece_end, stream)
+                                       self.d_cuts, self.d_piece_end, stream, model=self.model)
 
     def read_back(self, stream=None):
         from . import SEAM_HEAD, SLICE_CODER
@@ -339,7 +341,7 @@ class SplitBatch:
         if self.nu:
             self.ctx.decompress_pieces(self.d_units, self.pieces, self.nu, self.max_w, self.ps.max_mb_height,
                                        self.d_recs, self.plan.n_recs, self.plan.rec_stride, self.d_arena,
-                                       self.d_unit_work, self.d_unit_res, stream)
+                                       self.d_unit_work, self.d_unit_res, stream, model=self.model)
 
     def pack(self, stream=None):
         nu, dev = self.nu, self.device

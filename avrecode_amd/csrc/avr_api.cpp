@@ -316,9 +316,10 @@ hipError_t reserve_parallel(avr_ctx* c, int n, int max_w, bool field_lane = fals
 constexpr int32_t kStatusNoRoundtrip = AVR_SLICE_NO_ROUNDTRIP;
 
 // ------------------------------------------------------------------------ the long-slice split
-// The parallel model (on arithmetic_code<uint64_t, uint8_t>) cuts a long progressive slice at
-// macroblock-row starts into pieces re-coded with fresh models, so its decompress runs one workgroup
-// per piece instead of one chain (the reference decodes a slice as one chain, recode.cpp:1411-1520).
+// The parallel model (on arithmetic_code<uint64_t, uint8_t>; on the P32 coder with avr_set_split_p32)
+// cuts a long progressive slice at macroblock-row starts into pieces re-coded with fresh models, so
+// its decompress runs one workgroup per piece instead of one chain (the reference decodes a slice as
+// one chain, recode.cpp:1411-1520).
 // The format is this library's own, restated and checked by the oracle (oracle/oracle_seams.c,
 // avr_oracle.h):
 //   - a cut candidate every 8 split_bytes CABAC bits decoded (at a row start, half a piece still
@@ -420,6 +421,7 @@ struct SplitJob {
   uint32_t nrec = 0;
   size_t stride = 0;
   int max_w = 1;
+  uint32_t coder = 0;   // coder_flag(model): the walk's and the verify launch's coder
   EventPair ev;   // around the split compress kernel
 };
 
@@ -456,7 +458,7 @@ int split_begin(avr_ctx* c, SplitJob* j, size_t split_bytes, uint32_t flags) {
   return launch_split_walk(c, c->sp_descs.as<avr_slice_desc>(), n, j->max_w, c->sp_in.as<uint8_t>(),
                            c->sp_out.as<uint8_t>(), c->sp_res.as<avr_slice_result>(), j->slots.data(),
                            c->sp_recs.as<uint8_t>(), (int)j->nrec, j->stride, cuts, cuts + n, split_bytes,
-                           flags & avr::kFlagBill, st, &j->ctl, &c->sp_ctl, &j->ev);
+                           (flags & avr::kFlagBill) | j->coder, st, &j->ctl, &c->sp_ctl, &j->ev);
 }
 
 // One launch of pieces on the split stream: descs / ctl uploaded, records already in sp_recs,
@@ -472,6 +474,15 @@ struct SplitPending {
   const void* out_dev = nullptr;
   size_t res_bytes = 0, out_bytes = 0;
 };
+// The device buffers of a pieces launch besides its input and output: the context's first set, or the
+// second (a decompress call with split blocks of both coders: one launch per coder, avr_ctx.h)
+struct SplitLane {
+  DevBuf *descs, *res, *ctl, *recs;
+};
+SplitLane split_lane(avr_ctx* c, int second) {
+  return second ? SplitLane{&c->sp2_descs, &c->sp2_res, &c->sp2_ctl, &c->sp2_recs}
+                : SplitLane{&c->sp_descs, &c->sp_res, &c->sp_ctl, &c->sp_recs};
+}
 bool split_timing() { return getenv("AVR_SPLIT_TIMING") != nullptr; }
 int split_wait(avr_ctx* c, SplitPending* pend) {
   if (!pend->ev.e0) return AVR_OK;
@@ -486,7 +497,7 @@ int split_wait(avr_ctx* c, SplitPending* pend) {
 }
 int split_launch(avr_ctx* c, std::vector<avr_slice_desc>& d, const std::vector<avr::PieceCtl>& ctl, const uint8_t* in_dev,
                  int max_w, size_t stride, uint32_t flags, std::vector<avr_slice_result>* res, Bytes* out,
-                 DevBuf* out_dev, SplitPending* pending = nullptr) {
+                 DevBuf* out_dev, SplitPending* pending = nullptr, int second = 0) {
   const int n = (int)d.size();
   uint64_t total = 0;
   for (auto& x : d) place_output(&x, &total);
@@ -495,20 +506,21 @@ int split_launch(avr_ctx* c, std::vector<avr_slice_desc>& d, const std::vector<a
   if (!n) return AVR_OK;
   hipStream_t st = c->split_stream;
   HIP_TRY(c, out_dev->reserve(total + 4096));
-  HIP_TRY(c, c->sp_descs.reserve(sizeof(avr_slice_desc) * n));
-  HIP_TRY(c, c->sp_res.reserve(sizeof(avr_slice_result) * n));
-  HIP_TRY(c, hipMemcpyAsync(c->sp_descs.p, d.data(), sizeof(avr_slice_desc) * n, hipMemcpyHostToDevice, st));
+  const SplitLane ln = split_lane(c, second);
+  HIP_TRY(c, ln.descs->reserve(sizeof(avr_slice_desc) * n));
+  HIP_TRY(c, ln.res->reserve(sizeof(avr_slice_result) * n));
+  HIP_TRY(c, hipMemcpyAsync(ln.descs->p, d.data(), sizeof(avr_slice_desc) * n, hipMemcpyHostToDevice, st));
   avr::SplitArgs sa;
-  sa.recs = c->sp_recs.as<uint8_t>();
+  sa.recs = ln.recs->as<uint8_t>();
   sa.rec_stride = (uint32_t)stride;
   SplitPending local;
   SplitPending* pend = pending ? pending : &local;
   if (int r = pend->ev.create(c)) return r;
-  if (int r = launch_split_ctl(c, 1, c->sp_descs.as<avr_slice_desc>(), n, max_w, in_dev, out_dev->as<uint8_t>(),
-                               c->sp_res.as<avr_slice_result>(), ctl.data(), &c->sp_ctl, sa, flags, st, &pend->ev))
+  if (int r = launch_split_ctl(c, 1, ln.descs->as<avr_slice_desc>(), n, max_w, in_dev, out_dev->as<uint8_t>(),
+                               ln.res->as<avr_slice_result>(), ctl.data(), ln.ctl, sa, flags, st, &pend->ev))
     return r;
   pend->res = res->data();
-  pend->res_dev = c->sp_res.p;
+  pend->res_dev = ln.res->p;
   pend->res_bytes = sizeof(avr_slice_result) * n;
   pend->out = out->data();
   pend->out_dev = out_dev->p;
@@ -563,7 +575,8 @@ int split_finish(avr_ctx* c, SplitJob* j, bool verify, std::vector<SplitOut>* ou
   HIP_TRY(c, hipMemcpyAsync(c->sp_in2.p, vp.arena.data(), vp.arena.size(), hipMemcpyHostToDevice, st));
   std::vector<avr_slice_result> r3;
   Bytes out3;
-  if (int e = split_launch(c, vp.descs, pc, c->sp_in2.as<uint8_t>(), j->max_w, j->stride, 0, &r3, &out3, &c->sp_out2))
+  if (int e = split_launch(c, vp.descs, pc, c->sp_in2.as<uint8_t>(), j->max_w, j->stride, j->coder, &r3, &out3,
+                           &c->sp_out2))
     return e;
   for (int k = 0; k < n; k++) {
     if (first[k] < 0) continue;
@@ -637,7 +650,9 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   // the parallel model's long slices (split_slot): the split job, its first pass on the split
   // stream beside the batch (cand_of = -2 - index there)
   SplitJob sj;
-  const size_t split_bytes = model == AVR_MODEL_PARALLEL ? c->split_bytes : 0;
+  const size_t split_bytes =
+      model == AVR_MODEL_PARALLEL || (model == AVR_MODEL_PARALLEL32 && c->split_p32) ? c->split_bytes : 0;
+  sj.coder = coder_flag(model);
   std::vector<std::vector<int>> cand_of(nf);
   for (int f = 0; f < nf; f++) {
     cand_of[f].assign(pf[f].slices.size(), -1);
@@ -812,7 +827,9 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
   // u64 coder; on the P32 coder
   Plan plans[3];   // indexed by plan_of(model): the chained model's chains go to the reference plan
   Plan& rp = plans[AVR_MODEL_REFERENCE];
-  SplitPlan sp;    // the pieces of split blocks
+  // the pieces of split blocks, one plan per coder (the coder is a compile-time parameter of the
+  // split kernel, so one launch cannot hold both): [0] the u64 coder's, [1] the P32 coder's
+  SplitPlan sps[2];
   auto plan_of = [](int m) { return parallel_model(m) ? m : (int)AVR_MODEL_REFERENCE; };
   for (int f = 0; f < nf; f++) {
     out[f] = nullptr;
@@ -824,6 +841,7 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
     Plan* plan = &plans[plan_of(m)];
     const size_t n0 = plan->descs.size();
     if (!parallel) rp.file_first.push_back((int)n0);
+    SplitPlan& sp = sps[m == AVR_MODEL_PARALLEL32];
     const size_t s_descs = sp.plan.descs.size(), s_recs = sp.recs.size(), s_arena = sp.plan.arena.size();
     st[f] = decompress_setup(c, in[f], in_len[f], &jobs[f], plan, &sp);
     if (st[f]) {   // drop whatever the failed file left
@@ -847,20 +865,28 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
   std::vector<avr_slice_result> res_of[3];
   std::vector<uint8_t> out_of[3];
   pc.mark_demux();
-  // the pieces of split blocks on the split stream, beside the other plans
-  std::vector<avr_slice_result> pr;
-  Bytes po;
-  SplitPending pend;
+  // the pieces of split blocks on the split stream, beside the other plans: the two coders' launches
+  // one after the other there, each with its own input / output / record buffers
+  std::vector<avr_slice_result> prs[2];
+  Bytes pos[2];
+  SplitPending pends[2];
   double t_split = 0;
-  if (!sp.plan.descs.empty()) {
+  for (int i = 0; i < 2; i++) {
+    SplitPlan& sp = sps[i];
+    if (sp.plan.descs.empty()) continue;
     const double t = now_s();
     hipStream_t ss = c->split_stream;
-    HIP_TRY(c, c->sp_in.reserve(sp.plan.arena.size() + 4096));
-    HIP_TRY(c, c->sp_recs.reserve(sp.recs.size() + 64));
-    HIP_TRY(c, hipMemcpyAsync(c->sp_in.p, sp.plan.arena.data(), sp.plan.arena.size(), hipMemcpyHostToDevice, ss));
-    HIP_TRY(c, hipMemcpyAsync(c->sp_recs.p, sp.recs.data(), sp.recs.size(), hipMemcpyHostToDevice, ss));
-    if (int r = split_launch(c, sp.plan.descs, sp.ctl, c->sp_in.as<uint8_t>(), sp.plan.max_w, sp.stride, flags, &pr, &po,
-                             &c->sp_out, &pend)) {
+    DevBuf* in_dev = i ? &c->sp_in2 : &c->sp_in;
+    DevBuf* recs_dev = split_lane(c, i).recs;
+    auto launch = [&]() -> int {
+      HIP_TRY(c, in_dev->reserve(sp.plan.arena.size() + 4096));
+      HIP_TRY(c, recs_dev->reserve(sp.recs.size() + 64));
+      HIP_TRY(c, hipMemcpyAsync(in_dev->p, sp.plan.arena.data(), sp.plan.arena.size(), hipMemcpyHostToDevice, ss));
+      HIP_TRY(c, hipMemcpyAsync(recs_dev->p, sp.recs.data(), sp.recs.size(), hipMemcpyHostToDevice, ss));
+      return split_launch(c, sp.plan.descs, sp.ctl, in_dev->as<uint8_t>(), sp.plan.max_w, sp.stride,
+                          flags | (i ? avr::kFlagP32 : 0u), &prs[i], &pos[i], i ? &c->sp_out2 : &c->sp_out, &pends[i], i);
+    };
+    if (int r = launch()) {   // what is in flight still reads this call's host buffers
       (void)hipStreamSynchronize(ss);
       return r;
     }
@@ -880,11 +906,19 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
       return r;
     }
   }
-  if (!sp.plan.descs.empty()) {   // the pieces of split blocks, then each block spliced
+  if (!sps[0].plan.descs.empty() || !sps[1].plan.descs.empty()) {   // the pieces of split blocks, then each block spliced
     const double t = now_s();
-    if (int r = split_wait(c, &pend)) return r;
+    for (SplitPending& pend : pends)
+      if (int r = split_wait(c, &pend)) {
+        drain();
+        return r;
+      }
     for (int f = 0; f < nf; f++) {
       if (st[f]) continue;
+      const int i = jobs[f].model == AVR_MODEL_PARALLEL32;   // the file's blocks are in its coder's plan
+      const SplitPlan& sp = sps[i];
+      const std::vector<avr_slice_result>& pr = prs[i];
+      const Bytes& po = pos[i];
       for (SplitBlock& x : jobs[f].splits) {
         for (int k = x.first; k < x.first + x.pieces; k++)
           if (pr[k].status == 0)
@@ -1270,6 +1304,7 @@ int avr_create(int device, avr_ctx** out) {
     c->split_bytes = e ? (size_t)strtoull(e, nullptr, 10) : kSplitBytesDefault;
   }
   if (const char* e = getenv("AVR_RECODE_ESCAPED")) c->recode_escaped = strtol(e, nullptr, 10) != 0;
+  if (const char* e = getenv("AVR_SPLIT_P32")) c->split_p32 = strtol(e, nullptr, 10) != 0;
   if (const char* e = getenv("AVR_FIELD_LANE"); !e || strcmp(e, "0") != 0) {
     if (hipStreamCreateWithFlags(&c->fld_stream, hipStreamNonBlocking) != hipSuccess) return AVR_ERR_DEVICE;
     for (auto& ev : c->fld_ev)
@@ -1303,6 +1338,13 @@ int avr_set_split_bytes(avr_ctx* c, size_t bytes) {
   return AVR_OK;
 }
 size_t avr_get_split_bytes(const avr_ctx* c) { return c ? c->split_bytes : 0; }
+
+int avr_set_split_p32(avr_ctx* c, int on) {
+  if (!c) return AVR_ERR_INVALID_ARGUMENT;
+  c->split_p32 = on != 0;
+  return AVR_OK;
+}
+int avr_get_split_p32(const avr_ctx* c) { return c && c->split_p32; }
 
 int avr_set_recode_escaped(avr_ctx* c, int on) {
   if (!c) return AVR_ERR_INVALID_ARGUMENT;
@@ -1651,10 +1693,11 @@ int avr_pack_outputs(avr_ctx* c, const avr_slice_desc* d_desc, const avr_slice_r
 // The units of a piece plan on the device: the split kernel (one workgroup per unit) on the caller's
 // stream, from the caller's device-resident descriptors, streams and seam records.  The piece array
 // is checked here, before anything is launched: a record index outside d_recs would be read.
-int avr_decompress_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* pieces, int n, int max_w,
-                          int max_h, const uint8_t* d_recs, int n_recs, size_t rec_stride, const uint8_t* d_in,
-                          uint8_t* d_out, avr_slice_result* d_res, void* stream) {
-  if (!c || n < 0 || n_recs < 0 || (n && (!d_desc || !pieces || !d_in || !d_out || !d_res)) || (n_recs && !d_recs) ||
+// model: which of the two split kernels (the coder is a template parameter of the kernel).
+int avr_decompress_pieces_m(avr_ctx* c, int model, const avr_slice_desc* d_desc, const avr_piece* pieces, int n,
+                            int max_w, int max_h, const uint8_t* d_recs, int n_recs, size_t rec_stride,
+                            const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res, void* stream) {
+  if (!c || !parallel_model(model) || n < 0 || n_recs < 0 || (n && (!d_desc || !pieces || !d_in || !d_out || !d_res)) || (n_recs && !d_recs) ||
       max_w <= 0 || max_h <= 0)
     return AVR_ERR_INVALID_ARGUMENT;
   if (max_w > avr::kMringCols || rec_stride < avr::seam_rec_bytes(max_w) || rec_stride > UINT32_MAX)
@@ -1671,9 +1714,15 @@ int avr_decompress_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_pi
     avr::SplitArgs sa;
     sa.recs = const_cast<uint8_t*>(d_recs);
     sa.rec_stride = (uint32_t)rec_stride;
-    return launch_split_ctl(c, 1, d_desc, n, max_w, d_in, d_out, d_res, c->pc_host.data(), &c->pc_ctl, sa, 0,
-                            (hipStream_t)stream, nullptr);
+    return launch_split_ctl(c, 1, d_desc, n, max_w, d_in, d_out, d_res, c->pc_host.data(), &c->pc_ctl, sa,
+                            coder_flag(model), (hipStream_t)stream, nullptr);
   });
+}
+int avr_decompress_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* pieces, int n, int max_w,
+                          int max_h, const uint8_t* d_recs, int n_recs, size_t rec_stride, const uint8_t* d_in,
+                          uint8_t* d_out, avr_slice_result* d_res, void* stream) {
+  return avr_decompress_pieces_m(c, AVR_MODEL_PARALLEL, d_desc, pieces, n, max_w, max_h, d_recs, n_recs, rec_stride, d_in,
+                                 d_out, d_res, stream);
 }
 
 int avr_pack_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* d_pieces, const avr_slice_result* d_res,
@@ -1690,11 +1739,11 @@ int avr_pack_pieces(avr_ctx* c, const avr_slice_desc* d_desc, const avr_piece* d
 // The split walk (launch_split_walk) for a caller's device-resident batch (include/avrecode.h, ABI 8):
 // on the caller's stream into the caller's records, cut counts and piece ends.  The slots are checked
 // here, before anything is launched: a record outside d_recs would be written.
-int avr_compress_split_slices(avr_ctx* c, const avr_slice_desc* d_desc, int n, int max_w, int max_h,
-                              const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res,
-                              const avr_split_slot* slots, size_t split_bytes, uint8_t* d_recs, int n_recs,
-                              size_t rec_stride, uint32_t* d_cuts, uint32_t* d_piece_end, void* stream) {
-  if (!c || n < 0 || n_recs < 0 || (n && (!d_desc || !d_in || !d_out || !d_res || !slots || !d_cuts)) ||
+int avr_compress_split_slices_m(avr_ctx* c, int model, const avr_slice_desc* d_desc, int n, int max_w, int max_h,
+                                const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res,
+                                const avr_split_slot* slots, size_t split_bytes, uint8_t* d_recs, int n_recs,
+                                size_t rec_stride, uint32_t* d_cuts, uint32_t* d_piece_end, void* stream) {
+  if (!c || !parallel_model(model) || n < 0 || n_recs < 0 || (n && (!d_desc || !d_in || !d_out || !d_res || !slots || !d_cuts)) ||
       (n_recs && (!d_recs || !d_piece_end)) || max_w <= 0 || max_h <= 0)
     return AVR_ERR_INVALID_ARGUMENT;
   if (max_w > avr::kMringCols || rec_stride < avr::seam_rec_bytes(max_w) || rec_stride > UINT32_MAX)
@@ -1712,8 +1761,16 @@ int avr_compress_split_slices(avr_ctx* c, const avr_slice_desc* d_desc, int n, i
   return guarded(c, [&]() -> int {
     HIP_TRY(c, hipSetDevice(c->device));
     return launch_split_walk(c, d_desc, n, max_w, d_in, d_out, d_res, slots, d_recs, n_recs, rec_stride, d_cuts,
-                             d_piece_end, split_bytes, 0, (hipStream_t)stream, &c->sc_host, &c->sc_ctl, nullptr);
+                             d_piece_end, split_bytes, coder_flag(model), (hipStream_t)stream, &c->sc_host, &c->sc_ctl,
+                             nullptr);
   });
+}
+int avr_compress_split_slices(avr_ctx* c, const avr_slice_desc* d_desc, int n, int max_w, int max_h,
+                              const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res,
+                              const avr_split_slot* slots, size_t split_bytes, uint8_t* d_recs, int n_recs,
+                              size_t rec_stride, uint32_t* d_cuts, uint32_t* d_piece_end, void* stream) {
+  return avr_compress_split_slices_m(c, AVR_MODEL_PARALLEL, d_desc, n, max_w, max_h, d_in, d_out, d_res, slots,
+                                     split_bytes, d_recs, n_recs, rec_stride, d_cuts, d_piece_end, stream);
 }
 
 int avr_stage_pieces(avr_ctx* c, avr_slice_desc* d_desc, const uint64_t* d_src, int n, const uint8_t* d_out,

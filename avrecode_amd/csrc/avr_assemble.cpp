@@ -160,9 +160,12 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
              const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out,
              size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0, const SeamsArg& sa = SeamsArg(),
              uint32_t flags = 0) {
-  // the escaped second chance is the parallel models' own format
-  if ((flags & ~(uint32_t)AVR_ASSEMBLE_ESCAPED) || ((flags & AVR_ASSEMBLE_ESCAPED) && !parallel_model(model)))
+  // the escaped second chance is the parallel models' own format, the opt-in split the P32 coder's
+  if ((flags & ~(uint32_t)(AVR_ASSEMBLE_ESCAPED | AVR_ASSEMBLE_SPLIT32)) ||
+      ((flags & AVR_ASSEMBLE_ESCAPED) && !parallel_model(model)) ||
+      ((flags & AVR_ASSEMBLE_SPLIT32) && model != AVR_MODEL_PARALLEL32))
     return AVR_ERR_INVALID_ARGUMENT;
+  const bool seams_ok = model == AVR_MODEL_PARALLEL || (flags & AVR_ASSEMBLE_SPLIT32);
   std::vector<char> ok(sv.size(), 0);
   std::vector<std::pair<const uint8_t*, size_t>> blobs(sv.size(), {nullptr, 0}), fields;
   if (sa.p) fields.assign(sv.size(), {nullptr, 0});
@@ -173,8 +176,9 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
       blobs[i] = {recoded + offsets[i], lens[i]};
     }
     if (sa.p && sa.lens[i]) {
-      // a seams field belongs to a coded slice of the parallel model on the u64 coder, and lies in the blob
-      if (model != AVR_MODEL_PARALLEL || !ok[i] || sa.offsets[i] > sa.len || sa.lens[i] > sa.len - sa.offsets[i])
+      // a seams field belongs to a coded slice of the parallel model -- on the u64 coder, or on the P32
+      // coder with AVR_ASSEMBLE_SPLIT32 -- and lies in the blob
+      if (!seams_ok || !ok[i] || sa.offsets[i] > sa.len || sa.lens[i] > sa.len - sa.offsets[i])
         return AVR_ERR_INVALID_ARGUMENT;
       fields[i] = {sa.p + sa.offsets[i], sa.lens[i]};
     }
@@ -332,7 +336,7 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
                    const std::vector<std::pair<const uint8_t*, size_t>>& recoded, int model, uint8_t** out,
                    size_t* out_len, uint8_t* dst, size_t cap,
                    const std::vector<std::pair<const uint8_t*, size_t>>* seams, const std::vector<uint32_t>* escapes) {
-  bool any_escapes = false;
+  bool any_escapes = false, any_seams = false;
   std::vector<avr::PbBlock> blocks;
   blocks.reserve(2 * sv.size() + 1);
   size_t prev_end = 0;
@@ -356,7 +360,8 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
       b.has_cabac = true;
       b.cabac = recoded[i].first;
       b.cabac_len = recoded[i].second;
-      if (seams && (*seams)[i].second) b.has_seams = true, b.seams = (*seams)[i].first, b.seams_len = (*seams)[i].second;
+      if (seams && (*seams)[i].second)
+        b.has_seams = any_seams = true, b.seams = (*seams)[i].first, b.seams_len = (*seams)[i].second;
     } else {
       b.has_skip = true;
       b.skip_coded = true;
@@ -371,8 +376,11 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
   lit.literal_len = n - prev_end;
   blocks.push_back(lit);
   std::vector<uint8_t> md;
-  // a container without field 17 keeps the plain tag and the plain bytes
-  const char* tag = any_escapes ? avr::escaped_version_of_model(model) : avr::version_of_model(model);
+  // a container without field 17 keeps the plain tag and the plain bytes; so does a P32 one without
+  // field 16, and one with it says so in its tag (P32S / P32SE; P64's seams need none)
+  const char* tag = any_seams && model == AVR_MODEL_PARALLEL32 ? avr::split32_version_of(any_escapes)
+                    : any_escapes                              ? avr::escaped_version_of_model(model)
+                                                               : avr::version_of_model(model);
   if (any_escapes && !tag) return fail(nullptr, AVR_ERR_INVALID_ARGUMENT, "escapes on a model without the field");
   if (tag) avr::pb_put_metadata_version(&md, tag);
   size_t total = md.size();

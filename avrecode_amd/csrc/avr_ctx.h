@@ -50,7 +50,12 @@ struct avr_ctx : avr_host::ErrSink {
   // long slices' first pass overlaps the rest of the batch, and its own estimator scratch
   hipStream_t split_stream = nullptr;
   DevBuf sp_in, sp_out, sp_descs, sp_res, sp_ctl, sp_recs, sp_snapn, sp_est, sp_in2, sp_out2;
+  // the second pieces launch of a decompress call that holds split blocks of both coders (one kernel
+  // runs one coder): its input and output are sp_in2 / sp_out2, its descriptors, results, piece
+  // controls and records these; sp_est is shared, the two launches being ordered on split_stream
+  DevBuf sp2_descs, sp2_res, sp2_ctl, sp2_recs;
   size_t split_bytes = 0;   // avr_set_split_bytes / AVR_SPLIT_BYTES (0: no split)
+  bool split_p32 = false;   // avr_set_split_p32 / AVR_SPLIT_P32: AVR_MODEL_PARALLEL32 reads split_bytes too
   bool recode_escaped = false;   // avr_set_recode_escaped / AVR_RECODE_ESCAPED (Block field 17)
   // avr_decompress_pieces: the batch's PieceCtl array, host (alive while its upload is in flight) and device
   std::vector<avr::PieceCtl> pc_host;

@@ -14,10 +14,14 @@ const char* const kParallel32ModelTag = "avrecode-amd:P32";   // parallel model,
 const char* const kChainedModelTag = "avrecode-amd:R16";      // reference model in chains of 16 coded slices
 const char* const kParallelEscTag = "avrecode-amd:P64E";      // P64 with Block field 17 (escapes) somewhere
 const char* const kParallel32EscTag = "avrecode-amd:P32E";    // P32 likewise
+// P32 with Block field 16 (seams: the long-slice split) somewhere, and with field 17 as well: tags
+// of their own, so a reader from before P32 had a split refuses them instead of misreading Block.cabac
+const char* const kParallel32SplitTag = "avrecode-amd:P32S";
+const char* const kParallel32SplitEscTag = "avrecode-amd:P32SE";
 
 int model_of_version(const std::string& v) {
   if (v == kParallelModelTag || v == kParallelEscTag) return 1;
-  if (v == kParallel32ModelTag || v == kParallel32EscTag) return 2;
+  if (v == kParallel32ModelTag || v == kParallel32EscTag || v == kParallel32SplitTag || v == kParallel32SplitEscTag) return 2;
   if (v == kChainedModelTag) return 3;
   return v.rfind("avrecode-amd:", 0) == 0 ? -1 : 0;
 }
@@ -25,7 +29,11 @@ const char* version_of_model(int model) {
   return model == 1 ? kParallelModelTag : model == 2 ? kParallel32ModelTag : model == 3 ? kChainedModelTag : nullptr;
 }
 
-bool escaped_version(const std::string& v) { return v == kParallelEscTag || v == kParallel32EscTag; }
+bool escaped_version(const std::string& v) {
+  return v == kParallelEscTag || v == kParallel32EscTag || v == kParallel32SplitEscTag;
+}
+bool split32_version(const std::string& v) { return v == kParallel32SplitTag || v == kParallel32SplitEscTag; }
+const char* split32_version_of(bool escaped) { return escaped ? kParallel32SplitEscTag : kParallel32SplitTag; }
 const char* escaped_version_of_model(int model) {
   return model == 1 ? kParallelEscTag : model == 2 ? kParallel32EscTag : nullptr;
 }

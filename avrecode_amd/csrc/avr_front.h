@@ -150,12 +150,16 @@ extern const char* const kChainedModelTag;      // "avrecode-amd:R16"
 // field refuses the tag instead of skipping the field and writing a wrong file
 extern const char* const kParallelEscTag;       // "avrecode-amd:P64E"
 extern const char* const kParallel32EscTag;     // "avrecode-amd:P32E"
+extern const char* const kParallel32SplitTag;     // "avrecode-amd:P32S": P32 with Block field 16 somewhere
+extern const char* const kParallel32SplitEscTag;  // "avrecode-amd:P32SE": with field 17 as well
 // The model a container's Metadata.version names: 0 reference (no tag, or any foreign one), 1
 // parallel / u64 coder, 2 parallel / P32 coder (AVR_MODEL_*); -1 another avrecode-amd format (the
 // round-2 "avrecode-amd:P", ...), which must be refused rather than read as a reference container.
 int model_of_version(const std::string& version);
 const char* version_of_model(int model);   // nullptr for the reference model
-bool escaped_version(const std::string& version);   // one of the two "E" tags
+bool escaped_version(const std::string& version);   // one of the "E" tags
+bool split32_version(const std::string& version);   // one of the two P32 "S" tags (P64's split has no tag of its own)
+const char* split32_version_of(bool escaped);
 const char* escaped_version_of_model(int model);    // nullptr for any but the parallel models
 
 // Emulation prevention (7.4.1) from a clean state: a 03 before any byte <= 3 that follows two zero

@@ -494,7 +494,7 @@ int avr_hooks_decompress_begin(avr_ctx* c, const uint8_t* avrc, size_t n, avr_ho
           if (avr::escaped_version(version))
             return fail(c, AVR_ERR_UNSUPPORTED, "hooks: a container with re-coded escaped slices (" + version +
                                                     ") decompresses through the whole-file calls and the plans only");
-          if (m == AVR_MODEL_PARALLEL) {
+          if (parallel_model(m)) {   // either coder's split (P32's: the "P32S" tag)
             std::vector<avr::PbBlock> blocks;
             if (avr::pb_parse(avrc, n, &blocks, &version))
               for (const auto& b : blocks) split = split || b.has_seams;

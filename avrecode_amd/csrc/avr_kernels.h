@@ -64,12 +64,17 @@ struct SplitArgs {
                                    //   one entry per record (from PieceCtl::snap)
 };
 // compress (mode 0: whole long slices, cut as they are walked) / decompress (1: the pieces) with the
-// parallel model on arithmetic_code<uint64_t, uint8_t> (avr_k_split.hip): one workgroup per
-// descriptor, min(n, resident slots) workgroups; est holds that many estimator scratches
+// parallel model on arithmetic_code<uint64_t, uint8_t> (avr_k_split.hip) or, with kFlagP32 in flags,
+// on the P32 coder (avr_k_split32.hip): one workgroup per descriptor, min(n, resident slots)
+// workgroups; est holds that many estimator scratches
 int split_grid(int n, int max_mb_width);
 hipError_t launch_split(int mode, const EngineTables* T, const avr_slice_desc* descs, int n, int max_mb_width,
                         const uint8_t* in, uint8_t* out, avr_slice_result* res, uint16_t* est, const SplitArgs& sp,
                         uint32_t flags, hipStream_t stream);
+// the P32 kernels of launch_split, which has sized the launch (grid, lds) and set the flags
+hipError_t launch_split32(int mode, const EngineTables* T, const avr_slice_desc* descs, int n, int grid, size_t lds,
+                          const uint8_t* in, uint8_t* out, avr_slice_result* res, uint16_t* est, const SplitArgs& sp,
+                          uint32_t flags, hipStream_t stream);
 // flags: kFlagBill (1) = the coders bill per CodingType into avr_slice_result.bill
 hipError_t launch_slices(int mode, bool sequential, const EngineTables* T, const avr_slice_desc* descs, int n,
                          int max_mb_width, const uint8_t* in, uint8_t* out, avr_slice_result* res, uint16_t* est,

@@ -25,6 +25,8 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
                                        " or " + avr::kParallel32ModelTag + ")");
   j->parallel = parallel_model(j->model);
   const bool esc_tag = avr::escaped_version(version);
+  // seams (field 16) belong to the u64 coder's containers and, of the P32 coder's, to those tagged S
+  const bool seams_ok = j->model == AVR_MODEL_PARALLEL || avr::split32_version(version);
   // read_packet (recode.cpp:1359-1409): literals and surrogate blocks form the stream -- its layout
   // first, then one allocation, the markers, and the literal copies and 'X' fills on host threads
   uint64_t seq = 1;
@@ -104,7 +106,7 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
     }
     if (b.has_cabac && b.has_seams) {   // a split block: its pieces go to the split plan
       if (!sp) return fail(c, AVR_ERR_UNSUPPORTED, "split slices (block field 16) decompress through the whole-file calls only");
-      if (j->model != AVR_MODEL_PARALLEL || d.structure != AVR_STRUCT_FRAME || d.mb_width > SplitPlan::kMringCols)
+      if (!seams_ok || d.structure != AVR_STRUCT_FRAME || d.mb_width > SplitPlan::kMringCols)
         return fail(c, AVR_ERR_FORMAT, "seams on a block that cannot be split");
       SeamsDecoded sd;
       if (!seams_decode(b.seams, b.seams_len, d, sp->stride, &sd))

@@ -124,13 +124,14 @@ AVR_FI void parallel_slice(uint8_t* smem, const EngineTables* G, const avr_slice
 }
 
 // The long-slice split's launches (avr_kernels.h SplitArgs): progressive frame slices and pieces of
-// the parallel model on arithmetic_code<uint64_t, uint8_t>, the model row in LDS; each workgroup
+// the parallel model on either of its coders, the model row in LDS; each workgroup
 // takes descriptors blockIdx.x, blockIdx.x + gridDim.x, ... (a grid of at most the resident slots:
 // one estimator scratch per workgroup).  Compress: whole long slices in a single walk, each cut as
 // it is walked -- the cut records taken (PieceCtl::snap) and the model started afresh at every cut;
 // or pieces (seam >= 0: started from a record, n_mbs > 0: stopped at the next cut).  Decompress: the
 // pieces, from records the host wrote (the container's seams).
-template <int MODE>
+// P32: the same launches on the P32 coder (avr_k_split32.hip; the cuts do not depend on the coder).
+template <int MODE, bool P32 = false>
 __global__ __launch_bounds__(192, 4) void slices_split_kernel(const EngineTables* G, const avr_slice_desc* descs, int n,
                                                              const uint8_t* in, uint8_t* out, avr_slice_result* res,
                                                              uint16_t* est_scratch, SplitArgs sp, uint32_t flags) {
@@ -144,8 +145,8 @@ __global__ __launch_bounds__(192, 4) void slices_split_kernel(const EngineTables
       loaded = true;
       if (threadIdx.x < 64) cell = cu_cell();
     }
-    parallel_slice<MODE, false, false, false, true>(smem, G, descs, s, in, out, res,
-                                                    est_scratch + (size_t)blockIdx.x * kEstGlobal, flags, cell, &sp);
+    parallel_slice<MODE, false, P32, false, true>(smem, G, descs, s, in, out, res,
+                                                  est_scratch + (size_t)blockIdx.x * kEstGlobal, flags, cell, &sp);
   }
 }
 

@@ -2052,6 +2052,12 @@ AVR_FI void begin_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w, const avr_slice
       }
     }
   } else if (MODE == MODE_DECOMPRESS) {
+    // A piece (SPL) starts its decoder like a slice.  The P32 decoder's window runs up to 4 bytes
+    // past its stream, the u64 one's up to 8: in_fill_call loads no byte at or past in.limit (the
+    // piece's own length, read_limit) and gives zeros there, and every layout a piece comes from
+    // (append_pieces, avr_stage_pieces, the piece plans' arena) follows each stream with >= 16 zero
+    // bytes besides -- so a piece reads what the encoder's finish assumed, never its neighbour's
+    // bytes, and the AVR_SLICE_OVERREAD check below stops a damaged piece at its own end.
     rd_init(w.rd, w.in);
   } else {
     ce_init(w.ce);
@@ -2108,6 +2114,16 @@ AVR_FI void walker_slice(Walker<MODE, RM, FLD, P32, SPL, SRD>& w, const avr_slic
   if constexpr (SPL) {
     cut = w.cut;
     if (!status && w.piece_mbs && !cut) status = AVR_SLICE_NO_END;   // end_of_slice inside a non-last piece
+    // A P32 piece has to have used up its stream.  The decoder reads 4 bytes at rd_init and one per
+    // renormalisation: next = 4 + R.  The encoder made a digit at each of the same R renormalisations
+    // and its finish k more, 0 <= k <= 4 (re_finish shifts while low != 0, and low has 32 bits), all of
+    // them written out by the end: the stream is L = R + k bytes.  So next - L = 4 - k is in [0, 4]
+    // for a stream the encoder made, whether the piece ends at a cut or at end_of_slice.  A damaged
+    // piece decodes other decisions and stops, by macroblock count or at the picture's end, somewhere
+    // else in its stream (the format has no checksum of a stream; this is the check it allows).
+    if constexpr (P32 && MODE == MODE_DECOMPRESS) {
+      if (!status && w.in.limit && w.rd.next - w.in.limit > 4u) status = AVR_SLICE_CODER;
+    }
   }
   int stop_ok = 1;
   if (MODE == MODE_COMPRESS && !status && !cut) {

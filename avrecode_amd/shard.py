@@ -41,7 +41,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import (MODEL_CHAINED, MODEL_PARALLEL, PIECE, SLICE_NO_END, DecompressPlan, ParsedStream, assemble_container,
+from . import (MODEL_CHAINED, MODEL_PARALLEL, MODEL_PARALLEL32, PIECE, SLICE_NO_END, DecompressPlan, ParsedStream, assemble_container,
                container_model, parse_stream, plan_decompress, seams_of_container, splice_container)
 
 
@@ -257,11 +257,13 @@ def collapse_units(pieces, status, offsets, lens):
     return st.astype(np.int32), off.astype(np.uint64), ln.astype(np.uint32)
 
 
-def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL, split_bytes: int = 0):
+def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL, split_bytes: int = 0,
+                   split_p32: bool = False):
     """This rank's slice range of a sharded compress on its GPU: (flat uint8 tensor, status, offsets,
     lens, seams) with slice k's re-coded bytes at flat[offsets[k] : offsets[k] + lens[k]] and status 0
     where it is to be coded (-1: stored skip_coded).  split_bytes 0 (or a model other than
-    MODEL_PARALLEL): every slice whole through batch.DeviceBatch, seams None.  Otherwise the range's
+    MODEL_PARALLEL, or MODEL_PARALLEL32 with split_p32): every slice whole through batch.DeviceBatch,
+    seams None.  Otherwise the range's
     split candidates (split_plan at split_bytes, coded slices only) go through batch.SplitBatch on a
     side stream beside the DeviceBatch of the rest; the two are joined before the packs; seams is one
     bytes per slice (b"" without a cut).  A candidate whose walk, cut check or verify fails is
@@ -274,7 +276,8 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
     n = len(part.descs)
     dev = torch.device("cuda", ctx.device) if device is None else device
     cand = np.zeros(n, bool)
-    if split_bytes and model == MODEL_PARALLEL:
+    split_bytes = split_bytes if model == MODEL_PARALLEL or (model == MODEL_PARALLEL32 and split_p32) else 0
+    if split_bytes:
         cand = split_plan(part.descs, split_bytes).candidate & (part.descs["coded"] != 0)
     if not cand.any():
         b = DeviceBatch(ctx, part, device=dev)
@@ -286,11 +289,11 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
         offs = d_off.cpu().numpy()[:n].astype(np.int64)
         lens = np.where(res["status"] == 0, res["out_len"], 0).astype(np.int64)
         status = np.where(v == 1, 0, -1).astype(np.int64)
-        return flat, status, offs, lens, ([b""] * n if split_bytes and model == MODEL_PARALLEL else None)
+        return flat, status, offs, lens, ([b""] * n if split_bytes else None)
     idx_c, idx_r = np.flatnonzero(cand), np.flatnonzero(~cand)
     cur = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(dev)
-    sb = SplitBatch(ctx, select(part, idx_c), split_bytes, device=dev)
+    sb = SplitBatch(ctx, select(part, idx_c), split_bytes, device=dev, model=model)
     side.wait_stream(cur)                   # after the batch's uploads and zero fills on the current stream
     sb.compress(side)                       # the long walks first, beside everything below
     b = None
@@ -333,7 +336,7 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
 
 def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = None,
                      model: int = MODEL_PARALLEL, split_bytes: int | None = None, run_range=None,
-                     escaped: bool = False) -> bytes | None:
+                     escaped: bool = False, split_p32: bool = False) -> bytes | None:
     """PARALLEL-model compress of one file across all ranks; the container is returned on rank 0.
 
     Every rank parses the file (host), takes its contiguous slice range (partition), runs it on its
@@ -343,12 +346,14 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     (avr_assemble_container_parsed).  model = MODEL_PARALLEL or MODEL_PARALLEL32.
     split_bytes None or 0 (the default): every slice is coded whole -- byte-identical to
     ctx.compress(data, model) at ctx.split_bytes = 0, or where no slice is a split candidate.
-    split_bytes = s with MODEL_PARALLEL (MODEL_PARALLEL32 ignores it, as the whole-file call does):
+    split_bytes = s with MODEL_PARALLEL, or with MODEL_PARALLEL32 and split_p32 (pass ctx.split_p32;
+    without it MODEL_PARALLEL32 ignores split_bytes, as the whole-file call does by default):
     each rank takes its range's split candidates (a progressive slice of at least 1.5 s payload
     bytes) through the split walk, checks them piece by piece on the device and builds their seams
     fields (batch.SplitBatch); a second gather_flat brings the fields to rank 0, which assembles with
-    them (avr_assemble_container_seams_parsed).  Byte-identical to ctx.compress(data, MODEL_PARALLEL)
-    at ctx.split_bytes = s; sharded_compress(ctx, x, split_bytes=ctx.split_bytes) is the whole-file
+    them (avr_assemble_container_seams_parsed; for MODEL_PARALLEL32 avr_assemble_container_opts with
+    ASSEMBLE_SPLIT32, which writes the P32S / P32SE tag).  Byte-identical to ctx.compress(data, model)
+    at ctx.split_bytes = s (and ctx.split_p32 on for MODEL_PARALLEL32); sharded_compress(ctx, x, split_bytes=ctx.split_bytes) is the whole-file
     container.  A slice is one rank's: the cut pieces help the decompress, a single slice's compress
     walk stays one chain.
     escaped (pass ctx.recode_escaped): rank 0 assembles with the second search of
@@ -361,13 +366,14 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
 
     rank, world = dist.get_rank(), dist.get_world_size()
     ps = ps if ps is not None else parse_stream(data)
-    split = int(split_bytes or 0) if model == MODEL_PARALLEL else 0
+    split32 = model == MODEL_PARALLEL32 and bool(split_p32)
+    split = int(split_bytes or 0) if model == MODEL_PARALLEL or split32 else 0
     lo, hi = partition(ps.descs["payload_size"], world)[rank]
     part = subset(ps, lo, hi)
     dev = _gather_device(ctx, device)
     seams = None
     if hi > lo:
-        flat, status, offs, lens, seams = (run_range or (lambda p: compress_range(ctx, p, None, model, split)))(part)
+        flat, status, offs, lens, seams = (run_range or (lambda p: compress_range(ctx, p, None, model, split, split_p32=split32)))(part)
     else:
         flat = torch.zeros(16, dtype=torch.uint8, device=dev)
         offs = lens = status = np.zeros(0, np.int64)
@@ -387,7 +393,7 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     if gs is not None:
         _, sblob, soffs, slens = gs
         return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, seams=(sblob, soffs, slens),
-                                  escaped=escaped)
+                                  escaped=escaped, split32=split32)
     return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, escaped=escaped)
 
 
@@ -423,7 +429,8 @@ def decompress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PA
 def decompress_units_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL):
     """This rank's unit range of a sharded decompress of a split container on its GPU
     (batch.UnitBatch): (flat uint8 tensor, status, offsets, lens) per unit, unit k's kept bytes at
-    flat[offsets[k] : offsets[k] + lens[k]].  The pieces go through avr_decompress_pieces, the whole
+    flat[offsets[k] : offsets[k] + lens[k]].  The pieces go through avr_decompress_pieces_m on the
+    container's coder (model: MODEL_PARALLEL, or MODEL_PARALLEL32 for a P32S container), the whole
     slices through avr_decompress_slices, one launch after the other on the current stream, and one
     avr_pack_pieces packs all units in unit order, each piece cut down to its share of its slice."""
     import torch

@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define AVRECODE_ABI_VERSION 9  /* 9: escaped slices re-coded (avr_set_recode_escaped, Block field 17, the "E" tags,
+#define AVRECODE_ABI_VERSION 10 /* 10: the long-slice split on the P32 coder, opt-in (avr_set_split_p32, the "P32S" / "P32SE"
+                                 *    tags, avr_compress_split_slices_m, avr_decompress_pieces_m, AVR_ASSEMBLE_SPLIT32);
+                                 * 9: escaped slices re-coded (avr_set_recode_escaped, Block field 17, the "E" tags,
                                  *    avr_assemble_container_opts, avr_escape_payload);
                                  * 8: split compress of slice batches (avr_split_plan, avr_compress_split_slices,
                                  *    avr_seams_build, avr_stage_pieces, avr_verify_units, avr_assemble_container_seams);
@@ -100,9 +102,25 @@ void avr_free(void* p);
  * A caller that holds slice batches on the device makes them with avr_split_plan,
  * avr_compress_split_slices, avr_seams_build and avr_assemble_container_seams (ABI 8, below).
  * split_bytes = 0: no split.  Default: the environment's AVR_SPLIT_BYTES, else 98304.  Checked by the oracle's
- * restatement (oracle/oracle_seams.c). */
+ * restatement (oracle/oracle_seams.c).
+ * AVR_MODEL_PARALLEL32 takes the same split only with avr_set_split_p32 on (below): by default its
+ * whole-file compress ignores split_bytes and writes the containers it always wrote. */
 int avr_set_split_bytes(avr_ctx* ctx, size_t split_bytes);
 size_t avr_get_split_bytes(const avr_ctx* ctx);
+/* The long-slice split for AVR_MODEL_PARALLEL32, an option, off by default.  With it on,
+ * avr_compress_file(s) and avr_roundtrip_file(s) of AVR_MODEL_PARALLEL32 read split_bytes exactly as
+ * AVR_MODEL_PARALLEL does: the same candidate slices, the same cuts (a cut is placed from the CABAC
+ * decoder's state and the payload alone, so it does not depend on the coder the pieces are re-coded
+ * with), every cut checked by the host's restatement; the pieces are P32 streams.  A container with at
+ * least one Block field 16 is tagged "avrecode-amd:P32S", with a field 17 as well "avrecode-amd:P32SE"
+ * (a reader from before ABI 10 refuses the tag instead of decoding Block.cabac as one stream); one
+ * without field 16 keeps "avrecode-amd:P32" / "P32E" and its bytes, option on or off.  Reading needs
+ * no option: every decompress call that takes a split AVR_MODEL_PARALLEL container takes these
+ * (whole files, avr_dec_plan_load_pieces, the hooks decompress session for "P32S"); field 16 under
+ * "avrecode-amd:P32" / "P32E" stays AVR_ERR_FORMAT, and an S tag without any field 16 is accepted.
+ * Default: the environment's AVR_SPLIT_P32 (non-zero: on), else 0. */
+int avr_set_split_p32(avr_ctx* ctx, int on);
+int avr_get_split_p32(const avr_ctx* ctx);
 
 /* Slices whose NAL unit carries emulation-prevention bytes (00 00 03, H.264 7.4.1) re-coded: an
  * option of the parallel models, off by default.  The segmentation looks for a slice's unescaped
@@ -461,6 +479,12 @@ int avr_dec_plan_recs(const avr_dec_plan* plan, uint8_t* out, size_t cap);
 int avr_decompress_pieces(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_piece* pieces, int n,
                           int max_mb_width, int max_mb_height, const uint8_t* d_recs, int n_recs, size_t rec_stride,
                           const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res, void* stream);
+/* The same for units of either parallel model: model = AVR_MODEL_PARALLEL (avr_decompress_pieces
+ * exactly) or AVR_MODEL_PARALLEL32 (the units of an "avrecode-amd:P32S" container, on the P32 split
+ * kernel); any other model: AVR_ERR_INVALID_ARGUMENT.  One call runs one coder. */
+int avr_decompress_pieces_m(avr_ctx* ctx, int model, const avr_slice_desc* d_desc, const avr_piece* pieces, int n,
+                            int max_mb_width, int max_mb_height, const uint8_t* d_recs, int n_recs, size_t rec_stride,
+                            const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res, void* stream);
 /* avr_pack_outputs for units: unit k's kept bytes -- all out_len of them when d_pieces[k].keep is
  * UINT32_MAX, else the first keep -- packed at d_packed + d_offsets[k] (d_offsets: n + 1 entries, the
  * exclusive prefix sum of d_kept).  d_status[k] = the unit's status, or AVR_SLICE_NO_END when it
@@ -509,6 +533,13 @@ int avr_compress_split_slices(avr_ctx* ctx, const avr_slice_desc* d_desc, int n,
                               const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res,
                               const avr_split_slot* slots, size_t split_bytes, uint8_t* d_recs, int n_recs,
                               size_t rec_stride, uint32_t* d_cuts, uint32_t* d_piece_end, void* stream);
+/* The same walk re-coding with either parallel model's coder: model = AVR_MODEL_PARALLEL
+ * (avr_compress_split_slices exactly) or AVR_MODEL_PARALLEL32; any other: AVR_ERR_INVALID_ARGUMENT.
+ * The cuts, records and counts are the same for both; the streams and piece ends are the coder's. */
+int avr_compress_split_slices_m(avr_ctx* ctx, int model, const avr_slice_desc* d_desc, int n, int max_mb_width,
+                                int max_mb_height, const uint8_t* d_in, uint8_t* d_out, avr_slice_result* d_res,
+                                const avr_split_slot* slots, size_t split_bytes, uint8_t* d_recs, int n_recs,
+                                size_t rec_stride, uint32_t* d_cuts, uint32_t* d_piece_end, void* stream);
 /* Host only: the Block-field-16 bytes of every cut slice of such a batch, from what the caller read
  * back -- descs / arena (the host descriptors and payloads, avr_parse_stream's), res, cuts,
  * piece_end (n_recs entries) and recs (n_recs * rec_stride bytes, at least recs_len).  status[k] =
@@ -549,8 +580,12 @@ int avr_assemble_container_seams_parsed(const uint8_t* file, size_t n, int model
  * compress writes what avr_compress_file writes with the option on; with descs it parses the file
  * once more when some coded slice's payload does not stand verbatim (a descriptor does not carry
  * its NAL's place).  AVR_ERR_INVALID_ARGUMENT for the flag with a model that is not one of the two
- * parallel ones, and for unknown flag bits. */
-enum { AVR_ASSEMBLE_ESCAPED = 1 };
+ * parallel ones, and for unknown flag bits.
+ * AVR_ASSEMBLE_SPLIT32: seams fields are allowed for AVR_MODEL_PARALLEL32 (without the flag every
+ * assemble call refuses them), and a container that holds one is tagged "avrecode-amd:P32S" /
+ * "P32SE": what avr_compress_file writes with avr_set_split_p32 on.  AVR_ERR_INVALID_ARGUMENT for the
+ * flag with any other model. */
+enum { AVR_ASSEMBLE_ESCAPED = 1, AVR_ASSEMBLE_SPLIT32 = 2 };
 int avr_assemble_container_opts(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
                                 const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
                                 size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, const uint8_t* seams,
