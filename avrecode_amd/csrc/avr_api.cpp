@@ -160,86 +160,15 @@ bool check_reciprocals(const avr::EngineTables& t) {
 
 constexpr int kRModeFallback = 1;
 
-// Does the parallel reference-model compress beat one workgroup per file on this plan?  Its time is
-// its largest slice's: the scan twice (count, write) and the recoded coder, one after the other;
-// the sequential kernel's is its largest file's, with walker, modeler and coder overlapped on three
-// waves.  Measured per payload byte of the chain (profiles/r05_rcode_ab.txt and
-// r05m_rmode_files_before.log: a 4K 4:4:4 slice of 1.38 MB, scan 1.3-1.8 s per pass, coder ~1.5 s
-// per MB; the per-file kernel's compress of a 2-slice such file 1.4 s per MB): the parallel pass
-// pays when the largest file's payload exceeds ~3.7 times the largest slice's (cockatoo.mp4: 280
-// slices; a 1-2-slice-per-picture 4K file does not).
-// AVR_RMODE_PARALLEL=1 forces the parallel pass (tests), AVR_RMODE_SEQUENTIAL=1 the sequential kernel.
-bool rmode_parallel_pays(const Plan& plan) {
-  if (getenv("AVR_RMODE_PARALLEL")) return true;
-  const int nf = plan.n_files(), n = (int)plan.descs.size();
-  uint64_t max_slice = 0, max_file = 0;
-  for (int f = 0; f < nf; f++) {
-    const int e = f + 1 < nf ? plan.file_begin(f + 1) : n;
-    uint64_t fs = 0;
-    for (int k = plan.file_begin(f); k < e; k++) {
-      const uint64_t s = plan.descs[k].coded ? plan.descs[k].payload_size : 0;
-      fs += s;
-      max_slice = std::max(max_slice, s);
-    }
-    max_file = std::max(max_file, fs);
-  }
-  return max_file * 10 > max_slice * 37;
-}
-
-// Reference-model compress of a plan (file order) in parallel over slices (avr_k_rmode.hip).
-// Frame metadata generations mirror update_frame_spec (recode.cpp:824-843) as
-// slices_sequential_kernel implements it; a stream whose frame size changes with a stale other
-// frame is left to the sequential kernel (kRModeFallback), as is a plan too large for one pass.
-int run_rmode_compress(avr_ctx* c, Plan& plan, uint64_t out_total, uint32_t flags) {
+// Reference-model compress of a plan (file order) in parallel over slices (avr_k_rmode.hip), the
+// device half: the frame generations are rmode_generations' (avr_cplan.cpp), which also leaves a
+// plan to the sequential kernel (kRModeFallback), as does a plan too large for one pass.
+int run_rmode_compress(avr_ctx* c, Plan& plan, uint32_t flags) {
   const int n = (int)plan.descs.size();
   const int nf = plan.n_files();
-  if (nf > avr::rmode_max_files_per_pass()) return kRModeFallback;
-  struct Fb { int gen = -1, w = 0, h = 0, fid = 0; } fb[2];
-  std::vector<uint8_t> gen_parity;   // field parities (1 top, 2 bottom) seen per frame generation
-  int cur = 0;
-  std::vector<int64_t> gen_off, goff(2 * (size_t)n);
+  std::vector<int64_t> goff;
   int64_t fbytes = 0;
-  std::vector<char> file_start(n + 1, 0);
-  for (int f = 0; f < nf; f++) file_start[plan.file_begin(f)] = 1;
-  for (int k = 0; k < n; k++) {
-    if (file_start[k]) {   // a new file: a fresh model, frames of its own
-      fb[0] = Fb();
-      fb[1] = Fb();
-      cur = 0;
-    }
-    const avr_slice_desc& d = plan.descs[k];
-    const int W = d.mb_width, H = d.mb_height;
-    if (fb[cur].w != W || fb[cur].h != H || !(fb[cur].fid == d.picture_id && fb[cur].w && fb[cur].h)) {
-      cur = 1 - cur;
-      Fb& nw = fb[cur];
-      Fb& ot = fb[1 - cur];
-      const bool reinit_other = (nw.w != W || nw.h != H) && (ot.w != W || ot.h != H);
-      nw.gen = (int)gen_off.size();
-      gen_off.push_back(fbytes);
-      gen_parity.push_back(0);
-      fbytes += (int64_t)W * H * 52;
-      if (reinit_other) {
-        ot.gen = -1;
-        ot.w = W;
-        ot.h = H;
-      }
-      nw.w = W;
-      nw.h = H;
-      nw.fid = d.picture_id;
-    }
-    const Fb& ot = fb[1 - cur];
-    if (ot.gen >= 0 && (ot.w != W || ot.h != H)) return kRModeFallback;
-    goff[2 * k] = gen_off[fb[cur].gen];
-    goff[2 * k + 1] = ot.gen < 0 ? -1 : gen_off[ot.gen];
-    // a field whose frame has no slice of the other parity yet (its rows are still zero in the
-    // sequential model, but filled in the buffer the parallel scan reads): offsets are 4-aligned
-    if (d.structure == AVR_STRUCT_TOP_FIELD || d.structure == AVR_STRUCT_BOTTOM_FIELD) {
-      uint8_t& seen = gen_parity[fb[cur].gen];
-      if (!(seen & (d.structure == AVR_STRUCT_TOP_FIELD ? 2 : 1))) goff[2 * k] |= 1;
-      seen |= (uint8_t)(d.structure == AVR_STRUCT_TOP_FIELD ? 1 : 2);
-    }
-  }
-  if (fbytes > ((int64_t)4 << 30)) return kRModeFallback;
+  if (nf > avr::rmode_max_files_per_pass() || !rmode_generations(plan, &goff, &fbytes)) return kRModeFallback;
   const size_t lds = avr::shared_bytes(plan.max_w);
   HIP_TRY(c, c->frames.reserve((size_t)fbytes + 64));
   HIP_TRY(c, hipMemsetAsync(c->frames.p, 0, (size_t)fbytes + 64, c->stream));
@@ -298,7 +227,6 @@ int run_rmode_compress(avr_ctx* c, Plan& plan, uint64_t out_total, uint32_t flag
   HIP_TRY(c, avr::launch_rcode(c->tables.as<avr::EngineTables>(), c->descs.as<avr_slice_desc>(), n, rops,
                                c->rm_off.as<uint64_t>(), c->rm_counts.as<uint32_t>(), c->out.as<uint8_t>(),
                                c->res.as<avr_slice_result>(), c->rm_stop.as<int32_t>(), flags, c->stream));
-  (void)out_total;
   return AVR_OK;
 }
 
@@ -311,9 +239,6 @@ hipError_t reserve_parallel(avr_ctx* c, int n, int max_w, bool field_lane = fals
   if (e == hipSuccess) e = c->queue.reserve(std::max<size_t>(256, avr::queue_scratch_bytes(n)));
   return e;
 }
-
-// a slice whose compress output does not regenerate its payload (run_plan's verify)
-constexpr int32_t kStatusNoRoundtrip = AVR_SLICE_NO_ROUNDTRIP;
 
 // ------------------------------------------------------------------------ the long-slice split
 // The parallel model (on arithmetic_code<uint64_t, uint8_t>; on the P32 coder with avr_set_split_p32)
@@ -625,6 +550,63 @@ void add_bill(Bill* b, const avr_slice_result& r) {
   for (int i = 0; i < 6; i++) (*b)[i] += r.bill[i];
 }
 
+// ------------------------------------------------------------------------ whole-file compress
+// Per file f and slice i of it, compress_files keeps: ok (offered to the segmentation), found
+// (where the segmentation found it; null: not coded) and recoded (what its block holds).
+
+// The reference-model pass: the coded slices of every file in file order, estimators per file (per
+// chain: reference_plan); a slice that fails there is demoted to skip_coded and its file's pass
+// repeated.
+int reference_pass(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* in_len, int model,
+                   const std::vector<ParsedFile>& pf, std::vector<Bill>* bills, std::vector<int32_t>& st,
+                   std::vector<std::vector<char>>& ok, std::vector<std::vector<const uint8_t*>>& found,
+                   std::vector<std::vector<std::vector<uint8_t>>>& recoded) {
+  std::vector<char> todo(nf, 0), coded;
+  for (int f = 0; f < nf; f++) todo[f] = st[f] == AVR_OK;
+  for (int attempt = 0;; attempt++) {
+    Plan rp;
+    std::vector<std::pair<int, int>> idx;   // (file, slice) per desc
+    for (int f = 0; f < nf; f++) {
+      if (!todo[f]) continue;
+      if (bills) (*bills)[f] = Bill{};   // this pass re-codes the whole file
+      coded.assign(found[f].size(), 0);
+      for (size_t i = 0; i < found[f].size(); i++) coded[i] = found[f][i] != nullptr;
+      reference_plan(&rp, pf[f], 0, (int)coded.size(), coded, model == AVR_MODEL_CHAINED, f, &idx);
+    }
+    if (rp.file_first.empty()) break;
+    rp.file_first.push_back((int)rp.descs.size());
+    std::vector<avr_slice_result> rr;
+    Bytes ro;
+    if (int r = run_plan(c, 0, true, rp, &rr, &ro, false, bills ? avr::kFlagBill : 0)) return r;
+    std::fill(todo.begin(), todo.end(), 0);
+    for (size_t k = 0; k < idx.size(); k++) {
+      const int f = idx[k].first, i = idx[k].second;
+      if (!found[f][i]) continue;
+      if (rr[k].status != 0) {
+        found[f][i] = nullptr;
+        todo[f] = 1;
+        continue;
+      }
+      recoded[f][i].assign(ro.begin() + rp.descs[k].out_offset, ro.begin() + rp.descs[k].out_offset + rr[k].out_len);
+      if (bills) add_bill(&(*bills)[f], rr[k]);
+    }
+    bool again = false;
+    for (int f = 0; f < nf; f++) {
+      if (!todo[f]) continue;
+      again = true;
+      // a demoted slice changes the literal gaps of later ones: redo the segmentation
+      for (size_t i = 0; i < pf[f].slices.size(); i++) ok[f][i] = ok[f][i] && found[f][i] != nullptr;
+      found[f] = segment(in[f], in_len[f], pf[f], ok[f]);
+      if (attempt == 7) {
+        st[f] = fail(c, AVR_ERR_DEVICE, "reference-model pass did not converge");
+        todo[f] = 0;
+      }
+    }
+    if (!again) break;
+  }
+  return AVR_OK;
+}
+
 // verify (parallel model): decompress every candidate slice on the device and code only those that
 // regenerate their payload.  avr_roundtrip_file skips it on a first attempt -- its own whole-file
 // decompress and compare check the same thing, as the reference's roundtrip() does with a
@@ -641,49 +623,26 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
     out_len[f] = 0;
     st[f] = parse_file(c, in[f], in_len[f], &pf[f], /*views=*/true);
   }
-  // 1) parallel model: every candidate slice of every file through the parallel kernel -- per-slice
-  //    parse, restore check, device roundtrip and the model's output.  Reference model: nothing
-  //    here; the reference-model pass below parses and checks every candidate itself (its statuses
-  //    carry the same parse / restore verdict) and demotes the failures, so a well-formed file
-  //    costs one reference-model pass, not a parallel-model pass before it.
+  // 1) plan, parallel model: every candidate slice of every file goes through the parallel kernel
+  //    -- per-slice parse, restore check, device roundtrip and the model's output -- the long ones
+  //    (split_slot) through the split job.  Reference model: nothing here; the reference-model
+  //    pass below parses and checks every candidate itself (its statuses carry the same parse /
+  //    restore verdict) and demotes the failures, so a well-formed file costs one reference-model
+  //    pass, not a parallel-model pass before it.
   Plan plan;
-  // the parallel model's long slices (split_slot): the split job, its first pass on the split
-  // stream beside the batch (cand_of = -2 - index there)
   SplitJob sj;
+  std::vector<std::vector<Route>> route;
   const size_t split_bytes =
       model == AVR_MODEL_PARALLEL || (model == AVR_MODEL_PARALLEL32 && c->split_p32) ? c->split_bytes : 0;
   sj.coder = coder_flag(model);
-  std::vector<std::vector<int>> cand_of(nf);
-  for (int f = 0; f < nf; f++) {
-    cand_of[f].assign(pf[f].slices.size(), -1);
-    if (st[f] || reference_model(model)) continue;
-    for (size_t i = 0; i < pf[f].slices.size(); i++) {
-      const avr::SliceInfo& s = pf[f].slices[i];
-      if (!recodable_candidate(s)) continue;
-      avr_slice_desc d = desc_from_header(s);
-      d.payload_size = (uint32_t)s.size;
-      uint64_t cap, oc;
-      if (split_slot(d, split_bytes, &cap, &oc)) {
-        cand_of[f][i] = -2 - (int)sj.sl.size();
-        sj.sl.push_back(&s);
-        sj.d.push_back(d);
-        continue;
-      }
-      append_aligned(&plan.arena, s.payload(), s.read_limit, 16, &d.payload_offset);
-      d.payload_size = (uint32_t)s.size;
-      d.read_limit = (uint32_t)s.read_limit;
-      d.out_capacity = (uint32_t)(s.size * 2 + 256);
-      plan.max_w = std::max(plan.max_w, ring_cols(d));
-      cand_of[f][i] = (int)plan.descs.size();
-      plan.descs.push_back(d);
-    }
-  }
+  if (parallel_model(model)) plan_candidates(pf, st, split_bytes, &plan, &sj.sl, &sj.d, &route);
+  // 2) launch the split job's first pass on the split stream, then the batch beside it; collect
   std::vector<avr_slice_result> res;
   Bytes outb;
   pc.mark_demux();
-  if (int r = split_begin(c, &sj, split_bytes, bills ? avr::kFlagBill : 0u)) return r;
-  if (int r = run_plan(c, 0, false, plan, &res, &outb, verify,
-                       (bills ? avr::kFlagBill : 0u) | coder_flag(model))) {
+  const uint32_t bill_flag = bills ? avr::kFlagBill : 0u;
+  if (int r = split_begin(c, &sj, split_bytes, bill_flag)) return r;
+  if (int r = run_plan(c, 0, false, plan, &res, &outb, verify, bill_flag | coder_flag(model))) {
     (void)hipStreamSynchronize(c->split_stream);   // its first pass still reads sj's buffers
     return r;
   }
@@ -693,109 +652,48 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
     if (int r = split_finish(c, &sj, verify, &so)) return r;
     c->plan_wall += now_s() - t;
   }
-  // 2) segmentation (find_next_coded_block_and_emit_literal, recode.cpp:1275-1297)
+  // 3) segmentation (find_next_coded_block_and_emit_literal, recode.cpp:1275-1297)
   std::vector<std::vector<char>> ok(nf);
   std::vector<std::vector<const uint8_t*>> found(nf);
   for (int f = 0; f < nf; f++) {
     ok[f].assign(pf[f].slices.size(), 0);
-    for (size_t i = 0; i < pf[f].slices.size(); i++)
+    for (size_t i = 0; i < pf[f].slices.size(); i++) {
+      const Route r = reference_model(model) ? Route{} : route[f][i];
       ok[f][i] = reference_model(model) ? st[f] == AVR_OK && recodable_candidate(pf[f].slices[i])
-                 : cand_of[f][i] >= 0    ? res[cand_of[f][i]].status == 0
-                 : cand_of[f][i] <= -2   ? so[-2 - cand_of[f][i]].status == 0
-                                         : false;
+                 : r.kind == Route::kBatch ? res[r.index].status == 0
+                                           : r.kind == Route::kSplit && so[r.index].status == 0;
+    }
   }
   // the parallel models' option (avr_set_recode_escaped): a slice the search misses is searched
   // once more by its escaped payload, and kept with Block field 17
   const bool escaped = parallel_model(model) && c->recode_escaped;
   std::vector<std::vector<uint32_t>> escapes(nf);
   parallel_files(nf, [&](int f) { found[f] = segment(in[f], in_len[f], pf[f], ok[f], escaped ? &escapes[f] : nullptr); });
-  // 3) reference model: the coded slices of every file in file order, estimators per file; a
-  //    slice that fails there is demoted to skip_coded and its file's pass repeated
+  // 4) the blocks of the coded slices: the reference-model pass, or what step 2 left
   std::vector<std::vector<std::vector<uint8_t>>> recoded(nf);
   for (int f = 0; f < nf; f++) recoded[f].resize(pf[f].slices.size());
   std::vector<std::vector<std::pair<const uint8_t*, size_t>>> seams_of(nf);
   for (int f = 0; f < nf; f++) seams_of[f].assign(pf[f].slices.size(), {nullptr, 0});
   if (reference_model(model)) {
-    std::vector<char> todo(nf, 0);
-    for (int f = 0; f < nf; f++) todo[f] = st[f] == AVR_OK;
-    for (int attempt = 0;; attempt++) {
-      Plan rp;
-      std::vector<std::pair<int, int>> idx;   // (file, slice) per desc
-      for (int f = 0; f < nf; f++) {
-        if (!todo[f]) continue;
-        if (bills) (*bills)[f] = Bill{};   // this pass re-codes the whole file
-        rp.file_first.push_back((int)rp.descs.size());
-        int coded_n = 0;
-        for (size_t i = 0; i < pf[f].slices.size(); i++) {
-          const avr::SliceInfo& s = pf[f].slices[i];
-          avr_slice_desc d = desc_from_header(s);
-          d.coded = found[f][i] != nullptr;
-          // chained model: a fresh model (a new "file" of the pass: estimators, frames) before every
-          // AVR_CHAIN_SLICES-th coded slice; uncoded slices before it still flip the old chain's frames
-          if (d.coded && model == AVR_MODEL_CHAINED && coded_n > 0 && coded_n % AVR_CHAIN_SLICES == 0)
-            rp.file_first.push_back((int)rp.descs.size());
-          coded_n += d.coded;
-          if (d.coded) {
-            append_aligned(&rp.arena, s.payload(), s.read_limit, 16, &d.payload_offset);
-            d.payload_size = (uint32_t)s.size;
-            d.read_limit = (uint32_t)s.read_limit;
-            d.out_capacity = (uint32_t)(s.size * 4 + 4096);
-            rp.max_w = std::max(rp.max_w, ring_cols(d));   // uncoded slices only flip frames
-          }
-          idx.push_back({f, (int)i});
-          rp.descs.push_back(d);
-        }
-      }
-      if (rp.file_first.empty()) break;
-      rp.file_first.push_back((int)rp.descs.size());
-      std::vector<avr_slice_result> rr;
-      Bytes ro;
-      if (int r = run_plan(c, 0, true, rp, &rr, &ro, false, bills ? avr::kFlagBill : 0)) return r;
-      std::fill(todo.begin(), todo.end(), 0);
-      for (size_t k = 0; k < idx.size(); k++) {
-        const int f = idx[k].first, i = idx[k].second;
-        if (!found[f][i]) continue;
-        if (rr[k].status != 0) {
-          found[f][i] = nullptr;
-          todo[f] = 1;
-          continue;
-        }
-        recoded[f][i].assign(ro.begin() + rp.descs[k].out_offset,
-                             ro.begin() + rp.descs[k].out_offset + rr[k].out_len);
-        if (bills) add_bill(&(*bills)[f], rr[k]);
-      }
-      bool again = false;
-      for (int f = 0; f < nf; f++) {
-        if (!todo[f]) continue;
-        again = true;
-        // a demoted slice changes the literal gaps of later ones: redo the segmentation
-        for (size_t i = 0; i < pf[f].slices.size(); i++) ok[f][i] = ok[f][i] && found[f][i] != nullptr;
-        found[f] = segment(in[f], in_len[f], pf[f], ok[f]);
-        if (attempt == 7) {
-          st[f] = fail(c, AVR_ERR_DEVICE, "reference-model pass did not converge");
-          todo[f] = 0;
-        }
-      }
-      if (!again) break;
-    }
+    if (int r = reference_pass(c, nf, in, in_len, model, pf, bills, st, ok, found, recoded)) return r;
   } else {
     for (int f = 0; f < nf; f++)
-      for (size_t i = 0; i < pf[f].slices.size(); i++)
-        if (found[f][i]) {
-          const int k = cand_of[f][i];
-          if (k <= -2) {   // a split slice: its pieces' streams and seams
-            SplitOut& x = so[-2 - k];
-            recoded[f][i].swap(x.recoded);
-            seams_of[f][i] = {x.seams.data(), x.seams.size()};
-            if (bills) add_bill(&(*bills)[f], x.bill);
-            continue;
-          }
-          recoded[f][i].assign(outb.begin() + plan.descs[k].out_offset,
-                               outb.begin() + plan.descs[k].out_offset + res[k].out_len);
-          if (bills) add_bill(&(*bills)[f], res[k]);
+      for (size_t i = 0; i < pf[f].slices.size(); i++) {
+        if (!found[f][i]) continue;
+        const Route r = route[f][i];
+        if (r.kind == Route::kSplit) {   // its pieces' streams and seams
+          SplitOut& x = so[r.index];
+          recoded[f][i].swap(x.recoded);
+          seams_of[f][i] = {x.seams.data(), x.seams.size()};
+          if (bills) add_bill(&(*bills)[f], x.bill);
+          continue;
         }
+        recoded[f][i].assign(outb.begin() + plan.descs[r.index].out_offset,
+                             outb.begin() + plan.descs[r.index].out_offset + res[r.index].out_len);
+        if (bills) add_bill(&(*bills)[f], res[r.index]);
+      }
   }
-  // 4) containers (compressor::run, recode.cpp:1115-1125)
+  // 5) containers (compressor::run, recode.cpp:1115-1125)
   int first_err = AVR_OK;
   parallel_files(nf, [&](int f) {
     if (st[f] != AVR_OK) return;
@@ -812,65 +710,12 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   return status ? AVR_OK : first_err;
 }
 
-// decompressor::run (recode.cpp:1312-1357) for several files at once: the slices of every
-// parallel-model file go to one parallel launch, every reference-model file to one workgroup of a
-// sequential launch.
-int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* in_len, uint8_t** out,
-                     size_t* out_len, int32_t* status, std::vector<Bill>* bills = nullptr) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  PhaseClock pc(c);
-  if (bills) bills->assign(nf, Bill{});
-  const uint32_t flags = bills ? avr::kFlagBill : 0;
-  std::vector<int32_t> st(nf, AVR_OK);
-  std::vector<DecJob> jobs(nf);
-  // plans[AVR_MODEL_*]: reference-model files (one workgroup each); parallel-model slices on the
-  // u64 coder; on the P32 coder
-  Plan plans[3];   // indexed by plan_of(model): the chained model's chains go to the reference plan
-  Plan& rp = plans[AVR_MODEL_REFERENCE];
-  // the pieces of split blocks, one plan per coder (the coder is a compile-time parameter of the
-  // split kernel, so one launch cannot hold both): [0] the u64 coder's, [1] the P32 coder's
-  SplitPlan sps[2];
-  auto plan_of = [](int m) { return parallel_model(m) ? m : (int)AVR_MODEL_REFERENCE; };
-  for (int f = 0; f < nf; f++) {
-    out[f] = nullptr;
-    out_len[f] = 0;
-    std::string version;
-    std::vector<avr::PbBlock> probe;
-    const int m = avr::pb_parse(in[f], in_len[f], &probe, &version) ? std::max(0, avr::model_of_version(version)) : 0;
-    const bool parallel = parallel_model(m);
-    Plan* plan = &plans[plan_of(m)];
-    const size_t n0 = plan->descs.size();
-    if (!parallel) rp.file_first.push_back((int)n0);
-    SplitPlan& sp = sps[m == AVR_MODEL_PARALLEL32];
-    const size_t s_descs = sp.plan.descs.size(), s_recs = sp.recs.size(), s_arena = sp.plan.arena.size();
-    st[f] = decompress_setup(c, in[f], in_len[f], &jobs[f], plan, &sp);
-    if (st[f]) {   // drop whatever the failed file left
-      plan->descs.resize(n0);
-      sp.plan.descs.resize(s_descs);
-      sp.ctl.resize(s_descs);
-      sp.recs.resize(s_recs);
-      sp.plan.arena.resize(s_arena);
-      if (!parallel) rp.file_first.pop_back();
-    } else if (jobs[f].model == AVR_MODEL_CHAINED) {
-      // one workgroup per chain: a new "file" of the sequential launch before every
-      // AVR_CHAIN_SLICES-th coded slice (the compress side's boundaries)
-      int coded_n = 0;
-      for (size_t k = n0; k < plan->descs.size(); k++) {
-        if (!plan->descs[k].coded) continue;
-        if (coded_n > 0 && coded_n % AVR_CHAIN_SLICES == 0) rp.file_first.push_back((int)k);
-        coded_n++;
-      }
-    }
-  }
-  std::vector<avr_slice_result> res_of[3];
-  std::vector<uint8_t> out_of[3];
-  pc.mark_demux();
-  // the pieces of split blocks on the split stream, beside the other plans: the two coders' launches
-  // one after the other there, each with its own input / output / record buffers
-  std::vector<avr_slice_result> prs[2];
-  Bytes pos[2];
-  SplitPending pends[2];
-  double t_split = 0;
+// ------------------------------------------------------------------------ whole-file decompress
+// The pieces of split blocks on the split stream, beside the other plans: the two coders' launches
+// one after the other there, each with its own input / output / record buffers.  A failure leaves
+// nothing in flight.
+int launch_pieces(avr_ctx* c, SplitPlan* sps, uint32_t flags, std::vector<avr_slice_result>* prs, Bytes* pos,
+                  SplitPending* pends, double* t_split) {
   for (int i = 0; i < 2; i++) {
     SplitPlan& sp = sps[i];
     if (sp.plan.descs.empty()) continue;
@@ -890,8 +735,61 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
       (void)hipStreamSynchronize(ss);
       return r;
     }
-    t_split += now_s() - t;
+    *t_split += now_s() - t;
   }
+  return AVR_OK;
+}
+
+// decompressor::run (recode.cpp:1312-1357) for several files at once: the slices of every
+// parallel-model file go to one parallel launch, every reference-model file to one workgroup of a
+// sequential launch.
+int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* in_len, uint8_t** out,
+                     size_t* out_len, int32_t* status, std::vector<Bill>* bills = nullptr) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  PhaseClock pc(c);
+  if (bills) bills->assign(nf, Bill{});
+  const uint32_t flags = bills ? avr::kFlagBill : 0;
+  std::vector<int32_t> st(nf, AVR_OK);
+  std::vector<DecJob> jobs(nf);
+  // 1) plan.  plans[AVR_MODEL_*]: reference-model files (one workgroup each); parallel-model slices
+  //    on the u64 coder; on the P32 coder
+  Plan plans[3];   // indexed by plan_of(model): the chained model's chains go to the reference plan
+  Plan& rp = plans[AVR_MODEL_REFERENCE];
+  // the pieces of split blocks, one plan per coder (the coder is a compile-time parameter of the
+  // split kernel, so one launch cannot hold both): [0] the u64 coder's, [1] the P32 coder's
+  SplitPlan sps[2];
+  auto plan_of = [](int m) { return parallel_model(m) ? m : (int)AVR_MODEL_REFERENCE; };
+  for (int f = 0; f < nf; f++) {
+    out[f] = nullptr;
+    out_len[f] = 0;
+    std::string version;
+    std::vector<avr::PbBlock> probe;
+    const int m = avr::pb_parse(in[f], in_len[f], &probe, &version) ? std::max(0, avr::model_of_version(version)) : 0;
+    Plan* plan = &plans[plan_of(m)];
+    const size_t n0 = plan->descs.size();
+    SplitPlan& sp = sps[m == AVR_MODEL_PARALLEL32];
+    const size_t s_descs = sp.plan.descs.size(), s_recs = sp.recs.size(), s_arena = sp.plan.arena.size();
+    st[f] = decompress_setup(c, in[f], in_len[f], &jobs[f], plan, &sp);
+    if (st[f]) {   // drop whatever the failed file left
+      plan->descs.resize(n0);
+      sp.plan.descs.resize(s_descs);
+      sp.ctl.resize(s_descs);
+      sp.recs.resize(s_recs);
+      sp.plan.arena.resize(s_arena);
+    } else if (!parallel_model(m)) {
+      // one workgroup per file, or per chain (the compress side's boundaries)
+      append_file_chains(&rp, n0, jobs[f].model == AVR_MODEL_CHAINED);
+    }
+  }
+  std::vector<avr_slice_result> res_of[3];
+  std::vector<uint8_t> out_of[3];
+  pc.mark_demux();
+  // 2) launch the pieces, then the slice plans beside them
+  std::vector<avr_slice_result> prs[2];
+  Bytes pos[2];
+  SplitPending pends[2];
+  double t_split = 0;
+  if (int r = launch_pieces(c, sps, flags, prs, pos, pends, &t_split)) return r;
   auto drain = [&]() { (void)hipStreamSynchronize(c->split_stream); };
   for (int m = AVR_MODEL_PARALLEL; m <= AVR_MODEL_PARALLEL32; m++)
     if (!plans[m].descs.empty())
@@ -906,7 +804,8 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
       return r;
     }
   }
-  if (!sps[0].plan.descs.empty() || !sps[1].plan.descs.empty()) {   // the pieces of split blocks, then each block spliced
+  // 3) collect the pieces of split blocks, then each block spliced
+  if (!sps[0].plan.descs.empty() || !sps[1].plan.descs.empty()) {
     const double t = now_s();
     for (SplitPending& pend : pends)
       if (int r = split_wait(c, &pend)) {
@@ -928,6 +827,7 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
     }
     c->plan_wall += t_split + (now_s() - t);
   }
+  // 4) the files written out (decompressor::run, recode.cpp:1338-1357)
   int first_err = AVR_OK;
   for (int f = 0; f < nf; f++) {
     DecJob& j = jobs[f];
@@ -936,18 +836,18 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
     const std::vector<uint8_t>& outb = out_of[plan_of(j.model)];
     std::vector<uint8_t> o;
     if (st[f] == AVR_OK)
-      st[f] = splice_job(c, j, [&](int k, const uint8_t** p, size_t* len) {
-        if (k <= -2) {   // a split block, spliced from its pieces
-          const SplitBlock& x = j.splits[-2 - k];
+      st[f] = splice_job(c, j, [&](Route r, const uint8_t** p, size_t* len) {
+        if (r.kind == Route::kSplit) {   // spliced from its pieces
+          const SplitBlock& x = j.splits[r.index];
           *p = x.regen.data();
           *len = x.regen.size();
           if (bills && x.status == 0) add_bill(&(*bills)[f], x.bill);
           return (int)x.status;
         }
-        *p = outb.data() + plan.descs[k].out_offset;
-        *len = res[k].out_len;
-        if (bills && res[k].status == 0) add_bill(&(*bills)[f], res[k]);
-        return res[k].status;
+        *p = outb.data() + plan.descs[r.index].out_offset;
+        *len = res[r.index].out_len;
+        if (bills && res[r.index].status == 0) add_bill(&(*bills)[f], res[r.index]);
+        return res[r.index].status;
       }, &o);
     if (st[f] == AVR_OK) {
       out[f] = (uint8_t*)malloc(o.size() ? o.size() : 1);
@@ -967,60 +867,26 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
 
 // ------------------------------------------------------------ the chained model across GPUs
 // The chained model's chains are independent by construction (a fresh model -- estimators, frames --
-// before every AVR_CHAIN_SLICES-th coded slice of a file), so one file's chains can run on several
-// GPUs: each rank takes a contiguous range of chains, balanced by payload bytes, and the re-coded
-// (or regenerated) slices are gathered to rank 0, which assembles (splices) them as for the
-// parallel model.  Chain c of a file starts at slice first[c]: the slice holding the
-// (AVR_CHAIN_SLICES c)-th coded slice (uncoded slices before it stay in chain c - 1, where they
-// only turn the old chain's frames over); first.back() = the slice count.
-std::vector<int> chain_starts(const std::vector<char>& coded) {
-  std::vector<int> first{0};
-  int coded_n = 0;
-  for (size_t i = 0; i < coded.size(); i++) {
-    if (!coded[i]) continue;
-    if (coded_n > 0 && coded_n % AVR_CHAIN_SLICES == 0) first.push_back((int)i);
-    coded_n++;
-  }
-  first.push_back((int)coded.size());
-  return first;
-}
+// before every AVR_CHAIN_SLICES-th coded slice of a file: chain_starts), so one file's chains can
+// run on several GPUs: each rank takes a contiguous range of chains, balanced by payload bytes, and
+// the re-coded (or regenerated) slices are gathered to rank 0, which assembles (splices) them as for
+// the parallel model.
 
-// [lo, hi) of rank's contiguous range of units weighted w: shard.partition's rule (the owner of a
-// unit is the rank its byte-prefix midpoint falls in), so both sides cut identically.
-std::pair<int, int> partition_range(const std::vector<double>& w, int world, int rank) {
-  const int n = (int)w.size();
-  if (world <= 1) return rank == 0 ? std::make_pair(0, n) : std::make_pair(n, n);
-  double total = 0;
-  for (double x : w) total += x;
-  std::vector<int> cuts(world + 1, n);
-  if (total <= 0) {
-    for (int r = 0; r < world; r++) cuts[r] = (int)std::nearbyint((double)r * n / world);
-  } else {
-    std::vector<int> owner(n);
-    double acc = 0;
-    for (int i = 0; i < n; i++) {
-      acc += w[i];
-      const double mid = acc - w[i] / 2;
-      owner[i] = std::min((int)(mid * world / total), world - 1);
-    }
-    for (int r = 0; r < world; r++) cuts[r] = (int)(std::lower_bound(owner.begin(), owner.end(), r) - owner.begin());
-  }
-  return {cuts[rank], cuts[rank + 1]};
+// This rank's slices [lo, hi): its share (partition_range) of the chains that start at `first`,
+// weighted by their coded payload bytes (size(i): slice i's, 0 when it is not coded).
+template <class Size>
+std::pair<int, int> rank_slices(const std::vector<int>& first, int world, int rank, Size&& size) {
+  const int nc = (int)first.size() - 1;
+  std::vector<double> w(nc, 0.0);
+  for (int ch = 0; ch < nc; ch++)
+    for (int i = first[ch]; i < first[ch + 1]; i++) w[ch] += (double)size(i);
+  const auto [clo, chi] = partition_range(w, world, rank);
+  return {first[clo], first[std::max(clo, chi)]};
 }
-
-// One rank's outputs over its slice range [lo, hi) of the file (compress) or of the container's
-// plan (decompress): per slice a status and its bytes (blob + offsets[k], lens[k]).
-struct ChainRangeOut {
-  int lo = 0, hi = 0;
-  std::vector<int32_t> status;
-  std::vector<uint64_t> offsets;
-  std::vector<uint32_t> lens;
-  std::vector<uint8_t> blob;
-};
 
 // compressor::run (recode.cpp:1102-1132) of the chained model, this rank's chains only: the parse
 // and the segmentation of the whole file (the coded slices, hence the chains, depend on every block
-// before them), then the reference-model pass over the chains [clo, chi) (run_plan: one workgroup
+// before them), then the reference-model pass over this rank's chains (run_plan: one workgroup
 // per chain, or the parallel reference-model compress when it pays).  status: 0 coded (bytes),
 // -1 not coded, -2 a coded slice the pass failed (the whole-file call would demote it and
 // re-segment, moving every later chain: the caller compresses the file whole instead).
@@ -1033,59 +899,17 @@ int compress_chain_range(avr_ctx* c, const uint8_t* in, size_t n, int world, int
   for (size_t i = 0; i < ns; i++) ok[i] = recodable_candidate(pf.slices[i]);
   const std::vector<const uint8_t*> found = segment(in, n, pf, ok);
   for (size_t i = 0; i < ns; i++) coded[i] = found[i] != nullptr;
-  const std::vector<int> first = chain_starts(coded);
-  const int nc = (int)first.size() - 1;
-  std::vector<double> w(nc, 0.0);
-  for (int ch = 0; ch < nc; ch++)
-    for (int i = first[ch]; i < first[ch + 1]; i++)
-      if (coded[i]) w[ch] += (double)pf.slices[i].size;
-  const auto [clo, chi] = partition_range(w, world, rank);
-  o->lo = first[clo];
-  o->hi = first[chi];
-  const int nr = o->hi - o->lo;
-  o->status.assign(nr, -1);
-  o->offsets.assign(nr, 0);
-  o->lens.assign(nr, 0);
-  o->blob.clear();
-  if (chi <= clo) return AVR_OK;
+  const auto [lo, hi] =
+      rank_slices(chain_starts(coded), world, rank, [&](int i) { return coded[i] ? pf.slices[i].size : 0; });
   Plan rp;
-  for (int ch = clo; ch < chi; ch++) {
-    rp.file_first.push_back((int)rp.descs.size());
-    for (int i = first[ch]; i < first[ch + 1]; i++) {   // as compress_files builds a chain
-      const avr::SliceInfo& s = pf.slices[i];
-      avr_slice_desc d = desc_from_header(s);
-      d.coded = coded[i];
-      if (d.coded) {
-        append_aligned(&rp.arena, s.payload(), s.read_limit, 16, &d.payload_offset);
-        d.payload_size = (uint32_t)s.size;
-        d.read_limit = (uint32_t)s.read_limit;
-        d.out_capacity = (uint32_t)(s.size * 4 + 4096);
-        rp.max_w = std::max(rp.max_w, ring_cols(d));
-      }
-      rp.descs.push_back(d);
-    }
-  }
-  rp.file_first.push_back((int)rp.descs.size());
   std::vector<avr_slice_result> rr;
   Bytes ro;
-  if (int r = run_plan(c, 0, true, rp, &rr, &ro, false, 0)) return r;
-  uint64_t total = 0;
-  for (int k = 0; k < nr; k++)
-    if (rp.descs[k].coded && rr[k].status == 0) total += rr[k].out_len;
-  o->blob.resize(total);
-  uint64_t at = 0;
-  for (int k = 0; k < nr; k++) {
-    if (!rp.descs[k].coded) continue;
-    if (rr[k].status != 0) {
-      o->status[k] = -2;
-      continue;
-    }
-    o->status[k] = 0;
-    o->offsets[k] = at;
-    o->lens[k] = rr[k].out_len;
-    if (rr[k].out_len) memcpy(o->blob.data() + at, ro.data() + rp.descs[k].out_offset, rr[k].out_len);
-    at += rr[k].out_len;
+  if (hi > lo) {
+    reference_plan(&rp, pf, lo, hi, coded, /*chained=*/true);
+    rp.file_first.push_back((int)rp.descs.size());
+    if (int r = run_plan(c, 0, true, rp, &rr, &ro, false, 0)) return r;
   }
+  pack_range(lo, rp.descs, rr, ro.data(), -1, [](int32_t) { return (int32_t)-2; }, o);
   return AVR_OK;
 }
 
@@ -1103,55 +927,33 @@ int decompress_chain_range(avr_ctx* c, const uint8_t* avrc, size_t n, int world,
   if (int r = decompress_setup(c, avrc, n, &j, &full)) return r;
   if (!reference_model(j.model)) return fail(c, AVR_ERR_UNSUPPORTED, "not a reference- or chained-model container");
   const int ns = (int)full.descs.size();
+  const bool chained = j.model == AVR_MODEL_CHAINED;
   std::vector<char> coded(ns);
   for (int k = 0; k < ns; k++) coded[k] = full.descs[k].coded != 0;
   // the reference model (one chain per file) is a single unit; the chained model's chains
-  const std::vector<int> first = j.model == AVR_MODEL_CHAINED ? chain_starts(coded) : std::vector<int>{0, ns};
-  const int nc = (int)first.size() - 1;
-  std::vector<double> w(nc, 0.0);
-  for (int ch = 0; ch < nc; ch++)
-    for (int k = first[ch]; k < first[ch + 1]; k++)
-      if (coded[k]) w[ch] += (double)full.descs[k].payload_size;
-  const auto [clo, chi] = partition_range(w, world, rank);
-  o->lo = first[clo];
-  o->hi = first[chi];
-  const int nr = o->hi - o->lo;
-  o->status.assign(nr, 1);
-  o->offsets.assign(nr, 0);
-  o->lens.assign(nr, 0);
-  o->blob.clear();
-  if (chi <= clo) return AVR_OK;
+  const auto [lo, hi] = rank_slices(chained ? chain_starts(coded) : std::vector<int>{0, ns}, world, rank,
+                                    [&](int k) { return coded[k] ? full.descs[k].payload_size : 0u; });
   // the range's re-coded streams: decompress_setup listed every coded slice's copy in plan order
   Plan sub;
   size_t ci = 0;
-  for (int k = 0; k < ns && k < o->hi; k++) {
+  for (int k = 0; k < hi; k++) {
     avr_slice_desc d = full.descs[k];
     const avr::PbCopy* cp = d.coded ? &full.arena_copies[ci++] : nullptr;
-    if (k < o->lo) continue;
+    if (k < lo) continue;
     if (cp) {
       append_aligned(&sub.arena, cp->src, cp->len, 16, &d.payload_offset);
       sub.max_w = std::max(sub.max_w, ring_cols(d));
     }
     sub.descs.push_back(d);
   }
-  for (int ch = clo; ch <= chi; ch++) sub.file_first.push_back(first[ch] - o->lo);
   std::vector<avr_slice_result> rr;
   Bytes ro;
-  if (int r = run_plan(c, 1, true, sub, &rr, &ro, false, 0)) return r;
-  uint64_t total = 0;
-  for (int k = 0; k < nr; k++)
-    if (sub.descs[k].coded && rr[k].status == 0) total += rr[k].out_len;
-  o->blob.resize(total);
-  uint64_t at = 0;
-  for (int k = 0; k < nr; k++) {
-    if (!sub.descs[k].coded) continue;
-    o->status[k] = rr[k].status == 0 ? 0 : std::min(-1, (int)rr[k].status);
-    if (rr[k].status != 0) continue;
-    o->offsets[k] = at;
-    o->lens[k] = rr[k].out_len;
-    if (rr[k].out_len) memcpy(o->blob.data() + at, ro.data() + sub.descs[k].out_offset, rr[k].out_len);
-    at += rr[k].out_len;
+  if (hi > lo) {
+    append_file_chains(&sub, 0, chained);   // the range starts at a chain's start: the file's cuts
+    sub.file_first.push_back(hi - lo);
+    if (int r = run_plan(c, 1, true, sub, &rr, &ro, false, 0)) return r;
   }
+  pack_range(lo, sub.descs, rr, ro.data(), 1, [](int32_t s) { return std::min((int32_t)-1, s); }, o);
   return AVR_OK;
 }
 
@@ -1212,7 +1014,7 @@ int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_
   HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
   int rm = kRModeFallback;
   if (sequential && mode == 0 && !getenv("AVR_RMODE_SEQUENTIAL") && rmode_parallel_pays(plan)) {
-    rm = run_rmode_compress(c, plan, out_total, flags);
+    rm = run_rmode_compress(c, plan, flags);
     if (rm < 0) return rm;
   }
   if (sequential && rm == AVR_OK) {
@@ -1277,7 +1079,7 @@ int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_
   c->phase.download_s += 1e-3 * ms[2];
   c->plan_wall += now_s() - t_wall;
   for (int k = 0; k < (int)verdict.size(); k++)
-    if ((*res)[k].status == 0 && verdict[k] != 1) (*res)[k].status = kStatusNoRoundtrip;
+    if ((*res)[k].status == 0 && verdict[k] != 1) (*res)[k].status = AVR_SLICE_NO_ROUNDTRIP;
   return AVR_OK;
 }
 
@@ -1647,32 +1449,29 @@ int avr_verify_slices(avr_ctx* c, const avr_slice_desc* d_desc, const avr_slice_
   return AVR_OK;
 }
 
+// the two chain-range calls: range = compress_chain_range or decompress_chain_range
+static int chain_range(decltype(compress_chain_range)* range, avr_ctx* c, const uint8_t* in, size_t n, int world, int rank,
+                       int* lo, int* hi, int32_t** status, uint8_t** blob, size_t* blob_len, uint64_t** offsets,
+                       uint32_t** lens) {
+  if (!c || !in || world < 1 || rank < 0 || rank >= world || !lo || !hi || !status || !blob || !blob_len || !offsets ||
+      !lens)
+    return AVR_ERR_INVALID_ARGUMENT;
+  *status = nullptr, *blob = nullptr, *offsets = nullptr, *lens = nullptr;
+  return guarded(c, [&]() -> int {
+    ChainRangeOut o;
+    if (int r = range(c, in, n, world, rank, &o)) return r;
+    return export_range(o, lo, hi, status, blob, blob_len, offsets, lens);
+  });
+}
 int avr_compress_chain_range(avr_ctx* c, const uint8_t* file, size_t n, int world, int rank, int* lo, int* hi,
                              int32_t** status, uint8_t** recoded, size_t* recoded_len, uint64_t** offsets,
                              uint32_t** lens) {
-  if (!c || !file || world < 1 || rank < 0 || rank >= world || !lo || !hi || !status || !recoded || !recoded_len ||
-      !offsets || !lens)
-    return AVR_ERR_INVALID_ARGUMENT;
-  *status = nullptr, *recoded = nullptr, *offsets = nullptr, *lens = nullptr;
-  return guarded(c, [&]() -> int {
-    ChainRangeOut o;
-    if (int r = compress_chain_range(c, file, n, world, rank, &o)) return r;
-    return export_range(o, lo, hi, status, recoded, recoded_len, offsets, lens);
-  });
+  return chain_range(compress_chain_range, c, file, n, world, rank, lo, hi, status, recoded, recoded_len, offsets, lens);
 }
-
 int avr_decompress_chain_range(avr_ctx* c, const uint8_t* avrc, size_t n, int world, int rank, int* lo, int* hi,
                                int32_t** status, uint8_t** regen, size_t* regen_len, uint64_t** offsets,
                                uint32_t** lens) {
-  if (!c || !avrc || world < 1 || rank < 0 || rank >= world || !lo || !hi || !status || !regen || !regen_len ||
-      !offsets || !lens)
-    return AVR_ERR_INVALID_ARGUMENT;
-  *status = nullptr, *regen = nullptr, *offsets = nullptr, *lens = nullptr;
-  return guarded(c, [&]() -> int {
-    ChainRangeOut o;
-    if (int r = decompress_chain_range(c, avrc, n, world, rank, &o)) return r;
-    return export_range(o, lo, hi, status, regen, regen_len, offsets, lens);
-  });
+  return chain_range(decompress_chain_range, c, avrc, n, world, rank, lo, hi, status, regen, regen_len, offsets, lens);
 }
 
 int avr_slice_kernel(avr_ctx* c, int decompress, int n, int max_mb_width, int* kind) {

@@ -506,7 +506,7 @@ int avr_parse_stream_range(const uint8_t* file, size_t n, int lo, int hi, avr_sl
       d.read_limit = (uint32_t)s.read_limit;
       d.coded = recodable_candidate(s);
       d.file_offset = s.file_payload_offset();
-      d.out_capacity = (uint32_t)(s.size * 2 + 256);
+      d.out_capacity = parallel_out_capacity(s.size);
       place_output(&d, &work);
       if (d.coded) mw = std::max(mw, ring_cols(d));   // uncoded slices are never walked
       mh = std::max(mh, d.mb_height);

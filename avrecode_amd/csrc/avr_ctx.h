@@ -101,7 +101,7 @@ namespace avr_host {
 // Upload plan, run the slice kernel over it (one launch, see launch_slices), download results and outputs.
 // verify (parallel compress only): also decompress every slice's output on the device, apply the
 // last-byte rule and compare with the payload (avr_roundtrip_slices); a slice whose output does not
-// regenerate its payload gets status kStatusNoRoundtrip, so no container ever holds a block that
+// regenerate its payload gets status AVR_SLICE_NO_ROUNDTRIP, so no container ever holds a block that
 // cannot be decompressed.
 // out_host: a std::vector<uint8_t> or a Bytes (not zero-filled first: the download overwrites it)
 // (defined in avr_api.cpp and instantiated there for both)

@@ -118,27 +118,16 @@ uint8_t next_state(uint8_t s, int bin) {
 int trace_slices(avr_hooks_session* hs, const std::vector<int>& which) {
   avr_ctx* c = hs->c;
   Plan plan;
-  std::vector<int> slice_of;
   for (const int i : which) {
     const avr::SliceInfo& s = hs->pf.slices[i];
-    avr_slice_desc d = desc_from_header(s);
-    append_aligned(&plan.arena, s.payload(), s.read_limit, 16, &d.payload_offset);
-    d.payload_size = (uint32_t)s.size;
-    d.read_limit = (uint32_t)s.read_limit;
-    // 2 bytes per bin (H.264 bounds a slice's bins by ~32/3 per payload byte plus a per-macroblock
-    // allowance, 7.4.2.2) and 12 bytes of map events per residual block (<= 51 per macroblock)
-    d.out_capacity = (uint32_t)std::min<uint64_t>(
-        0xfffffff0ull, 32ull * s.size + 1280ull * d.mb_width * d.mb_height + 8192);
-    plan.max_w = std::max(plan.max_w, ring_cols(d));
-    slice_of.push_back(i);
-    plan.descs.push_back(d);
+    plan_slice(&plan, s, trace_out_capacity(s.size, s.h.mb_width, s.h.mb_height));
   }
   if (plan.descs.empty()) return AVR_OK;
   std::vector<avr_slice_result> res;
   std::vector<uint8_t> traces;
   if (int r = run_plan(c, 3, false, plan, &res, &traces)) return r;
   for (size_t k = 0; k < plan.descs.size(); k++) {
-    const int i = slice_of[k];
+    const int i = which[k];
     if (res[k].status != 0)
       return fail(c, AVR_ERR_FORMAT, "hooks: device trace of slice " + std::to_string(i) + " failed (" +
                                          std::to_string(res[k].status) + ")");
@@ -312,13 +301,7 @@ int stream_device_work(avr_hooks_session* hs, size_t i) {
   Plan plan;
   for (const int k : which) {
     const avr::SliceInfo& s = hs->pf.slices[k];
-    avr_slice_desc d = desc_from_header(s);
-    append_aligned(&plan.arena, s.payload(), s.read_limit, 16, &d.payload_offset);
-    d.payload_size = (uint32_t)s.size;
-    d.read_limit = (uint32_t)s.read_limit;
-    d.out_capacity = (uint32_t)(s.size * 2 + 256);
-    plan.max_w = std::max(plan.max_w, ring_cols(d));
-    plan.descs.push_back(d);
+    plan_slice(&plan, s, parallel_out_capacity(s.size));
   }
   std::vector<avr_slice_result> res;
   std::vector<uint8_t> outb;
@@ -358,11 +341,7 @@ int lazy_device_work(avr_hooks_session* hs, size_t i, bool trace, size_t batch =
                                              std::to_string(res[q].status) + ")");
     std::vector<uint8_t>& g = hs->regen[k];
     g.assign(outb.begin() + sub.descs[q].out_offset, outb.begin() + sub.descs[q].out_offset + res[q].out_len);
-    const avr::PbBlock& b = hs->job.blocks[hs->block_of[k]];
-    if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {   // as splice_job
-      if ((int)b.length_parity != (int)(g.size() & 1)) g.push_back((uint8_t)b.last_byte[0]);
-      else if (!g.empty()) g.back() = (uint8_t)b.last_byte[0];
-    }
+    patch_last_byte(hs->job.blocks[hs->block_of[k]], g.size(), &g);
     // the regenerated payload in place of the surrogate one; the NAL's bytes after the payload
     // (from the literal that follows the block) stay, as does the parse's read limit
     avr::SliceInfo& s = hs->pf.slices[k];

@@ -1,6 +1,9 @@
 // Host-side types and helpers shared by the translation units of libavrecode (internal).  No HIP
-// here: avr_host.cpp, avr_seams.cpp, avr_plan.cpp and avr_assemble.cpp compile without ROCm, and the
-// first three link without the device library (tests/native/plan_fuzz.cpp).
+// here: avr_host.cpp, avr_seams.cpp, avr_plan.cpp (the decompress planner), avr_cplan.cpp (the
+// compress planner) and avr_assemble.cpp compile without ROCm, and all but the last link without
+// the device library (tests/native/plan_fuzz.cpp, cplan_check.cpp).  The one-line rules several
+// units share (the output capacities, the last-byte rule) are inline here, so using one adds no
+// link dependency.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -135,6 +138,17 @@ struct ParsedFile {
   std::vector<avr::SliceInfo> slices;
 };
 
+// Output space of a slice of `size` payload bytes: the parallel models' compress, the reference
+// model's compress.
+inline uint32_t parallel_out_capacity(size_t size) { return (uint32_t)(size * 2 + 256); }
+inline uint32_t reference_out_capacity(size_t size) { return (uint32_t)(size * 4 + 4096); }
+// The bin trace of the hooks surface: 2 bytes per bin (H.264 bounds a slice's bins by ~32/3 per
+// payload byte plus a per-macroblock allowance, 7.4.2.2) and 12 bytes of map events per residual
+// block (<= 51 per macroblock).
+inline uint32_t trace_out_capacity(size_t size, int mb_width, int mb_height) {
+  return (uint32_t)std::min<uint64_t>(0xfffffff0ull, 32ull * size + 1280ull * mb_width * mb_height + 8192);
+}
+
 // views: slices without emulation-prevention bytes point into `in` instead of holding a copy (the
 // caller keeps `in` alive while it uses pf)
 int parse_file(ErrSink* c, const uint8_t* in, size_t n, ParsedFile* pf, bool views = false,
@@ -182,6 +196,71 @@ void parallel_files(int nf, F&& fn) {
   for (auto& x : th) x.join();
   if (err) std::rethrow_exception(err);
 }
+
+// ------------------------------------------------------------------ avr_cplan.cpp: the compress planner
+// A parsed slice taken into a plan (returns its index): the header's descriptor, and -- coded -- its
+// payload in the arena, its sizes, out_capacity bytes of output and its columns of the LDS ring.
+// An uncoded slice of a reference-model plan is never walked: it only turns the frames over.
+int plan_slice(Plan* plan, const avr::SliceInfo& s, uint32_t out_capacity, bool coded = true);
+
+// The chained model's rule: a fresh model before every AVR_CHAIN_SLICES-th coded slice of a file.
+// Chain c starts at slice first[c], the slice holding the (AVR_CHAIN_SLICES c)-th coded slice
+// (uncoded slices before it stay in chain c - 1, where they only turn the old chain's frames
+// over); first.back() = the slice count.  Compress and decompress cut by this one function.
+std::vector<int> chain_starts(const std::vector<char>& coded);
+// The file whose slices are plan->descs[n0 ..] joins file_first: its start, and (chained) the
+// starts of its later chains -- each a "file" of the sequential launch (estimators, frames).
+void append_file_chains(Plan* plan, size_t n0, bool chained);
+
+// One range of a parsed file appended to a reference-model plan: every slice of [lo, hi), the
+// coded ones (coded[i], per slice of the file) with their payloads, then the range's chains in
+// file_first (the caller closes file_first after the last range).  idx (optional): (file, slice)
+// per descriptor.
+void reference_plan(Plan* rp, const ParsedFile& pf, int lo, int hi, const std::vector<char>& coded, bool chained,
+                    int file = 0, std::vector<std::pair<int, int>>* idx = nullptr);
+
+// Where a slice's re-coded bytes come from (the parallel models' compress), or a container block's
+// regenerated bytes (decompress): nowhere, entry `index` of the batch plan, or split slice `index`.
+struct Route {
+  enum Kind : uint8_t { kNone, kBatch, kSplit } kind = kNone;
+  int index = 0;
+};
+// DecJob::desc_of_block's encoding
+inline Route route_of_block(int k) {
+  return k >= 0 ? Route{Route::kBatch, k} : k <= -2 ? Route{Route::kSplit, -2 - k} : Route{};
+}
+// The parallel models' candidate pass over parsed files (st[f] != 0: the parse failed): every
+// recodable candidate goes to the batch plan, or -- a long slice, split_slot at split_bytes -- to
+// the split job (its slice, and a descriptor holding the header's fields and payload_size).
+void plan_candidates(const std::vector<ParsedFile>& pf, const std::vector<int32_t>& st, size_t split_bytes, Plan* batch,
+                     std::vector<const avr::SliceInfo*>* split_sl, std::vector<avr_slice_desc>* split_d,
+                     std::vector<std::vector<Route>>* route);
+
+// [lo, hi) of rank's contiguous range of units weighted w: shard.partition's rule (the owner of a
+// unit is the rank its byte-prefix midpoint falls in), so both sides cut identically.
+std::pair<int, int> partition_range(const std::vector<double>& w, int world, int rank);
+
+// One rank's outputs over its slice range [lo, hi) of the file (compress) or of the container's
+// plan (decompress): per slice a status and its bytes (blob + offsets[k], lens[k]).
+struct ChainRangeOut {
+  int lo = 0, hi = 0;
+  std::vector<int32_t> status;
+  std::vector<uint64_t> offsets;
+  std::vector<uint32_t> lens;
+  std::vector<uint8_t> blob;
+};
+// descs / res / out: a range's plan after its run (slice lo first).  Status 0 with its bytes for
+// a coded slice that came out, failed(its status) for one that did not, `uncoded` for the rest.
+void pack_range(int lo, const std::vector<avr_slice_desc>& descs, const std::vector<avr_slice_result>& res,
+                const uint8_t* out, int32_t uncoded, int32_t (*failed)(int32_t), ChainRangeOut* o);
+
+// Does the parallel reference-model compress beat one workgroup per file on this plan?
+bool rmode_parallel_pays(const Plan& plan);
+// Frame metadata generations of a reference-model plan for the parallel pass: per slice k the
+// buffer offsets of its frame's generation (goff[2k]; bit 0: the first field of its frame) and of
+// the other frame's (goff[2k + 1], -1: none), and the bytes of all generations.  False: the plan
+// is left to the sequential kernel.
+bool rmode_generations(const Plan& plan, std::vector<int64_t>* goff, int64_t* frame_bytes);
 
 // ------------------------------------------------------------------ avr_assemble.cpp: the container writer
 // A slice as the container writer sees it: its payload (init_decoder's buf, size) and whether the
@@ -295,11 +374,28 @@ struct DecJob {
 // hooks paths decompress slices, not pieces)
 int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* plan, SplitPlan* sp = nullptr);
 
+// The last-byte rule (x264 padding correction, recode.cpp:1345-1356) on a slice regenerated as `len`
+// bytes: the block's last_byte replaces its last byte, or -- the length's parity differs from the
+// block's -- is appended.  (The compress side's form, from the payload: last_byte_patch.)
+enum class LastByte { kKeep, kReplace, kAppend };
+inline LastByte last_byte_rule(const avr::PbBlock& b, size_t len) {
+  if (!b.has_parity || !b.has_last_byte || b.last_byte.empty()) return LastByte::kKeep;
+  if ((int)b.length_parity != (int)(len & 1)) return LastByte::kAppend;
+  return len ? LastByte::kReplace : LastByte::kKeep;
+}
+// the rule applied to the len regenerated bytes at the end of *v
+template <class V>
+void patch_last_byte(const avr::PbBlock& b, size_t len, V* v) {
+  const LastByte r = last_byte_rule(b, len);
+  if (r == LastByte::kAppend) v->push_back((uint8_t)b.last_byte[0]);
+  else if (r == LastByte::kReplace) v->back() = (uint8_t)b.last_byte[0];
+}
+
 // decompressor::run's output (recode.cpp:1338-1357): the literals and the regenerated slices in
-// block order, each slice patched by the last-byte rule (x264 padding correction, 1345-1356), then
-// -- a block with field 17 -- escaped: the patch decides the slice's last byte and length, and both
-// can change what is inserted before that byte.
-// slice(k, &p, &len) gives plan slice k's regenerated bytes and returns its status.
+// block order, each slice patched by the last-byte rule, then -- a block with field 17 -- escaped:
+// the patch decides the slice's last byte and length, and both can change what is inserted before
+// that byte.
+// slice(route, &p, &len) gives a coded block's regenerated bytes and returns its status.
 template <class Slice>
 int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>* o) {
   o->reserve(j.stream.size());
@@ -314,15 +410,11 @@ int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>*
     if (k == -1) return fail(c, AVR_ERR_FORMAT, "Not all blocks were decoded.");
     const uint8_t* p = nullptr;
     size_t len = 0;
-    if (int stt = slice(k, &p, &len))
+    if (int stt = slice(route_of_block(k), &p, &len))
       return fail(c, AVR_ERR_FORMAT, "slice " + std::to_string(k) + " failed to decode (" + std::to_string(stt) + ")");
     const size_t o0 = o->size();
     o->insert(o->end(), p, p + len);
-    if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {
-      const size_t n = o->size() - o0;
-      if ((int)b.length_parity != (int)(n & 1)) o->push_back((uint8_t)b.last_byte[0]);
-      else if (n) o->back() = (uint8_t)b.last_byte[0];
-    }
+    patch_last_byte(b, len, o);
     if (b.has_escapes) {
       const std::vector<uint8_t> e = avr::escape(o->data() + o0, o->size() - o0);
       if (e.size() - (o->size() - o0) != b.escapes)

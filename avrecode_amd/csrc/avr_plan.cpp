@@ -85,7 +85,6 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
   uint64_t seq_check = 1;
   std::vector<avr_slice_desc> descs;
   std::vector<int> block_of;
-  Plan local;
   for (auto& s : pf.slices) {
     while (next_coded < j->blocks.size() && !j->blocks[next_coded].has_cabac && !j->blocks[next_coded].has_skip)
       next_coded++;
@@ -160,16 +159,12 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
   if (plan->layout_only) {
     plan->arena_copies.insert(plan->arena_copies.end(), copies.begin(), copies.end());
     plan->arena_end = at;
-    for (size_t k = 0; k < descs.size(); k++) {
-      j->desc_of_block[block_of[k]] = (int)plan->descs.size();
-      plan->descs.push_back(descs[k]);
-    }
-    return AVR_OK;
+  } else {
+    const size_t a0 = plan->arena.size();
+    plan->arena.resize(at);
+    zero_gaps(copies, plan->arena.data(), a0, at);
+    parallel_copies(copies, plan->arena.data());
   }
-  const size_t a0 = plan->arena.size();
-  plan->arena.resize(at);
-  zero_gaps(copies, plan->arena.data(), a0, at);
-  parallel_copies(copies, plan->arena.data());
   for (size_t k = 0; k < descs.size(); k++) {
     j->desc_of_block[block_of[k]] = (int)plan->descs.size();
     plan->descs.push_back(descs[k]);
@@ -252,10 +247,7 @@ int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* r
     const size_t len = lens[k];
     if (b.has_escapes) {
       std::vector<uint8_t> p(regen + offsets[k], regen + offsets[k] + len);
-      if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {
-        if ((int)b.length_parity != (int)(len & 1)) p.push_back((uint8_t)b.last_byte[0]);
-        else if (len) p.back() = (uint8_t)b.last_byte[0];
-      }
+      patch_last_byte(b, len, &p);
       std::vector<uint8_t> e = avr::escape(p.data(), p.size());
       if (e.size() - p.size() != b.escapes) return AVR_ERR_FORMAT;   // not the count the block recorded
       side->push_back(std::move(e));
@@ -264,11 +256,9 @@ int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* r
       continue;
     }
     if (len) copies->push_back({at, regen + offsets[k], len});
-    size_t m = len;
-    if (b.has_parity && b.has_last_byte && !b.last_byte.empty()) {   // recode.cpp:1345-1356
-      if ((int)b.length_parity != (int)(m & 1)) patches->push_back({at + m, (uint8_t)b.last_byte[0]}), m++;
-      else if (m) patches->push_back({at + m - 1, (uint8_t)b.last_byte[0]});
-    }
+    const LastByte rule = last_byte_rule(b, len);
+    const size_t m = len + (rule == LastByte::kAppend);
+    if (rule != LastByte::kKeep) patches->push_back({at + m - 1, (uint8_t)b.last_byte[0]});
     at += m;
   }
   *total = at;

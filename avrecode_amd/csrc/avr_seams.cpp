@@ -168,7 +168,9 @@ bool splice_pieces(const avr_slice_desc* d, const avr_slice_result* r, const uin
   }
   return true;
 }
-// recode.cpp:1345-1356 on a regenerated slice (before it: the trailing 0x80 already dropped)
+// recode.cpp:1345-1356 on a regenerated slice (before it: the trailing 0x80 already dropped): the
+// compress side's form of last_byte_rule (avr_host.h), from the payload whose block, size > 1, will
+// carry the payload's parity and last byte
 void last_byte_patch(std::vector<uint8_t>* o, const uint8_t* payload, size_t size) {
   if (size <= 1) return;
   if ((int)(size & 1) != (int)(o->size() & 1)) o->push_back(payload[size - 1]);
