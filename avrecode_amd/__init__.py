@@ -25,7 +25,8 @@ __all__ = [
     "SLICE_RESULT", "SynthParams", "lib", "parse_stream", "assemble_container", "neighbor_tables",
     "plan_decompress", "splice_container", "container_model", "source_sha", "library_path", "EXPORTED_SYMBOLS",
     "seams_of_container", "SPLIT_SLOT", "SplitPlan", "split_plan", "seams_build", "escape_payload",
-    "ASSEMBLE_ESCAPED", "ASSEMBLE_SPLIT32",
+    "ASSEMBLE_ESCAPED", "ASSEMBLE_SPLIT32", "ASSEMBLE_CRC", "ERR_CHECKSUM", "crc32", "crc32_combine",
+    "file_crc_of_container",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,13 +42,15 @@ MODEL_CHAINED = 3   # the reference model in chains of CHAIN_SLICES coded slices
 CHAIN_SLICES = 16
 ASSEMBLE_ESCAPED = 1   # avr_assemble_container_opts' flag: the second search of Context.recode_escaped
 ASSEMBLE_SPLIT32 = 2   # and: seams fields for MODEL_PARALLEL32, under the "P32S" / "P32SE" tags (Context.split_p32)
+ASSEMBLE_CRC = 4       # and: a checked container, the file's CRC-32 in Metadata field 16 (Context.checksums)
+ERR_CHECKSUM = -7      # AVR_ERR_CHECKSUM: the container decoded, and its file is not the file it was made from
 SPLIT_BYTES_DEFAULT = 98304   # the parallel model's long-slice split (Context.split_bytes), unless AVR_SPLIT_BYTES
 MODEL_NAMES = {MODEL_REFERENCE: "R", MODEL_PARALLEL: "P", MODEL_PARALLEL32: "P32", MODEL_CHAINED: "C"}
 
 AVR_OK = 0
 _STATUS = {
     -1: "invalid argument", -2: "device error", -3: "format error", -4: "out of memory",
-    -5: "roundtrip mismatch", -6: "unsupported",
+    -5: "roundtrip mismatch", -6: "unsupported", -7: "checksum mismatch",
 }
 
 # every function include/avrecode.h declares
@@ -69,6 +72,8 @@ EXPORTED_SYMBOLS = (
     "avr_compress_split_slices", "avr_stage_pieces", "avr_verify_units",
     "avr_set_recode_escaped", "avr_get_recode_escaped", "avr_escape_payload", "avr_assemble_container_opts",
     "avr_set_split_p32", "avr_get_split_p32", "avr_compress_split_slices_m", "avr_decompress_pieces_m",
+    "avr_set_checksums", "avr_get_checksums", "avr_crc32", "avr_crc32_combine", "avr_crc_spans",
+    "avr_assemble_container_args", "avr_dec_plan_splice_crc",
 )
 
 # avr_slice_desc / avr_slice_result (include/avrecode.h), C layout
@@ -126,6 +131,15 @@ class _FileStats(ctypes.Structure):
                 ("bill", ctypes.c_uint64 * 6), ("cabac_bill", ctypes.c_uint64 * 6),
                 ("attempts", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("compress_phases", _PhaseTimes), ("decompress_phases", _PhaseTimes)]
+
+
+class _AssembleArgs(ctypes.Structure):   # avr_assemble_args
+    _fields_ = [("size", ctypes.c_size_t), ("file", ctypes.c_void_p), ("n", ctypes.c_size_t), ("model", ctypes.c_int),
+                ("descs", ctypes.c_void_p), ("n_slices", ctypes.c_int), ("arena", ctypes.c_void_p),
+                ("arena_len", ctypes.c_size_t), ("status", ctypes.c_void_p), ("recoded", ctypes.c_void_p),
+                ("recoded_len", ctypes.c_size_t), ("offsets", ctypes.c_void_p), ("lens", ctypes.c_void_p),
+                ("seams", ctypes.c_void_p), ("seams_len", ctypes.c_size_t), ("seam_offsets", ctypes.c_void_p),
+                ("seam_lens", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("crcs", ctypes.c_void_p)]
 
 
 class _SynthParams(ctypes.Structure):
@@ -252,6 +266,15 @@ def lib() -> ctypes.CDLL:
     L.avr_assemble_container_opts.argtypes = [vp, sz, i32, vp, i32, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp,
                                               ctypes.c_uint32, pp, psz]
     L.avr_get_split_bytes.argtypes = [vp]
+    L.avr_set_checksums.argtypes = [vp, i32]
+    L.avr_get_checksums.argtypes = [vp]
+    L.avr_crc32.argtypes = [ctypes.c_uint32, vp, sz]
+    L.avr_crc32.restype = ctypes.c_uint32
+    L.avr_crc32_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
+    L.avr_crc32_combine.restype = ctypes.c_uint32
+    L.avr_crc_spans.argtypes = [vp, vp, sz, vp, vp, i32, vp, vp, vp]
+    L.avr_assemble_container_args.argtypes = [ctypes.POINTER(_AssembleArgs), pp, psz]
+    L.avr_dec_plan_splice_crc.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, psz]
     L.avr_get_split_bytes.restype = sz
     for name in EXPORTED_SYMBOLS:   # fails here, not at first use, when the build is stale
         getattr(L, name)
@@ -464,7 +487,10 @@ class DecompressPlan:
         return ParsedStream(self.units.copy(), a, self.work_len, self.max_mb_width, self.max_mb_height,
                             self.pieces.copy(), self.recs, self.rec_stride)
 
-    def splice(self, status, regen, offsets, lens, out: "np.ndarray | None" = None):
+    def splice(self, status, regen, offsets, lens, out: "np.ndarray | None" = None, crcs=None):
+        """The file from the regenerated slices (avr_dec_plan_splice).  A checked container is checked
+        (AvrError ERR_CHECKSUM); crcs: the CRC-32 of each slice's regenerated bytes as a device
+        computed it (avr_dec_plan_splice_crc), else the splice computes them on host threads."""
         st = np.ascontiguousarray(status, dtype=np.int32)
         of = np.ascontiguousarray(offsets, dtype=np.uint64)
         ln = np.ascontiguousarray(lens, dtype=np.uint32)
@@ -473,12 +499,18 @@ class DecompressPlan:
         rp, rn, keep = _buf(regen)
         olen = ctypes.c_size_t()
         L = lib()
+        cr = None if crcs is None else np.ascontiguousarray(crcs, dtype=np.uint32)
+        if cr is not None and len(cr) != len(st):
+            raise ValueError("DecompressPlan.splice: one crc per planned slice")
+        cp = None if cr is None else cr.ctypes.data
         if out is None:
-            L.avr_dec_plan_splice(self._h, st.ctypes.data, rp, rn, of.ctypes.data, ln.ctypes.data, None, 0,
-                                  ctypes.byref(olen))
+            r = L.avr_dec_plan_splice_crc(self._h, st.ctypes.data, rp, rn, of.ctypes.data, ln.ctypes.data, cp, None, 0,
+                                          ctypes.byref(olen))
+            if r == ERR_CHECKSUM:
+                raise AvrError(r, "avr_dec_plan_splice failed")
             out = np.empty(olen.value, dtype=np.uint8)
-        r = L.avr_dec_plan_splice(self._h, st.ctypes.data, rp, rn, of.ctypes.data, ln.ctypes.data, out.ctypes.data,
-                                  out.nbytes, ctypes.byref(olen))
+        r = L.avr_dec_plan_splice_crc(self._h, st.ctypes.data, rp, rn, of.ctypes.data, ln.ctypes.data, cp,
+                                      out.ctypes.data, out.nbytes, ctypes.byref(olen))
         if r != AVR_OK:
             raise AvrError(r, f"avr_dec_plan_splice failed (file {olen.value} B, buffer {out.nbytes} B)")
         return out[:olen.value]
@@ -493,6 +525,17 @@ class DecompressPlan:
             self.close()
         except Exception:
             pass
+
+
+def crc32(data, crc: int = 0) -> int:
+    """zlib.crc32 through the library (avr_crc32).  Host only."""
+    p, n, keep = _buf(data)
+    return int(lib().avr_crc32(crc & 0xFFFFFFFF, p, n))
+
+
+def crc32_combine(a: int, b: int, len_b: int) -> int:
+    """crc(A + B) from crc(A), crc(B) and len(B) (avr_crc32_combine).  Host only."""
+    return int(lib().avr_crc32_combine(a & 0xFFFFFFFF, b & 0xFFFFFFFF, int(len_b)))
 
 
 def container_model(avrc) -> int:
@@ -594,7 +637,8 @@ def seams_build(descs, arena, res, slots, cuts, piece_end, recs, rec_stride: int
 
 def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, lens: np.ndarray,
                        model: int = MODEL_PARALLEL, ps: "ParsedStream | None" = None, as_array: bool = False,
-                       out: "np.ndarray | None" = None, seams=None, escaped: bool = False, split32: bool = False):
+                       out: "np.ndarray | None" = None, seams=None, escaped: bool = False, split32: bool = False,
+                       crcs=None, checksums: bool = False):
     """Recoded container from per-slice outputs gathered from the ranks (avr_assemble_container; with ps =
     parse_stream(data) already in hand, avr_assemble_container_parsed: no second parse).  recoded:
     bytes or a uint8 array.  model: the model / coder the outputs were made with (PARALLEL, PARALLEL32,
@@ -610,17 +654,55 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
     only, not with out), so that the result is what ctx.compress writes with the option on.
     split32 (ASSEMBLE_SPLIT32; MODEL_PARALLEL32 only, not with out): seams are allowed for that model
     and a container that holds one is tagged P32S / P32SE, what ctx.compress writes with
-    Context.split_p32 on.  Host only."""
+    Context.split_p32 on.
+    checksums (ASSEMBLE_CRC; any model, not with out): a checked container, what ctx.compress writes
+    with Context.checksums on (avr_assemble_container_args); crcs: the CRC-32 of every slice's payload
+    as the ranks' devices computed them (read for coded slices; trusted), else the assembly computes
+    them on host threads.  Host only."""
     L = lib()
     flags = (ASSEMBLE_ESCAPED if escaped else 0) | (ASSEMBLE_SPLIT32 if split32 else 0)
-    if flags and out is not None:
-        raise ValueError("assemble_container: escaped / split32 cannot be combined with out")
+    if (flags or checksums) and out is not None:
+        raise ValueError("assemble_container: escaped / split32 / checksums cannot be combined with out")
     p, n, keep = _buf(data)
     st = np.ascontiguousarray(status, dtype=np.int32)
     of = np.ascontiguousarray(offsets, dtype=np.uint64)
     ln = np.ascontiguousarray(lens, dtype=np.uint32)
     rp, rn, keep2 = _buf(recoded)
     res, olen = ctypes.c_void_p(), ctypes.c_size_t()
+    if checksums:
+        a = _AssembleArgs()
+        a.size, a.file, a.n, a.model, a.n_slices = ctypes.sizeof(_AssembleArgs), p, n, model, len(st)
+        a.status, a.recoded, a.recoded_len, a.offsets, a.lens = st.ctypes.data, rp, rn, of.ctypes.data, ln.ctypes.data
+        a.flags = flags | ASSEMBLE_CRC
+        if len(of) != len(st) or len(ln) != len(st):
+            raise ValueError("assemble_container: status / offsets / lens need one entry per slice")
+        if ps is not None:
+            dd = np.ascontiguousarray(ps.descs)
+            if len(dd) != len(st):
+                raise ValueError("assemble_container: status / offsets / lens need one entry per parsed slice")
+            a.descs, a.arena, a.arena_len = dd.ctypes.data, ps.arena.ctypes.data, ps.arena.nbytes
+        if seams is not None:
+            if isinstance(seams, list):
+                sl = np.array([len(x) for x in seams], dtype=np.uint32)
+                so = (np.cumsum(sl, dtype=np.uint64) - sl).astype(np.uint64)
+                sb = b"".join(seams)
+            else:
+                sb, so, sl = seams
+                so = np.ascontiguousarray(so, dtype=np.uint64)
+                sl = np.ascontiguousarray(sl, dtype=np.uint32)
+            if len(so) != len(st) or len(sl) != len(st):
+                raise ValueError("assemble_container: seams need one entry per slice")
+            sp, sn, keep3 = _buf(sb)
+            a.seams, a.seams_len, a.seam_offsets, a.seam_lens = sp, sn, so.ctypes.data, sl.ctypes.data
+        if crcs is not None:
+            cr = np.ascontiguousarray(crcs, dtype=np.uint32)
+            if len(cr) != len(st):
+                raise ValueError("assemble_container: crcs need one entry per slice")
+            a.crcs = cr.ctypes.data
+        r = L.avr_assemble_container_args(ctypes.byref(a), ctypes.byref(res), ctypes.byref(olen))
+        if r != AVR_OK:
+            raise AvrError(r, "avr_assemble_container_args failed")
+        return _take_array(res, olen.value) if as_array else _take(res, olen.value)
     if seams is not None:
         if out is not None:
             raise ValueError("assemble_container: seams cannot be combined with out")
@@ -737,6 +819,33 @@ def seams_of_container(avrc) -> list:
     return out
 
 
+def file_crc_of_container(avrc) -> "int | None":
+    """The file's CRC-32 a checked container carries (Recoded.Metadata field 16), or None: a walk over
+    the top-level fields that reads the Metadata only (no block's bytes).  Host only."""
+    b = memoryview(avrc) if not isinstance(avrc, np.ndarray) else memoryview(np.ascontiguousarray(avrc).view(np.uint8))
+    i, n = 0, len(b)
+    while i < n:
+        tag, i = _varint(b, i)
+        if tag & 7 != 2:
+            return None   # the writer's containers hold length-delimited fields only
+        ln, i = _varint(b, i)
+        if tag >> 3 == 1:
+            j, e = i, i + ln
+            while j < e:
+                t2, j = _varint(b, j)
+                if t2 == (16 << 3 | 5):
+                    return int.from_bytes(bytes(b[j:j + 4]), "little")
+                if t2 & 7 == 2:
+                    l2, j = _varint(b, j)
+                    j += l2
+                elif t2 & 7 == 0:
+                    _, j = _varint(b, j)
+                else:
+                    j += 4 if t2 & 7 == 5 else 8
+        i += ln
+    return None
+
+
 def describe_container(avrc) -> tuple[dict, bytes]:
     """Parse a Recoded protobuf with the library's wire codec (avr_container_describe): its fields
     (hex strings for bytes) and the message re-serialised by the library's writer.  Host only."""
@@ -843,6 +952,27 @@ class Context:
         self._check(lib().avr_set_recode_escaped(self._h, 1 if on else 0), "avr_set_recode_escaped")
 
     # ------------------------------------------------------------------ whole files
+    @property
+    def checksums(self) -> bool:
+        """Checked containers (avr_set_checksums; default: AVR_CHECKSUMS, else off): compress and
+        roundtrip of every model write the file's CRC-32 (zlib.crc32) into Recoded.Metadata field 16,
+        6 bytes (8 for the reference model), folded from per-slice CRCs the device computes.  Reading
+        needs no option: every decompress of a container that has the field checks it and raises
+        AvrError with code ERR_CHECKSUM on a mismatch."""
+        return bool(lib().avr_get_checksums(self._h))
+
+    @checksums.setter
+    def checksums(self, on: bool):
+        self._check(lib().avr_set_checksums(self._h, 1 if on else 0), "avr_set_checksums")
+
+    def crc_spans(self, d_buf, buf_len, d_off, d_len, n, d_crc, d_status, stream=None):
+        """d_crc[k] = the CRC-32 of d_buf[d_off[k] : d_off[k] + d_len[k]] (avr_crc_spans: one workgroup
+        per span, device tensors, nothing synchronised); d_status[k] = SLICE_OVERFLOW for a span outside
+        buf_len."""
+        self._check(lib().avr_crc_spans(self._h, self._ptr(d_buf), int(buf_len), self._ptr(d_off), self._ptr(d_len),
+                                        int(n), self._ptr(d_crc), self._ptr(d_status), self._stream(stream)),
+                    "avr_crc_spans")
+
     def compress(self, data, model: int = MODEL_REFERENCE) -> bytes:
         p, n, keep = _buf(data)
         out, olen = ctypes.c_void_p(), ctypes.c_size_t()

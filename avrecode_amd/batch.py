@@ -22,6 +22,29 @@ def _dev_bytes(a: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(device)
 
 
+def _payload_spans(descs, device):
+    """(d_off int64[n], d_len int32[n]) of a batch's payloads in its input arena."""
+    off = torch.from_numpy(descs["payload_offset"].astype(np.int64)).to(device)
+    ln = torch.from_numpy(descs["payload_size"].astype(np.uint32).view(np.int32).copy()).to(device)
+    return off, ln
+
+
+def _packed_spans(d_offsets, n: int, d_kept=None):
+    """(d_off, d_len) of n packed outputs: where a pack left them, as long as it made them."""
+    off = d_offsets[:n].contiguous()
+    ln = d_kept[:n].contiguous() if d_kept is not None else (d_offsets[1:n + 1] - d_offsets[:n]).to(torch.int32)
+    return off, ln
+
+
+def _crc_spans(b, d_off, d_len, d_buf, stream=None):
+    n = int(d_off.numel())
+    d_crc = torch.zeros(max(1, n), dtype=torch.int32, device=b.device)
+    d_status = torch.zeros(max(1, n), dtype=torch.int32, device=b.device)
+    with torch.cuda.stream(stream) if stream is not None else _null():
+        b.ctx.crc_spans(d_buf, d_buf.numel(), d_off, d_len, n, d_crc, d_status, stream)
+    return d_crc, d_status
+
+
 class DeviceBatch:
     def __init__(self, ctx: Context, ps: ParsedStream, device=None):
         self.ctx = ctx
@@ -76,6 +99,15 @@ class DeviceBatch:
         res = self.d_res_c if which == "c" else self.d_res_d
         self.ctx.pack_outputs(self.d_desc, res, self.n, self.d_work, self.d_packed, self.d_offsets, stream)
         return self.d_packed, self.d_offsets
+
+    def crcs(self, which: str = "in", stream=None):
+        """The CRC-32 of every slice's bytes where they lie on the device (avr_crc_spans), for a checked
+        container: "in" = the payloads in the input arena (a compress batch: what the file's CRC is
+        folded from), "packed" = the outputs pack() left in d_packed (a decompress batch: the
+        regenerated slices).  (d_crc int32[n] holding uint32, d_status int32[n]); nothing is synchronised."""
+        return _crc_spans(self, *(_payload_spans(self.ps.descs, self.device) if which == "in" else
+                                  _packed_spans(self.d_offsets, self.n)),
+                          self.d_in if which == "in" else self.d_packed, stream)
 
     # ----------------------------------------------------------------- results (host copies)
     def results(self, which: str = "c") -> np.ndarray:
@@ -224,6 +256,11 @@ class UnitBatch:
                              d_status, stream)
         return d_packed, d_offsets, d_kept, d_status
 
+    def crcs(self, d_packed, d_offsets, d_kept, stream=None):
+        """The CRC-32 of every unit's kept bytes in pack()'s outputs (avr_crc_spans): (d_crc, d_status) per
+        unit; shard.collapse_unit_crcs folds a cut slice's into the slice's."""
+        return _crc_spans(self, *_packed_spans(d_offsets, self.n, d_kept), d_packed, stream)
+
     def results(self) -> np.ndarray:
         return self.d_res.cpu().numpy().reshape(-1).view(SLICE_RESULT)[: self.n]
 
@@ -367,6 +404,10 @@ class SplitBatch:
             self.decompress(stream)
             self.pack(stream)
             self.verify(stream)
+
+    def crcs(self, stream=None):
+        """The CRC-32 of every slice's payload in the input arena (avr_crc_spans): (d_crc, d_status)."""
+        return _crc_spans(self, *_payload_spans(self.ps.descs, self.device), self.d_in, stream)
 
     def pack_recoded(self, stream=None):
         """The slices' re-coded bytes packed contiguously on the device (avr_pack_outputs):

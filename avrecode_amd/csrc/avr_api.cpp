@@ -335,6 +335,7 @@ struct SplitOut {
   int32_t status = 0;
   std::vector<uint8_t> recoded, seams;   // seams empty: no cut
   avr_slice_result bill{};
+  uint32_t crc = 0;   // SplitJob::crc: the payload's CRC-32
 };
 struct SplitJob {
   std::vector<const avr::SliceInfo*> sl;
@@ -347,6 +348,7 @@ struct SplitJob {
   size_t stride = 0;
   int max_w = 1;
   uint32_t coder = 0;   // coder_flag(model): the walk's and the verify launch's coder
+  bool crc = false;     // a checked container: the payloads' CRCs too, over the uploaded arena
   EventPair ev;   // around the split compress kernel
 };
 
@@ -380,6 +382,11 @@ int split_begin(avr_ctx* c, SplitJob* j, size_t split_bytes, uint32_t flags) {
   HIP_TRY(c, hipMemcpyAsync(c->sp_in.p, j->arena.data(), j->arena.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(c->sp_descs.p, j->d.data(), sizeof(avr_slice_desc) * n, hipMemcpyHostToDevice, st));
   uint32_t* cuts = c->sp_snapn.as<uint32_t>();   // then the piece ends
+  if (j->crc) {
+    HIP_TRY(c, c->sp_crc.reserve(2 * sizeof(uint32_t) * n));
+    HIP_TRY(c, avr::launch_crc_slices(c->sp_descs.as<avr_slice_desc>(), nullptr, n, false, c->sp_in.as<uint8_t>(),
+                                      j->arena.size(), c->sp_crc.as<uint32_t>(), c->sp_crc.as<int32_t>() + n, st));
+  }
   return launch_split_walk(c, c->sp_descs.as<avr_slice_desc>(), n, j->max_w, c->sp_in.as<uint8_t>(),
                            c->sp_out.as<uint8_t>(), c->sp_res.as<avr_slice_result>(), j->slots.data(),
                            c->sp_recs.as<uint8_t>(), (int)j->nrec, j->stride, cuts, cuts + n, split_bytes,
@@ -466,7 +473,11 @@ int split_finish(avr_ctx* c, SplitJob* j, bool verify, std::vector<SplitOut>* ou
   HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->sp_snapn.p, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(out1.data(), c->sp_out.p, j->out_total, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(recs.data(), c->sp_recs.p, recs.size(), hipMemcpyDeviceToHost, st));
+  std::vector<uint32_t> crcs(j->crc ? 2 * (size_t)n : 0);   // then the statuses
+  if (j->crc) HIP_TRY(c, hipMemcpyAsync(crcs.data(), c->sp_crc.p, sizeof(uint32_t) * crcs.size(), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
+  for (int k = 0; j->crc && k < n; k++)   // a payload inside the arena is never refused
+    (*out)[k].crc = crcs[n + k] == 0 ? crcs[k] : avr_crc32(0, j->sl[k]->payload(), j->sl[k]->size);
   float ms = 0;
   HIP_TRY(c, hipEventElapsedTime(&ms, j->ev.e0, j->ev.e1));
   if (split_timing()) fprintf(stderr, "split: compress kernel %.3f s (%d slices)\n", 1e-3 * ms, n);
@@ -635,6 +646,11 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   const size_t split_bytes =
       model == AVR_MODEL_PARALLEL || (model == AVR_MODEL_PARALLEL32 && c->split_p32) ? c->split_bytes : 0;
   sj.coder = coder_flag(model);
+  // a checked container (avr_set_checksums): the candidates' payload CRCs from the device, where the
+  // uploads put them; the reference models' pass re-plans, and its payloads are CRC'd by emit_container
+  const bool checks = c->checksums;
+  sj.crc = checks;
+  SliceCrcs crcs_dev;
   if (parallel_model(model)) plan_candidates(pf, st, split_bytes, &plan, &sj.sl, &sj.d, &route);
   // 2) launch the split job's first pass on the split stream, then the batch beside it; collect
   std::vector<avr_slice_result> res;
@@ -642,7 +658,7 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   pc.mark_demux();
   const uint32_t bill_flag = bills ? avr::kFlagBill : 0u;
   if (int r = split_begin(c, &sj, split_bytes, bill_flag)) return r;
-  if (int r = run_plan(c, 0, false, plan, &res, &outb, verify, bill_flag | coder_flag(model))) {
+  if (int r = run_plan(c, 0, false, plan, &res, &outb, verify, bill_flag | coder_flag(model), checks ? &crcs_dev : nullptr)) {
     (void)hipStreamSynchronize(c->split_stream);   // its first pass still reads sj's buffers
     return r;
   }
@@ -674,6 +690,8 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   for (int f = 0; f < nf; f++) recoded[f].resize(pf[f].slices.size());
   std::vector<std::vector<std::pair<const uint8_t*, size_t>>> seams_of(nf);
   for (int f = 0; f < nf; f++) seams_of[f].assign(pf[f].slices.size(), {nullptr, 0});
+  std::vector<std::vector<uint32_t>> crc_of(nf);
+  for (int f = 0; f < nf && checks && parallel_model(model); f++) crc_of[f].assign(pf[f].slices.size(), 0);
   if (reference_model(model)) {
     if (int r = reference_pass(c, nf, in, in_len, model, pf, bills, st, ok, found, recoded)) return r;
   } else {
@@ -685,9 +703,13 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
           SplitOut& x = so[r.index];
           recoded[f][i].swap(x.recoded);
           seams_of[f][i] = {x.seams.data(), x.seams.size()};
+          if (checks) crc_of[f][i] = x.crc;
           if (bills) add_bill(&(*bills)[f], x.bill);
           continue;
         }
+        if (checks)
+          crc_of[f][i] = crcs_dev.have(r.index) ? crcs_dev.crc[r.index]
+                                                : avr_crc32(0, pf[f].slices[i].payload(), pf[f].slices[i].size);
         recoded[f][i].assign(outb.begin() + plan.descs[r.index].out_offset,
                              outb.begin() + plan.descs[r.index].out_offset + res[r.index].out_len);
         if (bills) add_bill(&(*bills)[f], res[r.index]);
@@ -700,7 +722,8 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
     std::vector<std::pair<const uint8_t*, size_t>> blobs(pf[f].slices.size(), {nullptr, 0});
     for (size_t i = 0; i < pf[f].slices.size(); i++) blobs[i] = {recoded[f][i].data(), recoded[f][i].size()};
     st[f] = emit_container(in[f], in_len[f], views_of(pf[f]), found[f], blobs, model, &out[f], &out_len[f], nullptr, 0,
-                           &seams_of[f], escaped ? &escapes[f] : nullptr);
+                           &seams_of[f], escaped ? &escapes[f] : nullptr,
+                           FileCrcArg{checks, crc_of[f].empty() ? nullptr : crc_of[f].data()});
   });
   for (int f = 0; f < nf; f++) {
     if (status) status[f] = st[f];
@@ -783,6 +806,12 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
   }
   std::vector<avr_slice_result> res_of[3];
   std::vector<uint8_t> out_of[3];
+  // checked containers: the regenerated slices' CRCs from the device, before the download (the pieces
+  // of split blocks are spliced on the host, and CRC'd there by the fold)
+  SliceCrcs crcs_of[3];
+  bool checks[3] = {false, false, false};
+  for (int f = 0; f < nf; f++)
+    if (st[f] == AVR_OK && jobs[f].has_crc) checks[plan_of(jobs[f].model)] = true;
   pc.mark_demux();
   // 2) launch the pieces, then the slice plans beside them
   std::vector<avr_slice_result> prs[2];
@@ -793,13 +822,14 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
   auto drain = [&]() { (void)hipStreamSynchronize(c->split_stream); };
   for (int m = AVR_MODEL_PARALLEL; m <= AVR_MODEL_PARALLEL32; m++)
     if (!plans[m].descs.empty())
-      if (int r = run_plan(c, 1, false, plans[m], &res_of[m], &out_of[m], false, flags | coder_flag(m))) {
+      if (int r = run_plan(c, 1, false, plans[m], &res_of[m], &out_of[m], false, flags | coder_flag(m),
+                           checks[m] ? &crcs_of[m] : nullptr)) {
         drain();
         return r;
       }
   if (!rp.file_first.empty()) {
     rp.file_first.push_back((int)rp.descs.size());
-    if (int r = run_plan(c, 1, true, rp, &res_of[0], &out_of[0], false, flags)) {
+    if (int r = run_plan(c, 1, true, rp, &res_of[0], &out_of[0], false, flags, checks[0] ? &crcs_of[0] : nullptr)) {
       drain();
       return r;
     }
@@ -848,7 +878,12 @@ int decompress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t*
         *len = res[r.index].out_len;
         if (bills && res[r.index].status == 0) add_bill(&(*bills)[f], res[r.index]);
         return res[r.index].status;
-      }, &o);
+      }, &o, [&](Route r, uint32_t* crc) {
+        const SliceCrcs& cs = crcs_of[plan_of(j.model)];
+        if (r.kind != Route::kBatch || !cs.have(r.index)) return false;
+        *crc = cs.crc[r.index];
+        return true;
+      });
     if (st[f] == AVR_OK) {
       out[f] = (uint8_t*)malloc(o.size() ? o.size() : 1);
       if (!out[f]) {
@@ -990,8 +1025,9 @@ namespace avr_host {
 // instantiated below for the two host buffers it is used with
 template <class HostBuf>
 int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_slice_result>* res,
-             HostBuf* out_host, bool verify, uint32_t flags) {
+             HostBuf* out_host, bool verify, uint32_t flags, SliceCrcs* crcs) {
   const int n = (int)plan.descs.size();
+  if (crcs) crcs->crc.clear(), crcs->status.clear();
   if (plan.fields()) flags |= avr::kFlagFields;
   // a parallel batch of progressive and field slices: the two kernels side by side
   const avr::FieldLane lane = !sequential && plan.mixed() ? c->field_lane() : avr::FieldLane();
@@ -1067,7 +1103,22 @@ int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_
     verdict.resize(n);
     HIP_TRY(c, hipMemcpyAsync(verdict.data(), c->verdict.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
   }
+  if (crcs) {
+    // the payloads where the upload put them, or the regenerated bytes where the kernel left them
+    HIP_TRY(c, c->crc.reserve(2 * sizeof(uint32_t) * n));
+    crcs->crc.resize(n);
+    crcs->status.resize(n);
+    HIP_TRY(c, avr::launch_crc_slices(c->descs.as<avr_slice_desc>(), c->res.as<avr_slice_result>(), n, mode == 1,
+                                      mode == 1 ? c->out.as<uint8_t>() : c->in.as<uint8_t>(),
+                                      mode == 1 ? out_total : plan.arena.size(), c->crc.as<uint32_t>(),
+                                      c->crc.as<int32_t>() + n, c->stream));
+  }
   HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  if (crcs) {
+    HIP_TRY(c, hipMemcpyAsync(crcs->crc.data(), c->crc.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(crcs->status.data(), c->crc.as<int32_t>() + n, sizeof(int32_t) * n, hipMemcpyDeviceToHost,
+                              c->stream));
+  }
   HIP_TRY(c, hipMemcpyAsync(res->data(), c->res.p, sizeof(avr_slice_result) * n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(out_host->data(), c->out.p, out_total, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
@@ -1083,8 +1134,9 @@ int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_
   return AVR_OK;
 }
 
-template int run_plan(avr_ctx*, int, bool, Plan&, std::vector<avr_slice_result>*, Bytes*, bool, uint32_t);
-template int run_plan(avr_ctx*, int, bool, Plan&, std::vector<avr_slice_result>*, std::vector<uint8_t>*, bool, uint32_t);
+template int run_plan(avr_ctx*, int, bool, Plan&, std::vector<avr_slice_result>*, Bytes*, bool, uint32_t, SliceCrcs*);
+template int run_plan(avr_ctx*, int, bool, Plan&, std::vector<avr_slice_result>*, std::vector<uint8_t>*, bool, uint32_t,
+                      SliceCrcs*);
 
 }  // namespace avr_host
 
@@ -1107,6 +1159,7 @@ int avr_create(int device, avr_ctx** out) {
   }
   if (const char* e = getenv("AVR_RECODE_ESCAPED")) c->recode_escaped = strtol(e, nullptr, 10) != 0;
   if (const char* e = getenv("AVR_SPLIT_P32")) c->split_p32 = strtol(e, nullptr, 10) != 0;
+  if (const char* e = getenv("AVR_CHECKSUMS")) c->checksums = strtol(e, nullptr, 10) != 0;
   if (const char* e = getenv("AVR_FIELD_LANE"); !e || strcmp(e, "0") != 0) {
     if (hipStreamCreateWithFlags(&c->fld_stream, hipStreamNonBlocking) != hipSuccess) return AVR_ERR_DEVICE;
     for (auto& ev : c->fld_ev)
@@ -1154,6 +1207,13 @@ int avr_set_recode_escaped(avr_ctx* c, int on) {
   return AVR_OK;
 }
 int avr_get_recode_escaped(const avr_ctx* c) { return c && c->recode_escaped; }
+
+int avr_set_checksums(avr_ctx* c, int on) {
+  if (!c) return AVR_ERR_INVALID_ARGUMENT;
+  c->checksums = on != 0;
+  return AVR_OK;
+}
+int avr_get_checksums(const avr_ctx* c) { return c && c->checksums; }
 
 void avr_free(void* p) { free(p); }
 
@@ -1486,6 +1546,16 @@ int avr_pack_outputs(avr_ctx* c, const avr_slice_desc* d_desc, const avr_slice_r
   if (!c || n < 0 || (n && (!d_desc || !d_res || !d_out || !d_packed || !d_offsets))) return AVR_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, avr::launch_pack(d_desc, d_res, n, d_out, d_packed, d_offsets, (hipStream_t)stream));
+  return AVR_OK;
+}
+
+int avr_crc_spans(avr_ctx* c, const uint8_t* d_buf, size_t buf_len, const uint64_t* d_off, const uint32_t* d_len, int n,
+                  uint32_t* d_crc, int32_t* d_status, void* stream) {
+  if (!c) return AVR_ERR_INVALID_ARGUMENT;
+  if (n <= 0) return AVR_OK;
+  if (!d_buf || !d_off || !d_len || !d_crc || !d_status) return AVR_ERR_INVALID_ARGUMENT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, avr::launch_crc_spans(d_buf, buf_len, d_off, d_len, n, d_crc, d_status, (hipStream_t)stream));
   return AVR_OK;
 }
 

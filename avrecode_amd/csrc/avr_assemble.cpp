@@ -159,9 +159,10 @@ struct SeamsArg {
 int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceView>& sv, const int32_t* status,
              const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out,
              size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0, const SeamsArg& sa = SeamsArg(),
-             uint32_t flags = 0) {
-  // the escaped second chance is the parallel models' own format, the opt-in split the P32 coder's
-  if ((flags & ~(uint32_t)(AVR_ASSEMBLE_ESCAPED | AVR_ASSEMBLE_SPLIT32)) ||
+             uint32_t flags = 0, const uint32_t* crcs = nullptr) {
+  // the escaped second chance is the parallel models' own format, the opt-in split the P32 coder's;
+  // the file's CRC is any model's
+  if ((flags & ~(uint32_t)(AVR_ASSEMBLE_ESCAPED | AVR_ASSEMBLE_SPLIT32 | AVR_ASSEMBLE_CRC)) ||
       ((flags & AVR_ASSEMBLE_ESCAPED) && !parallel_model(model)) ||
       ((flags & AVR_ASSEMBLE_SPLIT32) && model != AVR_MODEL_PARALLEL32))
     return AVR_ERR_INVALID_ARGUMENT;
@@ -189,7 +190,7 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
   const std::vector<const uint8_t*> found = segment(file, n, sv, ok, esc ? &escapes : nullptr);
   const double t1 = now_s();
   const int r = emit_container(file, n, sv, found, blobs, model, out, out_len, dst, cap, sa.p ? &fields : nullptr,
-                               esc ? &escapes : nullptr);
+                               esc ? &escapes : nullptr, FileCrcArg{(flags & AVR_ASSEMBLE_CRC) != 0, crcs});
   if (getenv("AVR_ASM_TIMING")) fprintf(stderr, "assemble: segment %.3f s, emit %.3f s\n", t1 - t0, now_s() - t1);
   return r;
 }
@@ -197,7 +198,8 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
 int assemble_parsed(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
                     const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
                     size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out, size_t* out_len,
-                    uint8_t* dst, size_t cap, const SeamsArg& sa = SeamsArg(), uint32_t flags = 0) {
+                    uint8_t* dst, size_t cap, const SeamsArg& sa = SeamsArg(), uint32_t flags = 0,
+                    const uint32_t* crcs = nullptr) {
   if (!file || !out_len || n_slices < 0 || (n_slices && (!descs || !arena || !status || !offsets || !lens)) ||
       !assemblable(model) || (sa.p && n_slices && (!sa.offsets || !sa.lens)))
     return AVR_ERR_INVALID_ARGUMENT;
@@ -234,7 +236,8 @@ int assemble_parsed(const uint8_t* file, size_t n, int model, const avr_slice_de
       for (int i = 0; i < n_slices; i++)
         sv[i].nal_lo = pf.slices[i].nal_offset, sv[i].nal_hi = pf.slices[i].nal_offset + pf.slices[i].nal_size;
     }
-    return assemble(file, n, model, sv, status, recoded, recoded_len, offsets, lens, out, out_len, dst, cap, sa, flags);
+    return assemble(file, n, model, sv, status, recoded, recoded_len, offsets, lens, out, out_len, dst, cap, sa, flags,
+                    crcs);
   });
 }
 
@@ -335,10 +338,15 @@ std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const ParsedFil
 int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv, const std::vector<const uint8_t*>& found,
                    const std::vector<std::pair<const uint8_t*, size_t>>& recoded, int model, uint8_t** out,
                    size_t* out_len, uint8_t* dst, size_t cap,
-                   const std::vector<std::pair<const uint8_t*, size_t>>* seams, const std::vector<uint32_t>* escapes) {
+                   const std::vector<std::pair<const uint8_t*, size_t>>* seams, const std::vector<uint32_t>* escapes,
+                   const FileCrcArg& crc) {
   bool any_escapes = false, any_seams = false;
   std::vector<avr::PbBlock> blocks;
   blocks.reserve(2 * sv.size() + 1);
+  // a checked container: what each block contributes to the file's CRC (fold_file_crc) -- a literal
+  // its bytes, a coded block its payload's CRC, an escaped one the size + k file bytes it stands for
+  std::vector<CrcItem> items;
+  if (crc.on) items.reserve(2 * sv.size() + 1);
   size_t prev_end = 0;
   for (size_t i = 0; i < sv.size(); i++) {
     const SliceView& s = sv[i];
@@ -350,6 +358,11 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
       lit.literal_len = (size_t)(found[i] - (in + prev_end));
       blocks.push_back(lit);
       const uint32_t k = escapes ? (*escapes)[i] : 0u;   // the block stands for size + k file bytes
+      if (crc.on) {
+        items.push_back(CrcItem{lit.literal, lit.literal_len});
+        if (k || !crc.crcs) items.push_back(CrcItem{found[i], s.size + k});
+        else items.push_back(CrcItem{nullptr, s.size, crc.crcs[i], true});
+      }
       prev_end = (size_t)(found[i] - in) + s.size + k;
       if (k) b.has_escapes = any_escapes = true, b.escapes = k;
       b.has_size = true;
@@ -375,6 +388,7 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
   lit.literal = in + prev_end;
   lit.literal_len = n - prev_end;
   blocks.push_back(lit);
+  if (crc.on) items.push_back(CrcItem{lit.literal, lit.literal_len});
   std::vector<uint8_t> md;
   // a container without field 17 keeps the plain tag and the plain bytes; so does a P32 one without
   // field 16, and one with it says so in its tag (P32S / P32SE; P64's seams need none)
@@ -382,7 +396,12 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
                     : any_escapes                              ? avr::escaped_version_of_model(model)
                                                                : avr::version_of_model(model);
   if (any_escapes && !tag) return fail(nullptr, AVR_ERR_INVALID_ARGUMENT, "escapes on a model without the field");
-  if (tag) avr::pb_put_metadata_version(&md, tag);
+  if (crc.on) {
+    const std::string version = tag ? tag : "";
+    avr::pb_put_metadata(&md, tag ? &version : nullptr, fold_file_crc(&items));
+  } else if (tag) {
+    avr::pb_put_metadata_version(&md, tag);
+  }
   size_t total = md.size();
   for (const auto& b : blocks) total += avr::pb_block_size(b);
   if (dst && total > cap) {
@@ -410,26 +429,32 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
 
 extern "C" {
 
+int avr_assemble_container_args(const avr_assemble_args* a, uint8_t** out, size_t* out_len) {
+  if (!a || a->size != sizeof(avr_assemble_args) || !out) return AVR_ERR_INVALID_ARGUMENT;
+  const SeamsArg sa{a->seams, a->seams_len, a->seam_offsets, a->seam_lens};
+  if (a->descs || a->arena)
+    return assemble_parsed(a->file, a->n, a->model, a->descs, a->n_slices, a->arena, a->arena_len, a->status, a->recoded,
+                           a->recoded_len, a->offsets, a->lens, out, out_len, nullptr, 0, sa, a->flags, a->crcs);
+  if (!a->file || !out_len || a->n_slices < 0 || (a->n_slices && (!a->status || !a->offsets || !a->lens)) ||
+      !assemblable(a->model) || (a->seams && a->n_slices && (!a->seam_offsets || !a->seam_lens)))
+    return AVR_ERR_INVALID_ARGUMENT;
+  return guarded(nullptr, [&]() -> int {
+    ParsedFile pf;
+    if (int r = parse_file(nullptr, a->file, a->n, &pf, /*views=*/true)) return r;
+    if ((size_t)a->n_slices != pf.slices.size()) return AVR_ERR_INVALID_ARGUMENT;
+    return assemble(a->file, a->n, a->model, views_of(pf), a->status, a->recoded, a->recoded_len, a->offsets, a->lens, out,
+                    out_len, nullptr, 0, sa, a->flags, a->crcs);
+  });
+}
+
 int avr_assemble_container_opts(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
                                 const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
                                 size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, const uint8_t* seams,
                                 size_t seams_len, const uint64_t* seam_offsets, const uint32_t* seam_lens,
                                 uint32_t flags, uint8_t** out, size_t* out_len) {
-  if (!out) return AVR_ERR_INVALID_ARGUMENT;
-  const SeamsArg sa{seams, seams_len, seam_offsets, seam_lens};
-  if (descs || arena)
-    return assemble_parsed(file, n, model, descs, n_slices, arena, arena_len, status, recoded, recoded_len, offsets, lens,
-                           out, out_len, nullptr, 0, sa, flags);
-  if (!file || !out_len || n_slices < 0 || (n_slices && (!status || !offsets || !lens)) || !assemblable(model) ||
-      (seams && n_slices && (!seam_offsets || !seam_lens)))
-    return AVR_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() -> int {
-    ParsedFile pf;
-    if (int r = parse_file(nullptr, file, n, &pf, /*views=*/true)) return r;
-    if ((size_t)n_slices != pf.slices.size()) return AVR_ERR_INVALID_ARGUMENT;
-    return assemble(file, n, model, views_of(pf), status, recoded, recoded_len, offsets, lens, out, out_len, nullptr, 0,
-                    sa, flags);
-  });
+  const avr_assemble_args a{sizeof(avr_assemble_args), file, n, model, descs, n_slices, arena, arena_len, status, recoded,
+                            recoded_len, offsets, lens, seams, seams_len, seam_offsets, seam_lens, flags, nullptr};
+  return avr_assemble_container_args(&a, out, out_len);
 }
 
 int avr_assemble_container_seams(const uint8_t* file, size_t n, int model, int n_slices, const int32_t* status,
@@ -571,7 +596,8 @@ int avr_container_describe(const uint8_t* in, size_t n, char** json, uint8_t** r
   std::vector<avr::PbBlock> blocks;
   std::string version;
   bool has_md = false;
-  if (!avr::pb_parse(in, n, &blocks, &version, &has_md)) return AVR_ERR_FORMAT;
+  avr::PbFileCrc fc;
+  if (!avr::pb_parse(in, n, &blocks, &version, &has_md, &fc)) return AVR_ERR_FORMAT;
   static const char* hexd = "0123456789abcdef";
   auto hex = [&](const uint8_t* p, size_t k) {
     std::string h;
@@ -581,9 +607,11 @@ int avr_container_describe(const uint8_t* in, size_t n, char** json, uint8_t** r
   };
   std::string j = "{\"version\": ";
   j += has_md ? "\"" + hex((const uint8_t*)version.data(), version.size()) + "\"" : std::string("null");
+  if (fc.present) j += ", \"file_crc\": " + std::to_string(fc.value);
   j += ", \"blocks\": [";
   std::vector<uint8_t> o;
-  if (has_md) avr::pb_put_metadata_version(&o, version);
+  if (fc.present) avr::pb_put_metadata(&o, fc.has_version ? &version : nullptr, fc.value);
+  else if (has_md) avr::pb_put_metadata_version(&o, version);
   for (size_t i = 0; i < blocks.size(); i++) {
     const avr::PbBlock& b = blocks[i];
     std::string e;

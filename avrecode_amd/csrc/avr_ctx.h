@@ -57,6 +57,8 @@ struct avr_ctx : avr_host::ErrSink {
   size_t split_bytes = 0;   // avr_set_split_bytes / AVR_SPLIT_BYTES (0: no split)
   bool split_p32 = false;   // avr_set_split_p32 / AVR_SPLIT_P32: AVR_MODEL_PARALLEL32 reads split_bytes too
   bool recode_escaped = false;   // avr_set_recode_escaped / AVR_RECODE_ESCAPED (Block field 17)
+  bool checksums = false;        // avr_set_checksums / AVR_CHECKSUMS (Metadata field 16: the file's CRC-32)
+  DevBuf crc, sp_crc;            // per-slice CRCs, then their statuses: run_plan's batch, the split job's slices
   // avr_decompress_pieces: the batch's PieceCtl array, host (alive while its upload is in flight) and device
   std::vector<avr::PieceCtl> pc_host;
   DevBuf pc_ctl;
@@ -105,8 +107,15 @@ namespace avr_host {
 // cannot be decompressed.
 // out_host: a std::vector<uint8_t> or a Bytes (not zero-filled first: the download overwrites it)
 // (defined in avr_api.cpp and instantiated there for both)
+// crcs (checked containers): the CRC-32 of every slice's payload (compress) or regenerated bytes
+// (decompress), computed on the device where they lie and read back with the results.
+struct SliceCrcs {
+  std::vector<uint32_t> crc;
+  std::vector<int32_t> status;   // != 0: no value (the slice failed, or its span was refused)
+  bool have(size_t k) const { return k < crc.size() && status[k] == 0; }
+};
 template <class HostBuf>
 int run_plan(avr_ctx* c, int mode, bool sequential, Plan& plan, std::vector<avr_slice_result>* res,
-             HostBuf* out_host, bool verify = false, uint32_t flags = 0);
+             HostBuf* out_host, bool verify = false, uint32_t flags = 0, SliceCrcs* crcs = nullptr);
 
 }  // namespace avr_host

@@ -786,6 +786,14 @@ void pb_put_metadata_version(std::vector<uint8_t>* o, const std::string& version
   bytes_field(o, 1, m.data(), m.size());
 }
 
+void pb_put_metadata(std::vector<uint8_t>* o, const std::string* version, uint32_t file_crc) {
+  std::vector<uint8_t> m;
+  if (version) bytes_field(&m, 1, (const uint8_t*)version->data(), version->size());
+  varint(&m, 16 << 3 | 5);
+  for (int i = 0; i < 4; i++) m.push_back((uint8_t)(file_crc >> (8 * i)));
+  bytes_field(o, 1, m.data(), m.size());
+}
+
 bool pb_read_version(const uint8_t* in, size_t n, std::string* version) {
   version->clear();
   const uint8_t *p = in, *e = in + n;
@@ -814,10 +822,12 @@ bool pb_read_version(const uint8_t* in, size_t n, std::string* version) {
   return true;
 }
 
-bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::string* version, bool* has_metadata) {
+bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::string* version, bool* has_metadata,
+              PbFileCrc* file_crc) {
   blocks->clear();
   version->clear();
   if (has_metadata) *has_metadata = false;
+  PbFileCrc fc;
   const uint8_t *p = in, *e = in + n;
   while (p < e) {
     uint64_t tag, len;
@@ -835,12 +845,19 @@ bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::st
       while (q < qe) {
         uint64_t t2, l2;
         if (!rd_varint(&q, qe, &t2)) return false;
+        if ((t2 >> 3) == 16) {   // the file's CRC: once, a fixed32
+          if ((t2 & 7) != 5 || fc.present || qe - q < 4) return false;
+          fc.present = true;
+          fc.value = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
+          q += 4;
+          continue;
+        }
         if ((t2 & 7) != 2) {
           if (!skip_field(&q, qe, (int)(t2 & 7))) return false;
           continue;
         }
         if (!rd_varint(&q, qe, &l2) || (uint64_t)(qe - q) < l2) return false;
-        if ((t2 >> 3) == 1) version->assign((const char*)q, l2);
+        if ((t2 >> 3) == 1) version->assign((const char*)q, l2), fc.has_version = true;
         q += l2;
       }
       continue;
@@ -869,6 +886,7 @@ bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::st
     }
     blocks->push_back(b);
   }
+  if (file_crc) *file_crc = fc;
   return true;
 }
 

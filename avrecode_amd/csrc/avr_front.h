@@ -134,8 +134,19 @@ struct PbCopy {
 size_t pb_block_size(const PbBlock& b);
 size_t pb_write_block(uint8_t* o, size_t at, const PbBlock& b, std::vector<PbCopy>* copies);
 void pb_put_metadata_version(std::vector<uint8_t>* o, const std::string& version);
+// Recoded.Metadata field 16, this library's own (not in recode.proto): the CRC-32 of the original
+// file, fixed32 -- a checked container (include/avrecode.h, avr_set_checksums).  Purely additive: a
+// reader that does not know it skips it.
+struct PbFileCrc {
+  bool present = false;
+  uint32_t value = 0;
+  bool has_version = false;   // the Metadata held a version field (a reference-model container's holds none)
+};
+// Metadata with the version (null: none, the reference model's) and then the file's CRC
+void pb_put_metadata(std::vector<uint8_t>* o, const std::string* version, uint32_t file_crc);
+// false also for a second Metadata field 16, or one that is not a fixed32
 bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::string* version,
-              bool* has_metadata = nullptr);
+              bool* has_metadata = nullptr, PbFileCrc* file_crc = nullptr);
 // Recoded.Metadata.version only (empty without Metadata); false for bytes that are not a Recoded
 // message at the top level.  No block list is built.
 bool pb_read_version(const uint8_t* in, size_t n, std::string* version);

@@ -434,11 +434,13 @@ int avr_hooks_compress_begin(avr_ctx* c, const uint8_t* file, size_t n, int mode
   uint8_t* avrc = nullptr;
   size_t avrc_len = 0;
   // a session's container never carries Block field 17: the callbacks serve the slices the plain
-  // segmentation codes
-  const int esc = avr_get_recode_escaped(c);
+  // segmentation codes; nor the file's CRC (Metadata field 16)
+  const int esc = avr_get_recode_escaped(c), chk = avr_get_checksums(c);
   avr_set_recode_escaped(c, 0);
+  avr_set_checksums(c, 0);
   const int cr = avr_compress_file(c, file, n, model, &avrc, &avrc_len);
   avr_set_recode_escaped(c, esc);
+  avr_set_checksums(c, chk);
   if (cr) return cr;
   hs->result.assign(avrc, avrc + avrc_len);
   free(avrc);
@@ -796,9 +798,12 @@ int avr_hooks_end(avr_hooks_session* hs, uint8_t** out, size_t* out_len) {
                                     &avrc, &avrc_len);
             }))
           return r;
-      } else if (int r = avr_compress_file(hs->c, hs->original.data(), hs->original.size(), hs->model, &avrc,
-                                           &avrc_len)) {
-        return r;
+      } else {   // as at avr_hooks_compress_begin: a session's container carries no file CRC
+        const int chk = avr_get_checksums(hs->c);
+        avr_set_checksums(hs->c, 0);
+        const int r = avr_compress_file(hs->c, hs->original.data(), hs->original.size(), hs->model, &avrc, &avrc_len);
+        avr_set_checksums(hs->c, chk);
+        if (r) return r;
       }
       hs->result.assign(avrc, avrc + avrc_len);
       free(avrc);
@@ -820,6 +825,9 @@ int avr_hooks_end(avr_hooks_session* hs, uint8_t** out, size_t* out_len) {
             if (b.has_cabac) o.insert(o.end(), hs->regen[i].begin(), hs->regen[i].end());
             i++;
           }
+          // a checked container: the file as the session regenerated it, slice by slice, against its CRC
+          if (hs->job.has_crc && avr_crc32(0, o.data(), o.size()) != hs->job.file_crc)
+            return fail(hs->c, AVR_ERR_CHECKSUM, "the container decoded to a file that is not the file it was made from (CRC-32)");
           hs->result.swap(o);
           return AVR_OK;
         }))

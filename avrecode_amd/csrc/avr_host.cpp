@@ -1,6 +1,7 @@
 // Host helpers shared by the translation units of libavrecode (avr_host.h): errors, the parse of a
 // whole file, descriptors, and the bulk byte work on host threads.  No HIP.
 #include <sys/mman.h>
+#include <zlib.h>
 
 #include <chrono>
 #include <cstdlib>
@@ -115,4 +116,94 @@ void zero_gaps(const std::vector<avr::PbCopy>& jobs, uint8_t* base, uint64_t fro
   memset(base + z, 0, end - z);
 }
 
+// ------------------------------------------------------------------ checked containers
+namespace {
+
+// a b mod P in the reflected representation (bit 31 - k is the coefficient of x^k), as the kernel's
+// crc_mulmod (avr_k_crc.hip)
+uint32_t crc_mulmod(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+  for (int i = 0; i < 32; i++) {
+    p ^= b & (0u - ((a >> (31 - i)) & 1));
+    b = (b >> 1) ^ (0xEDB88320u & (0u - (b & 1)));
+  }
+  return p;
+}
+
+// x^(2^k) mod P, k < 67: x^(8 len) for any 64-bit len is a product of at most 64 of them
+struct CrcPowers {
+  uint32_t p[67];
+  CrcPowers() {
+    p[0] = 0x40000000u;
+    for (int k = 1; k < 67; k++) p[k] = crc_mulmod(p[k - 1], p[k - 1]);
+  }
+};
+
+constexpr size_t kCrcChunk = (size_t)4 << 20;   // a long item's share of one host thread's turn
+
+}  // namespace
+
+uint32_t fold_file_crc(std::vector<CrcItem>* items) {
+  // the bytes nobody has CRC'd yet, in chunks, on host threads when they are many
+  struct Job {
+    size_t item;
+    const uint8_t* p;
+    size_t len;
+    uint32_t crc;
+  };
+  std::vector<Job> jobs;
+  uint64_t bytes = 0;
+  for (size_t i = 0; i < items->size(); i++) {
+    const CrcItem& it = (*items)[i];
+    if (it.known) continue;
+    for (uint64_t at = 0; at < it.len; at += kCrcChunk)
+      jobs.push_back({i, it.p + at, (size_t)std::min<uint64_t>(kCrcChunk, it.len - at), 0});
+    bytes += it.len;
+  }
+  const unsigned T = bytes < ((uint64_t)64 << 20) ? 1u : bulk_threads();
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (size_t k; (k = next.fetch_add(1)) < jobs.size();) jobs[k].crc = avr_crc32(0, jobs[k].p, jobs[k].len);
+  };
+  std::vector<std::thread> th;
+  for (unsigned t = 1; t < T; t++) th.emplace_back(work);
+  work();
+  for (auto& x : th) x.join();
+  for (CrcItem& it : *items)
+    if (!it.known) it.crc = 0;
+  for (const Job& j : jobs) (*items)[j.item].crc = avr_crc32_combine((*items)[j.item].crc, j.crc, j.len);
+  // the last-byte rule on each value, then the blocks in file order
+  const z_crc_t* byte_table = get_crc_table();
+  uint32_t crc = 0;
+  for (CrcItem& it : *items) {
+    uint64_t len = it.len;
+    if (it.rule == LastByte::kAppend) it.crc = avr_crc32(it.crc, &it.last_byte, 1), len++;
+    else if (it.rule == LastByte::kReplace) it.crc ^= (uint32_t)byte_table[it.regen_last ^ it.last_byte];
+    crc = avr_crc32_combine(crc, it.crc, len);
+  }
+  return crc;
+}
+
 }  // namespace avr_host
+
+extern "C" {
+
+uint32_t avr_crc32(uint32_t crc, const uint8_t* p, size_t n) {
+  while (n) {   // zlib takes 32-bit lengths
+    const size_t k = std::min<size_t>(n, (size_t)1 << 30);
+    crc = (uint32_t)crc32(crc, p, (uInt)k);
+    p += k;
+    n -= k;
+  }
+  return crc;
+}
+
+uint32_t avr_crc32_combine(uint32_t a, uint32_t b, uint64_t len_b) {
+  static const avr_host::CrcPowers pw;
+  uint32_t m = 0x80000000u;   // x^(8 len_b)
+  for (int k = 0; len_b; len_b >>= 1, k++)
+    if (len_b & 1) m = avr_host::crc_mulmod(m, pw.p[k + 3]);
+  return avr_host::crc_mulmod(a, m) ^ b;
+}
+
+}  // extern "C"

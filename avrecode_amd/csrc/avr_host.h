@@ -272,6 +272,13 @@ struct SliceView {
   uint64_t file_pos;   // where the payload stands verbatim in the file (the parse knows), or ~0
   size_t nal_lo = 0, nal_hi = 0;   // the slice's own NAL in the file, [lo, hi) (0, 0: not known)
 };
+// A checked container (Recoded.Metadata field 16, the file's CRC-32): write the field, with the
+// payload CRC of slice i from crcs[i] where the caller brings them (a device computed them; read for
+// coded blocks only, and trusted) or from the payloads on host threads.
+struct FileCrcArg {
+  bool on = false;
+  const uint32_t* crcs = nullptr;
+};
 bool recodable_candidate(const avr::SliceInfo& s);
 std::vector<SliceView> views_of(const ParsedFile& pf);
 // escapes (the parallel models' opt-in second chance, AVR_ASSEMBLE_ESCAPED): a slice the search
@@ -286,7 +293,7 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
                    const std::vector<std::pair<const uint8_t*, size_t>>& recoded, int model, uint8_t** out,
                    size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0,
                    const std::vector<std::pair<const uint8_t*, size_t>>* seams = nullptr,
-                   const std::vector<uint32_t>* escapes = nullptr);
+                   const std::vector<uint32_t>* escapes = nullptr, const FileCrcArg& crc = FileCrcArg());
 
 // ------------------------------------------------------------------ avr_seams.cpp: the seams codec
 struct SeamCe {
@@ -368,6 +375,8 @@ struct DecJob {
   int model = AVR_MODEL_REFERENCE;   // from Recoded.Metadata.version
   std::vector<int> desc_of_block;    // plan index per coded block (-1: none; <= -2: split block -2 - k)
   std::vector<SplitBlock> splits;
+  bool has_crc = false;              // Recoded.Metadata field 16: the file's CRC-32 (a checked container)
+  uint32_t file_crc = 0;
 };
 
 // sp: where the pieces of split blocks go (nullptr: such a container is refused -- the sharded and
@@ -391,18 +400,58 @@ void patch_last_byte(const avr::PbBlock& b, size_t len, V* v) {
   else if (r == LastByte::kReplace) v->back() = (uint8_t)b.last_byte[0];
 }
 
+// ------------------------------------------------------------------ avr_host.cpp: checked containers
+// The file's CRC-32 (Recoded.Metadata field 16; avr_crc32 / avr_crc32_combine, include/avrecode.h)
+// folded from its blocks in file order -- stated once, for the writer (emit_container) and every
+// splice.  An item is what one block contributes to the file: len bytes whose CRC the caller brings
+// (known: a device computed it over a slice's payload or regenerated bytes) or that stand at p and
+// are CRC'd here on host threads, a long one cut into chunks (literals: parameter sets, headers,
+// uncoded slices; an escaped block's bytes; every slice of a caller without device values).  rule:
+// the last-byte rule then applied to the CRC of a regenerated slice instead of to its bytes --
+// kAppend one more byte, kReplace the byte table's entry for the difference of the two last bytes
+// (two messages of one length that differ in the last byte differ by the raw CRC of that
+// difference), kKeep nothing.
+struct CrcItem {
+  const uint8_t* p = nullptr;
+  uint64_t len = 0;
+  uint32_t crc = 0;
+  bool known = false;
+  LastByte rule = LastByte::kKeep;
+  uint8_t last_byte = 0, regen_last = 0;   // the block's last_byte; kReplace: the regenerated last byte
+};
+uint32_t fold_file_crc(std::vector<CrcItem>* items);
+// a coded block's item: its len regenerated bytes at p (read for kReplace's one byte, and for the CRC
+// unless the caller brings it)
+inline CrcItem crc_item_of_slice(const avr::PbBlock& b, const uint8_t* p, size_t len, const uint32_t* crc) {
+  CrcItem it;
+  it.p = p;
+  it.len = len;
+  it.known = crc != nullptr;
+  if (crc) it.crc = *crc;
+  it.rule = last_byte_rule(b, len);
+  if (it.rule != LastByte::kKeep) it.last_byte = (uint8_t)b.last_byte[0];
+  if (it.rule == LastByte::kReplace) it.regen_last = p[len - 1];
+  return it;
+}
+
 // decompressor::run's output (recode.cpp:1338-1357): the literals and the regenerated slices in
 // block order, each slice patched by the last-byte rule, then -- a block with field 17 -- escaped:
 // the patch decides the slice's last byte and length, and both can change what is inserted before
 // that byte.
 // slice(route, &p, &len) gives a coded block's regenerated bytes and returns its status.
-template <class Slice>
-int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>* o) {
+// A checked container (j.has_crc) is checked here: crc_of(route, &crc) gives the CRC of those len
+// bytes where a device computed it (false: from the bytes, on host threads), and a file whose fold
+// is not the container's value is AVR_ERR_CHECKSUM.
+template <class Slice, class Crc>
+int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>* o, Crc&& crc_of) {
   o->reserve(j.stream.size());
+  std::vector<CrcItem> items;
+  if (j.has_crc) items.reserve(j.blocks.size());
   for (size_t i = 0; i < j.blocks.size(); i++) {
     const avr::PbBlock& b = j.blocks[i];
     if (b.has_literal) {
       o->insert(o->end(), b.literal, b.literal + b.literal_len);
+      if (j.has_crc) items.push_back(CrcItem{b.literal, b.literal_len});
       continue;
     }
     if (!b.has_cabac) continue;
@@ -421,8 +470,15 @@ int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>*
         return fail(c, AVR_ERR_FORMAT, "slice " + std::to_string(k) + ": escape count differs from the block's");
       o->resize(o0);
       o->insert(o->end(), e.begin(), e.end());
+      if (j.has_crc) items.push_back(CrcItem{nullptr, e.size(), avr_crc32(0, e.data(), e.size()), true});
+    } else if (j.has_crc) {
+      uint32_t crc = 0;
+      const bool have = crc_of(route_of_block(k), &crc);
+      items.push_back(crc_item_of_slice(b, p, len, have ? &crc : nullptr));
     }
   }
+  if (j.has_crc && fold_file_crc(&items) != j.file_crc)
+    return fail(c, AVR_ERR_CHECKSUM, "the container decoded to a file that is not the file it was made from (CRC-32)");
   return AVR_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "avr_kernels.h"
+#include "avr_load16.h"   // window32, load16_shifted
 
 namespace avr {
 
@@ -55,11 +56,6 @@ __global__ __launch_bounds__(1024) void scan_kept_kernel(const avr_piece* pieces
     run += kept[i];
   }
   if (t == nt - 1) offsets[n] = part[nt - 1];
-}
-
-// bytes [8 bs, 8 bs + 32) of the 64-bit window hi:lo (bs < 4)
-__device__ __forceinline__ uint32_t window32(uint32_t lo, uint32_t hi, uint32_t bs) {
-  return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * bs));
 }
 
 // One workgroup per unit.  The source (a unit's output in the work buffer) is 16-byte aligned, the
@@ -119,26 +115,6 @@ __global__ __launch_bounds__(256) void pack_pieces_kernel(const avr_slice_desc* 
 // slice's pieces one after the other in the work buffer, at any alignment; to check them on the
 // device they are staged into the layout the pieces' decompress reads, regenerated, packed
 // (pack_pieces_kernel above) and compared with the payload.  No reference counterpart.
-
-// 16 bytes from byte offset 16 j + a (a < 16) of the 16-byte aligned blocks s4: blocks j and, when the
-// bytes reach into it (a != 0 and `next`), j + 1 -- the caller clears `next` where block j + 1 lies
-// past the block of the last byte it may read (the bytes from there then read as zero).
-__device__ __forceinline__ uint4 load16_shifted(const uint4* s4, uint32_t j, uint32_t a, bool next) {
-  const uint4 x = s4[j];
-  if (!a) return x;
-  const uint4 y = next ? s4[j + 1] : make_uint4(0, 0, 0, 0);
-  const uint32_t bs = a & 3;
-  switch (a >> 2) {
-    case 0:
-      return make_uint4(window32(x.x, x.y, bs), window32(x.y, x.z, bs), window32(x.z, x.w, bs), window32(x.w, y.x, bs));
-    case 1:
-      return make_uint4(window32(x.y, x.z, bs), window32(x.z, x.w, bs), window32(x.w, y.x, bs), window32(y.x, y.y, bs));
-    case 2:
-      return make_uint4(window32(x.z, x.w, bs), window32(x.w, y.x, bs), window32(y.x, y.y, bs), window32(y.y, y.z, bs));
-    default:
-      return make_uint4(window32(x.w, y.x, bs), window32(y.x, y.y, bs), window32(y.y, y.z, bs), window32(y.z, y.w, bs));
-  }
-}
 
 // a unit's room in the staging arena: its stream, at least 16 zero bytes, rounded up to 16
 __device__ __forceinline__ uint64_t staged_room(uint32_t len) { return ((uint64_t)len + 16 + 15) & ~15ull; }

@@ -177,5 +177,14 @@ hipError_t launch_stage_pieces(avr_slice_desc* descs, const uint64_t* src, int n
 hipError_t launch_verify_units(const avr_slice_desc* descs, const avr_slice_result* rc, int n, const uint32_t* first,
                                int n_units, const uint8_t* in, const uint8_t* packed, const uint64_t* offsets, const uint32_t* kept,
                                const int32_t* ustatus, int32_t* verdict, hipStream_t stream);
+// avr_crc_spans (avr_k_crc.hip): crc[k] = the CRC-32 (zlib's) of buf[off[k], off[k] + len[k]), one
+// workgroup per span, any alignment; status[k] = 0, or AVR_SLICE_OVERFLOW (crc 0, nothing read) for a
+// span that does not lie inside buf_len
+hipError_t launch_crc_spans(const uint8_t* buf, uint64_t buf_len, const uint64_t* off, const uint32_t* len, int n,
+                            uint32_t* crc, int32_t* status, hipStream_t stream);
+// the same over a slice batch's own spans: its payloads (payload_offset, payload_size), or with regen
+// what its decompress left (out_offset, res.out_len; a failed slice: its status, crc 0)
+hipError_t launch_crc_slices(const avr_slice_desc* descs, const avr_slice_result* res, int n, bool regen,
+                             const uint8_t* buf, uint64_t buf_len, uint32_t* crc, int32_t* status, hipStream_t stream);
 
 }  // namespace avr

@@ -16,7 +16,10 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
   const bool tm = getenv("AVR_ASM_TIMING") != nullptr;
   double t0 = now_s();
   std::string version;
-  if (!avr::pb_parse(in, n, &j->blocks, &version)) return fail(c, AVR_ERR_FORMAT, "not a Recoded protobuf");
+  avr::PbFileCrc fc;
+  if (!avr::pb_parse(in, n, &j->blocks, &version, nullptr, &fc)) return fail(c, AVR_ERR_FORMAT, "not a Recoded protobuf");
+  j->has_crc = fc.present;
+  j->file_crc = fc.value;
   j->model = avr::model_of_version(version);
   // another avrecode-amd container format (the round-2 "avrecode-amd:P", ...) would be read as a
   // reference-model container and fail late: refuse it here
@@ -220,10 +223,13 @@ namespace {
 // (position, byte) and the total length.  An escaped block (field 17) is one more copy job: its
 // bytes -- regenerated, patched, then escaped -- stand in `side`, which the layout's caller keeps
 // until the copies are done.
+// A checked container (job.has_crc) is checked here, before anything is written: the fold of the
+// blocks' CRCs (fold_file_crc) -- the slices' from crcs, or without them from regen on host threads --
+// against the container's value, AVR_ERR_CHECKSUM when they differ.
 int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* regen, size_t regen_len,
                   const uint64_t* offsets, const uint32_t* lens, std::vector<avr::PbCopy>* copies,
                   std::vector<std::pair<size_t, uint8_t>>* patches, std::vector<std::vector<uint8_t>>* side,
-                  size_t* total) {
+                  size_t* total, const uint32_t* crcs = nullptr) {
   const DecJob& j = h->job;
   const int ns = (int)h->plan.descs.size();
   // every slice's regenerated bytes inside regen and within its own output capacity
@@ -232,11 +238,14 @@ int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* r
                            lens[k] > h->plan.descs[k].out_capacity))
       return AVR_ERR_INVALID_ARGUMENT;
   copies->reserve(j.blocks.size());
+  std::vector<CrcItem> items;
+  if (j.has_crc) items.reserve(j.blocks.size());
   size_t at = 0;
   for (size_t i = 0; i < j.blocks.size(); i++) {
     const avr::PbBlock& b = j.blocks[i];
     if (b.has_literal) {
       if (b.literal_len) copies->push_back({at, b.literal, b.literal_len});
+      if (j.has_crc) items.push_back(CrcItem{b.literal, b.literal_len});
       at += b.literal_len;
       continue;
     }
@@ -252,16 +261,19 @@ int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* r
       if (e.size() - p.size() != b.escapes) return AVR_ERR_FORMAT;   // not the count the block recorded
       side->push_back(std::move(e));
       copies->push_back({at, side->back().data(), side->back().size()});
+      if (j.has_crc) items.push_back(CrcItem{side->back().data(), side->back().size()});
       at += side->back().size();
       continue;
     }
     if (len) copies->push_back({at, regen + offsets[k], len});
+    if (j.has_crc) items.push_back(crc_item_of_slice(b, regen + offsets[k], len, crcs ? &crcs[k] : nullptr));
     const LastByte rule = last_byte_rule(b, len);
     const size_t m = len + (rule == LastByte::kAppend);
     if (rule != LastByte::kKeep) patches->push_back({at + m - 1, (uint8_t)b.last_byte[0]});
     at += m;
   }
   *total = at;
+  if (j.has_crc && fold_file_crc(&items) != j.file_crc) return AVR_ERR_CHECKSUM;
   return AVR_OK;
 }
 
@@ -430,6 +442,12 @@ int avr_dec_plan_arena(const avr_dec_plan* h, uint8_t* out, size_t cap) {
 
 int avr_dec_plan_splice(const avr_dec_plan* h, const int32_t* status, const uint8_t* regen, size_t regen_len,
                         const uint64_t* offsets, const uint32_t* lens, uint8_t* out, size_t out_cap, size_t* out_len) {
+  return avr_dec_plan_splice_crc(h, status, regen, regen_len, offsets, lens, nullptr, out, out_cap, out_len);
+}
+
+int avr_dec_plan_splice_crc(const avr_dec_plan* h, const int32_t* status, const uint8_t* regen, size_t regen_len,
+                            const uint64_t* offsets, const uint32_t* lens, const uint32_t* crcs, uint8_t* out,
+                            size_t out_cap, size_t* out_len) {
   const int ns = h ? (int)h->plan.descs.size() : 0;
   if (!h || !h->avrc || !out_len || (ns && (!status || !regen || !offsets || !lens))) return AVR_ERR_INVALID_ARGUMENT;
   *out_len = 0;
@@ -438,7 +456,7 @@ int avr_dec_plan_splice(const avr_dec_plan* h, const int32_t* status, const uint
     std::vector<std::pair<size_t, uint8_t>> patches;
     std::vector<std::vector<uint8_t>> side;
     size_t total = 0;
-    if (int r = splice_layout(h, status, regen, regen_len, offsets, lens, &copies, &patches, &side, &total)) return r;
+    if (int r = splice_layout(h, status, regen, regen_len, offsets, lens, &copies, &patches, &side, &total, crcs)) return r;
     *out_len = total;
     if (total > out_cap || (total && !out)) return AVR_ERR_INVALID_ARGUMENT;
     write_splice(copies, patches, out);

@@ -1,4 +1,4 @@
-// recode CLI (recode.cpp:1627-1659): recode [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] <input> [output]
+// recode CLI (recode.cpp:1627-1659): recode [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] <input> [output]
 //   -p    parallel model (fresh model per slice; slices independent) on the reference's
 //         arithmetic_code<uint64_t, uint8_t>; default = reference model.
 //   -p32  parallel model on the optional 32-bit P32 coder (avrecode-amd:P32 containers).
@@ -7,6 +7,8 @@
 //         bytes are re-coded too (avr_set_recode_escaped; avrecode-amd:P64E / P32E containers).
 //   -s    with -p32, compress and roundtrip: long slices are split as -p splits them
 //         (avr_set_split_p32; avrecode-amd:P32S / P32SE containers).
+//   -k    compress and roundtrip, any model: a checked container -- the file's CRC-32 in its Metadata
+//         (avr_set_checksums); decompress checks the field wherever it finds it.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,18 +43,19 @@ static void print_bill(const char* title, const uint64_t* b) {
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::cerr << "Usage: " << argv[0] << " [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] <input> [output]" << std::endl;
+    std::cerr << "Usage: " << argv[0] << " [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] <input> [output]" << std::endl;
     return 1;
   }
   std::string cmd = argv[1];
   int a = 2, model = AVR_MODEL_REFERENCE;
-  bool escaped = false, split32 = false;
-  for (; a < argc; a++) {   // the model, -e and -s, in any order
+  bool escaped = false, split32 = false, checks = false;
+  for (; a < argc; a++) {   // the model, -e, -s and -k, in any order
     if (!strcmp(argv[a], "-p")) model = AVR_MODEL_PARALLEL;
     else if (!strcmp(argv[a], "-p32")) model = AVR_MODEL_PARALLEL32;
     else if (!strcmp(argv[a], "-c")) model = AVR_MODEL_CHAINED;
     else if (!strcmp(argv[a], "-e")) escaped = true;
     else if (!strcmp(argv[a], "-s")) split32 = true;
+    else if (!strcmp(argv[a], "-k")) checks = true;
     else break;
   }
   if (escaped && ((model != AVR_MODEL_PARALLEL && model != AVR_MODEL_PARALLEL32) || cmd == "decompress")) {
@@ -78,6 +81,7 @@ int main(int argc, char** argv) {
   }
   if (escaped) avr_set_recode_escaped(ctx, 1);
   if (split32) avr_set_split_p32(ctx, 1);
+  if (checks) avr_set_checksums(ctx, 1);
   uint8_t* out = nullptr;
   size_t out_len = 0;
   int r;

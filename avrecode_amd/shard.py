@@ -42,7 +42,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import (MODEL_CHAINED, MODEL_PARALLEL, MODEL_PARALLEL32, PIECE, SLICE_NO_END, DecompressPlan, ParsedStream, assemble_container,
-               container_model, parse_stream, plan_decompress, seams_of_container, splice_container)
+               container_model, crc32, crc32_combine, file_crc_of_container, parse_stream, plan_decompress,
+               seams_of_container, splice_container)
 
 
 def partition(sizes, world: int) -> list[tuple[int, int]]:
@@ -257,8 +258,53 @@ def collapse_units(pieces, status, offsets, lens):
     return st.astype(np.int32), off.astype(np.uint64), ln.astype(np.uint32)
 
 
+def collapse_unit_crcs(pieces, crcs, lens):
+    """collapse_units for the units' CRCs (batch.UnitBatch.crcs over the packed outputs, gathered in
+    unit order): per slice the CRC-32 of its units' kept bytes one after the other, uint32 --
+    DecompressPlan.splice's crcs.  A whole slice's is its unit's; a cut slice's is folded from its
+    pieces' with crc32_combine (a CRC is linear: no byte is read again)."""
+    pieces = np.asarray(pieces, dtype=PIECE)
+    crcs = np.asarray(crcs).astype(np.uint32)
+    lens = np.asarray(lens, dtype=np.int64)
+    n = len(pieces)
+    if not (len(crcs) == len(lens) == n):
+        raise ValueError("collapse_unit_crcs: one crc / length per unit")
+    if n == 0:
+        return np.zeros(0, np.uint32)
+    sl = pieces["slice"]
+    first = np.flatnonzero(np.concatenate([[True], sl[1:] != sl[:-1]]))
+    count = np.diff(np.concatenate([first, [n]]))
+    out = crcs[first].copy()
+    for s in np.flatnonzero(count > 1):
+        c = int(out[s])
+        for u in range(int(first[s]) + 1, int(first[s] + count[s])):
+            c = crc32_combine(c, int(crcs[u]), int(lens[u]))
+        out[s] = c
+    return out
+
+
+def _host_crcs(part: ParsedStream) -> np.ndarray:
+    """The payload CRCs of a batch on the host (a device step that brought none)."""
+    return np.array([crc32(part.arena[int(d["payload_offset"]):int(d["payload_offset"]) + int(d["payload_size"])])
+                     for d in part.descs], dtype=np.uint32)
+
+
+def _gather_u32(values, status, dev):
+    """One uint32 per slice (unit) through gather_flat, as 4-byte items: rank 0 gets them in rank order."""
+    import torch
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    n = len(v)
+    flat = torch.from_numpy(np.concatenate([v.view(np.uint8), np.zeros(16, np.uint8)]))
+    g = gather_flat(flat.to(dev) if dev.type == "cuda" else flat, np.asarray(status, np.int64)[:n] * 0,
+                    4 * np.arange(n, dtype=np.int64), np.full(n, 4, np.int64), dst=0, device=dev)
+    if g is None:
+        return None
+    _, blob, offs, _ = g
+    return np.ascontiguousarray(blob[:4 * len(offs)]).view(np.uint32).copy()
+
+
 def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL, split_bytes: int = 0,
-                   split_p32: bool = False):
+                   split_p32: bool = False, checksums: bool = False):
     """This rank's slice range of a sharded compress on its GPU: (flat uint8 tensor, status, offsets,
     lens, seams) with slice k's re-coded bytes at flat[offsets[k] : offsets[k] + lens[k]] and status 0
     where it is to be coded (-1: stored skip_coded).  split_bytes 0 (or a model other than
@@ -267,7 +313,9 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
     split candidates (split_plan at split_bytes, coded slices only) go through batch.SplitBatch on a
     side stream beside the DeviceBatch of the rest; the two are joined before the packs; seams is one
     bytes per slice (b"" without a cut).  A candidate whose walk, cut check or verify fails is
-    stored skip_coded, as the whole-file compress stores it: no unsplit retry."""
+    stored skip_coded, as the whole-file compress stores it: no unsplit retry.
+    checksums: a sixth value, the CRC-32 of every slice's payload (uint32), computed over the batches'
+    input arenas on the device (DeviceBatch.crcs / SplitBatch.crcs) for a checked container."""
     import torch
 
     from . import split_plan
@@ -283,13 +331,15 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
         b = DeviceBatch(ctx, part, device=dev)
         b.roundtrip(model)
         flat, d_off = b.pack()
+        d_crc = b.crcs("in")[0] if checksums else None
         torch.cuda.synchronize()
         v = b.verdicts()
         res = b.results("c")
         offs = d_off.cpu().numpy()[:n].astype(np.int64)
         lens = np.where(res["status"] == 0, res["out_len"], 0).astype(np.int64)
         status = np.where(v == 1, 0, -1).astype(np.int64)
-        return flat, status, offs, lens, ([b""] * n if split_bytes else None)
+        out = (flat, status, offs, lens, ([b""] * n if split_bytes else None))
+        return out + (d_crc.cpu().numpy()[:n].view(np.uint32).copy(),) if checksums else out
     idx_c, idx_r = np.flatnonzero(cand), np.flatnonzero(~cand)
     cur = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(dev)
@@ -310,7 +360,15 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
     flat_c, off_c = sb.pack_recoded()
     if b is not None:
         flat_r, off_r = b.pack()
+    crcs = np.zeros(n, np.uint32)
+    if checksums:
+        crc_c = sb.crcs()[0]
+        crc_r = b.crcs("in")[0] if b is not None else None
     torch.cuda.synchronize()
+    if checksums:
+        crcs[idx_c] = crc_c.cpu().numpy()[:len(idx_c)].view(np.uint32)
+        if b is not None:
+            crcs[idx_r] = crc_r.cpu().numpy()[:len(idx_r)].view(np.uint32)
     status = np.full(n, -1, np.int64)
     offs, lens = np.zeros(n, np.int64), np.zeros(n, np.int64)
     seams = [b""] * n
@@ -331,12 +389,12 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
         lens[idx_r] = np.where(res["status"] == 0, res["out_len"], 0)
         total_r = int(off_r.cpu().numpy()[len(idx_r)])
         flat = torch.cat([flat_c[:total_c], flat_r[:max(16, total_r)]])
-    return flat, status, offs, lens, seams
+    return (flat, status, offs, lens, seams, crcs) if checksums else (flat, status, offs, lens, seams)
 
 
 def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = None,
                      model: int = MODEL_PARALLEL, split_bytes: int | None = None, run_range=None,
-                     escaped: bool = False, split_p32: bool = False) -> bytes | None:
+                     escaped: bool = False, split_p32: bool = False, checksums: bool = False) -> bytes | None:
     """PARALLEL-model compress of one file across all ranks; the container is returned on rank 0.
 
     Every rank parses the file (host), takes its contiguous slice range (partition), runs it on its
@@ -360,6 +418,12 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     Context.recode_escaped (avr_assemble_container_opts, ASSEMBLE_ESCAPED) -- the ranks' work does not
     change, since every candidate slice is compressed and checked anyway -- and the container is
     byte-identical to ctx.compress(data, model) with that option on.
+    checksums (pass ctx.checksums): a checked container.  Each rank computes its slices' payload
+    CRCs on its device, over the arenas its batches uploaded (compress_range's sixth value), and one
+    more gather_flat of 4-byte items brings them to rank 0, whose assembly folds them with the
+    literals' into the file's CRC (avr_assemble_container_args, ASSEMBLE_CRC): byte-identical to
+    ctx.compress(data, model) with ctx.checksums on.  A device step that returns no sixth value has
+    them computed from the payloads on the host.
     run_range(part) -> compress_range's tuple replaces the device step (CPU tests)."""
     import torch
     import torch.distributed as dist
@@ -371,9 +435,12 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     lo, hi = partition(ps.descs["payload_size"], world)[rank]
     part = subset(ps, lo, hi)
     dev = _gather_device(ctx, device)
-    seams = None
+    seams = crcs = None
     if hi > lo:
-        flat, status, offs, lens, seams = (run_range or (lambda p: compress_range(ctx, p, None, model, split, split_p32=split32)))(part)
+        out = (run_range or (lambda p: compress_range(ctx, p, None, model, split, split_p32=split32,
+                                                      checksums=checksums)))(part)
+        flat, status, offs, lens, seams = out[:5]
+        crcs = out[5] if len(out) > 5 else None
     else:
         flat = torch.zeros(16, dtype=torch.uint8, device=dev)
         offs = lens = status = np.zeros(0, np.int64)
@@ -387,14 +454,18 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
         sflat = torch.from_numpy(np.frombuffer(b"".join(fields) + b"\0" * 16, dtype=np.uint8).copy())
         gs = gather_flat(sflat.to(dev) if dev.type == "cuda" else sflat, np.asarray(status, np.int64), so, sl, dst=0,
                          device=dev)
+    gc = None
+    if checksums:
+        gc = _gather_u32(crcs if crcs is not None else _host_crcs(part), status, dev)
     if g is None:
         return None
     st, blob, offs, lens = g
     if gs is not None:
         _, sblob, soffs, slens = gs
         return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, seams=(sblob, soffs, slens),
-                                  escaped=escaped, split32=split32)
-    return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, escaped=escaped)
+                                  escaped=escaped, split32=split32, checksums=checksums, crcs=gc)
+    return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, escaped=escaped, checksums=checksums,
+                              crcs=gc)
 
 
 def _gather_device(ctx, device):
@@ -406,10 +477,12 @@ def _gather_device(ctx, device):
     return torch.device("cpu")
 
 
-def decompress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL):
+def decompress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL, crcs: bool = False):
     """This rank's slice range of a sharded decompress on its GPU: (flat uint8 tensor, status,
     offsets, lens) with slice k's regenerated bytes at flat[offsets[k] : offsets[k] + lens[k]]
-    (packed on the device, avr_pack_outputs).  model: the container's (container_model)."""
+    (packed on the device, avr_pack_outputs).  model: the container's (container_model).
+    crcs (a checked container): a fifth value, the CRC-32 of each slice's packed bytes (uint32),
+    computed on the device (DeviceBatch.crcs over the packed outputs)."""
     import torch
 
     from .batch import DeviceBatch
@@ -417,22 +490,25 @@ def decompress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PA
     b = DeviceBatch(ctx, part, device=device)
     b.decompress(model)
     flat, d_off = b.pack(which="d")
+    d_crc = b.crcs("packed")[0] if crcs else None
     torch.cuda.synchronize()
     res = b.results("d")
     n = len(part.descs)
     offs = d_off.cpu().numpy()[:n].astype(np.int64)
     status = res["status"].astype(np.int64)
     lens = np.where(status == 0, res["out_len"], 0).astype(np.int64)
-    return flat, status, offs, lens
+    out = (flat, status, offs, lens)
+    return out + (d_crc.cpu().numpy()[:n].view(np.uint32).copy(),) if crcs else out
 
 
-def decompress_units_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL):
+def decompress_units_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARALLEL, crcs: bool = False):
     """This rank's unit range of a sharded decompress of a split container on its GPU
     (batch.UnitBatch): (flat uint8 tensor, status, offsets, lens) per unit, unit k's kept bytes at
     flat[offsets[k] : offsets[k] + lens[k]].  The pieces go through avr_decompress_pieces_m on the
     container's coder (model: MODEL_PARALLEL, or MODEL_PARALLEL32 for a P32S container), the whole
     slices through avr_decompress_slices, one launch after the other on the current stream, and one
-    avr_pack_pieces packs all units in unit order, each piece cut down to its share of its slice."""
+    avr_pack_pieces packs all units in unit order, each piece cut down to its share of its slice.
+    crcs (a checked container): a fifth value, the CRC-32 of each unit's kept bytes (UnitBatch.crcs)."""
     import torch
 
     from .batch import UnitBatch
@@ -440,11 +516,13 @@ def decompress_units_range(ctx, part: ParsedStream, device=None, model: int = MO
     b = UnitBatch(ctx, part, device=device)
     b.decompress(model)
     flat, d_off, d_kept, d_status = b.pack()
+    d_crc = b.crcs(flat, d_off, d_kept)[0] if crcs else None
     torch.cuda.synchronize()
     n = len(part.descs)
     offs = d_off.cpu().numpy()[:n].astype(np.int64)
     lens = d_kept.cpu().numpy()[:n].view(np.uint32).astype(np.int64)
-    return flat, d_status.cpu().numpy()[:n].astype(np.int64), offs, lens
+    out = (flat, d_status.cpu().numpy()[:n].astype(np.int64), offs, lens)
+    return out + (d_crc.cpu().numpy()[:n].view(np.uint32).copy(),) if crcs else out
 
 
 def _sharded_decompress_units(ctx, avrc, device, run_range):
@@ -459,17 +537,36 @@ def _sharded_decompress_units(ctx, avrc, device, run_range):
     lo, hi = partition(pu.descs["payload_size"], world)[rank]
     part = subset_units(pu, lo, hi)
     dev = _gather_device(ctx, device)
+    checked = file_crc_of_container(avrc) is not None
+    crcs = None
     if hi > lo:
-        flat, status, offs, lens = (run_range or (lambda p: decompress_units_range(ctx, p, device, model)))(part)
+        out = (run_range or (lambda p: decompress_units_range(ctx, p, device, model, crcs=checked)))(part)
+        flat, status, offs, lens = out[:4]
+        crcs = out[4] if len(out) > 4 else None
     else:
         flat = torch.zeros(16, dtype=torch.uint8, device=dev)
         offs = lens = status = np.zeros(0, np.int64)
     g = gather_flat(flat, status, offs, lens, dst=0, device=dev)
+    gc = _gather_regen_crcs(checked, crcs, flat, status, offs, lens, dev)
     if g is None:
         return None
     st, blob, offs, lens = g
+    if gc is not None:
+        gc = collapse_unit_crcs(plan.pieces, gc, lens)
     st, offs, lens = collapse_units(plan.pieces, st, offs, lens)
-    return plan.splice(st, blob, offs, lens).tobytes()
+    return plan.splice(st, blob, offs, lens, crcs=gc).tobytes()
+
+
+def _gather_regen_crcs(checked, crcs, flat, status, offs, lens, dev):
+    """A checked container's per-slice (per-unit) CRCs gathered to rank 0, one more gather_flat of
+    4-byte items; None for a container without the field.  A device step that brought no values has
+    them computed from its packed bytes on the host."""
+    if not checked:
+        return None
+    if crcs is None:
+        h = flat.cpu().numpy()
+        crcs = np.array([crc32(h[int(o):int(o) + int(n)]) for o, n in zip(offs, lens)], dtype=np.uint32)
+    return _gather_u32(crcs, status, dev)
 
 
 def sharded_decompress(ctx, avrc: bytes, device=None, run_range=None) -> bytes | None:
@@ -486,7 +583,11 @@ def sharded_decompress(ctx, avrc: bytes, device=None, run_range=None) -> bytes |
     decompress_units_range (run_range then gets the unit batch of subset_units and returns per-unit
     outputs), and on rank 0 collapse_units before DecompressPlan.splice.
     A block that stands for escaped bytes (Block field 17, Context.recode_escaped) changes neither
-    route: descriptors and units are in the unescaped domain, and rank 0's splice escapes."""
+    route: descriptors and units are in the unescaped domain, and rank 0's splice escapes.
+    A checked container (Context.checksums, Metadata field 16) is checked on rank 0 (AvrError
+    ERR_CHECKSUM): each rank computes the CRC-32 of its slices' (units') regenerated bytes on its
+    device, over the packed outputs, one more gather_flat brings the values, and rank 0 folds them
+    (collapse_unit_crcs for the pieces of a cut slice, then the splice's fold with the literals)."""
     import torch
     import torch.distributed as dist
 
@@ -498,15 +599,22 @@ def sharded_decompress(ctx, avrc: bytes, device=None, run_range=None) -> bytes |
     lo, hi = partition(plan.descs["payload_size"], world)[rank]
     part = subset(plan, lo, hi)
     dev = _gather_device(ctx, device)
+    checked = file_crc_of_container(avrc) is not None
+    crcs = None
     if hi > lo:
-        flat, status, offs, lens = (run_range or (lambda p: decompress_range(ctx, p, device, model)))(part)
+        out = (run_range or (lambda p: decompress_range(ctx, p, device, model, crcs=checked)))(part)
+        flat, status, offs, lens = out[:4]
+        crcs = out[4] if len(out) > 4 else None
     else:
         flat = torch.zeros(16, dtype=torch.uint8, device=dev)
         offs = lens = status = np.zeros(0, np.int64)
     g = gather_flat(flat, status, offs, lens, dst=0, device=dev)
+    gc = _gather_regen_crcs(checked, crcs, flat, status, offs, lens, dev)
     if g is None:
         return None
     st, blob, offs, lens = g
+    if gc is not None:   # the device's values: the splice reads no slice's bytes for the check
+        return DecompressPlan().load(avrc).splice(st, blob, offs, lens, crcs=gc).tobytes()
     return splice_container(avrc, st, blob, offs, lens)
 
 

@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define AVRECODE_ABI_VERSION 10 /* 10: the long-slice split on the P32 coder, opt-in (avr_set_split_p32, the "P32S" / "P32SE"
+#define AVRECODE_ABI_VERSION 11 /* 11: checked containers, opt-in (avr_set_checksums, Metadata field 16, AVR_ERR_CHECKSUM,
+                                 *    avr_crc_spans, avr_crc32(_combine), avr_assemble_container_args, avr_dec_plan_splice_crc);
+                                 * 10: the long-slice split on the P32 coder, opt-in (avr_set_split_p32, the "P32S" / "P32SE"
                                  *    tags, avr_compress_split_slices_m, avr_decompress_pieces_m, AVR_ASSEMBLE_SPLIT32);
                                  * 9: escaped slices re-coded (avr_set_recode_escaped, Block field 17, the "E" tags,
                                  *    avr_assemble_container_opts, avr_escape_payload);
@@ -50,6 +52,7 @@ typedef enum {
   AVR_ERR_OUT_OF_MEMORY = -4,
   AVR_ERR_ROUNDTRIP = -5,       /* decompress(compress(x)) != x */
   AVR_ERR_UNSUPPORTED = -6,
+  AVR_ERR_CHECKSUM = -7,        /* the container decoded, and the file it gives is not the file it was made from */
 } avr_status;
 
 /* Model modes.  REFERENCE = recode.cpp's h264_model exactly (estimators persist across slices,
@@ -148,6 +151,42 @@ int avr_get_recode_escaped(const avr_ctx* ctx);
  * n + n / 2); written to dst when it fits cap, else AVR_ERR_INVALID_ARGUMENT with *len still set
  * (dst may be NULL with cap 0 to ask for the length).  Host only. */
 int avr_escape_payload(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* len);
+
+/* Checked containers: the file's CRC-32 in the container, an option, off by default (with it off every
+ * container is byte for byte what it was).  recode.proto has no check of what a container restores,
+ * and the splice keeps the reference's rule -- the regenerated length is never compared with `size` --
+ * so a damaged Block.cabac can decompress with status 0 to a wrong file.  With the option on,
+ * avr_compress_file(s) and avr_roundtrip_file(s) of every model write Recoded.Metadata field 16, wire
+ * type 5 (fixed32; bytes 85 01 + the value, little-endian) after `version`: the CRC-32 of the
+ * original file exactly as zlib.crc32 gives it (ISO-HDLC: reflected polynomial 0xEDB88320, init and
+ * xorout 0xFFFFFFFF).  6 bytes per container; a reference-model container, which has no Metadata
+ * otherwise, gets one holding only this field (8 bytes).  No tag changes: the field is additive, and a
+ * reader from before it (the reference's included) skips it and decodes the file.  Hooks compress
+ * sessions never write it.
+ * Reading needs no option: every call that writes a file from a container that has the field checks
+ * it (avr_decompress_file(s), avr_splice_container, avr_dec_plan_splice(_crc), avr_hooks_end of a
+ * decompress session) and returns AVR_ERR_CHECKSUM on a mismatch -- the whole-file calls without an
+ * output, a call that writes into the caller's buffer before it has written anything.  A second
+ * field 16 in the Metadata, or one of another wire type, is AVR_ERR_FORMAT.
+ * The value is a fold, never a pass over the file: a CRC is linear, so the file's is the combine
+ * (avr_crc32_combine), in block order, of each block's file bytes -- a literal's by a host CRC, a coded
+ * block's from the CRC of its slice's bytes, which avr_crc_spans computes on the device where the
+ * slice lies (the payload arena at compress, the regenerated buffer at decompress), with the
+ * last-byte rule (recode.cpp:1345-1356) applied to the value.  Default: the environment's
+ * AVR_CHECKSUMS (non-zero: on), else 0. */
+int avr_set_checksums(avr_ctx* ctx, int on);
+int avr_get_checksums(const avr_ctx* ctx);
+/* zlib's crc32 and crc32_combine: avr_crc32 continues `crc` (0 to start) over p[0, n);
+ * avr_crc32_combine(crc(A), crc(B), |B|) = crc(AB), in O(log |B|) multiply-mods.  Host only. */
+uint32_t avr_crc32(uint32_t crc, const uint8_t* p, size_t n);
+uint32_t avr_crc32_combine(uint32_t a, uint32_t b, uint64_t len_b);
+/* The CRC-32 of n spans of one device buffer, one workgroup per span on `stream` (NULL = default):
+ * d_crc[k] = crc32(d_buf[d_off[k] .. + d_len[k])), any alignment, overlaps allowed; d_status[k] = 0, or
+ * AVR_SLICE_OVERFLOW with d_crc[k] = 0 for a span that does not lie inside buf_len (checked on the
+ * device; nothing of it is read).  All pointers are device pointers; nothing is synchronised;
+ * n <= 0 launches nothing. */
+int avr_crc_spans(avr_ctx* ctx, const uint8_t* d_buf, size_t buf_len, const uint64_t* d_off, const uint32_t* d_len,
+                  int n, uint32_t* d_crc, int32_t* d_status, void* stream);
 
 /* ------------------------------------------------------------------ whole files (host memory) */
 /* in: an MP4 (avcC) or Annex-B H.264 file.  *out: serialized Recoded protobuf (recode.proto). */
@@ -438,6 +477,14 @@ int avr_dec_plan_descs(const avr_dec_plan* plan, avr_slice_desc* out);
 int avr_dec_plan_arena(const avr_dec_plan* plan, uint8_t* out, size_t cap);
 int avr_dec_plan_splice(const avr_dec_plan* plan, const int32_t* status, const uint8_t* regen, size_t regen_len,
                         const uint64_t* offsets, const uint32_t* lens, uint8_t* out, size_t out_cap, size_t* out_len);
+/* avr_dec_plan_splice with, for a checked container, crcs[k] = the CRC-32 of slice k's lens[k]
+ * regenerated bytes as a device computed it (avr_crc_spans over the regenerated buffer, or over a cut
+ * slice's units, combined): the splice then reads no slice's bytes for the check.  crcs NULL, and
+ * every other splice entry point, computes them from regen on host threads.  The values are read only
+ * when the container has the field; wrong ones fail the file (AVR_ERR_CHECKSUM). */
+int avr_dec_plan_splice_crc(const avr_dec_plan* plan, const int32_t* status, const uint8_t* regen, size_t regen_len,
+                            const uint64_t* offsets, const uint32_t* lens, const uint32_t* crcs, uint8_t* out,
+                            size_t out_cap, size_t* out_len);
 
 /* Piece plans: the sharded decompress of a container whose long slices were cut (avr_set_split_bytes).
  * The unit of work is what one workgroup regenerates: a whole coded slice, or one piece of a split
@@ -584,13 +631,44 @@ int avr_assemble_container_seams_parsed(const uint8_t* file, size_t n, int model
  * AVR_ASSEMBLE_SPLIT32: seams fields are allowed for AVR_MODEL_PARALLEL32 (without the flag every
  * assemble call refuses them), and a container that holds one is tagged "avrecode-amd:P32S" /
  * "P32SE": what avr_compress_file writes with avr_set_split_p32 on.  AVR_ERR_INVALID_ARGUMENT for the
- * flag with any other model. */
-enum { AVR_ASSEMBLE_ESCAPED = 1, AVR_ASSEMBLE_SPLIT32 = 2 };
+ * flag with any other model.
+ * AVR_ASSEMBLE_CRC: a checked container (avr_set_checksums), for every assemblable model: the file's
+ * CRC-32 is folded from the literals and the coded slices' payload CRCs, which the assembly computes
+ * on host threads -- or takes from avr_assemble_container_args' crcs. */
+enum { AVR_ASSEMBLE_ESCAPED = 1, AVR_ASSEMBLE_SPLIT32 = 2, AVR_ASSEMBLE_CRC = 4 };
 int avr_assemble_container_opts(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
                                 const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
                                 size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, const uint8_t* seams,
                                 size_t seams_len, const uint64_t* seam_offsets, const uint32_t* seam_lens,
                                 uint32_t flags, uint8_t** out, size_t* out_len);
+/* avr_assemble_container_opts with its parameters in a struct (size = sizeof(avr_assemble_args), first)
+ * and one more: crcs[k] = the CRC-32 of slice k's payload (avr_parse_stream order; read for coded
+ * slices only, and only with AVR_ASSEMBLE_CRC), as the ranks' devices computed them over their payload
+ * arenas (avr_crc_spans).  NULL: computed here.  Values a caller brings are trusted -- rank 0 cannot
+ * check them without doing the work again -- so wrong ones give a container that every checking
+ * reader refuses.  AVR_ERR_INVALID_ARGUMENT for a size that is not this struct's. */
+typedef struct {
+  size_t size;
+  const uint8_t* file;
+  size_t n;
+  int model;
+  const avr_slice_desc* descs;
+  int n_slices;
+  const uint8_t* arena;
+  size_t arena_len;
+  const int32_t* status;
+  const uint8_t* recoded;
+  size_t recoded_len;
+  const uint64_t* offsets;
+  const uint32_t* lens;
+  const uint8_t* seams;
+  size_t seams_len;
+  const uint64_t* seam_offsets;
+  const uint32_t* seam_lens;
+  uint32_t flags;
+  const uint32_t* crcs;
+} avr_assemble_args;
+int avr_assemble_container_args(const avr_assemble_args* args, uint8_t** out, size_t* out_len);
 /* The two device steps that let a rank check its split slices without their bytes leaving the device
  * (all pointers device pointers, nothing synchronised).
  * avr_stage_pieces: the units' streams -- unit k's d_desc[k].payload_size bytes at d_out + d_src[k],
@@ -617,8 +695,9 @@ int avr_verify_units(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_slice
 /* Container codec check (host only): parse a Recoded protobuf (recode.proto:1-19) with the
  * library's own wire codec -- the one avr_decompress_file uses -- and return (a) its fields as JSON,
  * {"version": null | hex, "blocks": [{"size": int, "literal": hex, "skip_coded": bool, "cabac": hex,
- * "length_parity": bool, "last_byte": hex, "seams": hex, "escapes": int}, ...]} with only the fields present, and (b) the message
- * re-serialised by the library's writer (the one avr_compress_file uses; Metadata.version only).
+ * "length_parity": bool, "last_byte": hex, "seams": hex, "escapes": int}, ...]} with only the fields present -- and
+ * "file_crc": int after "version" when the Metadata holds field 16 -- and (b) the message
+ * re-serialised by the library's writer (the one avr_compress_file uses; Metadata.version and field 16 only).
  * Both buffers are malloc'd (avr_free).  AVR_ERR_FORMAT when the bytes are not a Recoded message. */
 int avr_container_describe(const uint8_t* in, size_t n, char** json, uint8_t** reserialized, size_t* len);
 
