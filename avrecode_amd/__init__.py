@@ -26,7 +26,7 @@ __all__ = [
     "plan_decompress", "splice_container", "container_model", "source_sha", "library_path", "EXPORTED_SYMBOLS",
     "seams_of_container", "SPLIT_SLOT", "SplitPlan", "split_plan", "seams_build", "escape_payload",
     "ASSEMBLE_ESCAPED", "ASSEMBLE_SPLIT32", "ASSEMBLE_CRC", "ERR_CHECKSUM", "crc32", "crc32_combine",
-    "file_crc_of_container",
+    "file_crc_of_container", "Reader", "SPAN", "RANGE_TAIL", "SPAN_LITERAL", "RANGE_NO_POS", "RANGE_SPAN_BYTES",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,6 +74,9 @@ EXPORTED_SYMBOLS = (
     "avr_set_split_p32", "avr_get_split_p32", "avr_compress_split_slices_m", "avr_decompress_pieces_m",
     "avr_set_checksums", "avr_get_checksums", "avr_crc32", "avr_crc32_combine", "avr_crc_spans",
     "avr_assemble_container_args", "avr_dec_plan_splice_crc",
+    "avr_dec_plan_file_size", "avr_dec_plan_range", "avr_dec_plan_range_apply", "avr_gather_spans", "avr_range_tails",
+    "avr_reader_open", "avr_reader_info", "avr_reader_read", "avr_reader_read_device", "avr_reader_span",
+    "avr_reader_last", "avr_reader_close",
 )
 
 # avr_slice_desc / avr_slice_result (include/avrecode.h), C layout
@@ -98,6 +101,13 @@ SLICE_NO_END = -9        # AVR_SLICE_NO_END
 SLICE_CODER = -10        # AVR_SLICE_CODER
 SLICE_OVERFLOW = -12     # AVR_SLICE_OVERFLOW
 # avr_split_slot (include/avrecode.h): a slice's cut records in a split compress batch; (-1, 0): none
+# avr_span / avr_range_tail (range reads, ABI 12)
+SPAN = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("len", "<u4"), ("source", "<i4")], align=True)
+RANGE_TAIL = np.dtype([("keep", "<u4"), ("q_last", "<u4"), ("size", "<u4"), ("has_rule", "u1"), ("length_parity", "u1"),
+                       ("last_byte", "u1"), ("reserved", "u1"), ("final_pos", "<u8")], align=True)
+SPAN_LITERAL = -1               # avr_span.source of a literal: src_off indexes the container
+RANGE_NO_POS = 0xFFFFFFFFFFFFFFFF   # avr_range_tail.final_pos: the slice's final byte lies outside the window
+RANGE_SPAN_BYTES = 16384        # the planner's default span cap
 SPLIT_SLOT = np.dtype([("first", "<i4"), ("cap", "<u4")], align=True)
 # the head of a seam record in the split kernels' device layout (SeamRec, csrc/avr_records.h); then
 # 1024 context bytes and 40 edge bytes per macroblock column
@@ -131,6 +141,23 @@ class _FileStats(ctypes.Structure):
                 ("bill", ctypes.c_uint64 * 6), ("cabac_bill", ctypes.c_uint64 * 6),
                 ("attempts", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("compress_phases", _PhaseTimes), ("decompress_phases", _PhaseTimes)]
+
+
+class _RangeInfo(ctypes.Structure):   # avr_range_info
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("file_size", ctypes.c_uint64),
+                ("literal_bytes", ctypes.c_uint64), ("unit_lo", ctypes.c_int32), ("unit_hi", ctypes.c_int32),
+                ("n_spans", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class _ReaderInfo(ctypes.Structure):   # avr_reader_info_t
+    _fields_ = [("file_size", ctypes.c_uint64), ("model", ctypes.c_int32), ("random_access", ctypes.c_int32),
+                ("n_blocks", ctypes.c_int32), ("n_units", ctypes.c_int32), ("checked", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class _ReadStats(ctypes.Structure):   # avr_read_stats
+    _fields_ = [("units", ctypes.c_uint64), ("pieces", ctypes.c_uint64), ("regenerated_bytes", ctypes.c_uint64),
+                ("literal_bytes", ctypes.c_uint64), ("spans", ctypes.c_uint64), ("phases", _PhaseTimes)]
 
 
 class _AssembleArgs(ctypes.Structure):   # avr_assemble_args
@@ -276,6 +303,20 @@ def lib() -> ctypes.CDLL:
     L.avr_assemble_container_args.argtypes = [ctypes.POINTER(_AssembleArgs), pp, psz]
     L.avr_dec_plan_splice_crc.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, psz]
     L.avr_get_split_bytes.restype = sz
+    u64 = ctypes.c_uint64
+    L.avr_dec_plan_file_size.argtypes = [vp, ctypes.POINTER(u64)]
+    L.avr_dec_plan_range.argtypes = [vp, u64, u64, ctypes.c_uint32, ctypes.POINTER(_RangeInfo), pp, pp]
+    L.avr_dec_plan_range_apply.argtypes = [vp, i32, vp, i32, vp, sz, vp, sz, vp, vp, vp, sz, vp]
+    L.avr_gather_spans.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp, vp]
+    L.avr_range_tails.argtypes = [vp, vp, vp, i32, vp, sz, vp, vp]
+    L.avr_reader_open.argtypes = [vp, vp, sz, pp]
+    L.avr_reader_info.argtypes = [vp, ctypes.POINTER(_ReaderInfo)]
+    L.avr_reader_read.argtypes = [vp, u64, sz, vp, psz]
+    L.avr_reader_read_device.argtypes = [vp, u64, sz, vp, psz]
+    L.avr_reader_span.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), pi]
+    L.avr_reader_last.argtypes = [vp, ctypes.POINTER(_ReadStats)]
+    L.avr_reader_close.argtypes = [vp]
+    L.avr_reader_close.restype = None
     for name in EXPORTED_SYMBOLS:   # fails here, not at first use, when the build is stale
         getattr(L, name)
     _lib = L
@@ -514,6 +555,59 @@ class DecompressPlan:
         if r != AVR_OK:
             raise AvrError(r, f"avr_dec_plan_splice failed (file {olen.value} B, buffer {out.nbytes} B)")
         return out[:olen.value]
+
+    @property
+    def file_size(self) -> int:
+        """The size of the file the loaded container restores (avr_dec_plan_file_size): the prefix sum
+        of its blocks, from the container alone."""
+        v = ctypes.c_uint64()
+        r = lib().avr_dec_plan_file_size(self._h, ctypes.byref(v))
+        if r != AVR_OK:
+            raise AvrError(r, "avr_dec_plan_file_size failed")
+        return int(v.value)
+
+    def range(self, off: int, n: int, span_cap: int = 0) -> dict:
+        """The window [off, off + n) of the file, clamped to it, planned (avr_dec_plan_range; a piece
+        plan): {"off", "len", "file_size", "literal_bytes", "unit_lo", "unit_hi", "spans": SPAN[],
+        "tails": RANGE_TAIL[unit_hi - unit_lo]}.  A span's source is SPAN_LITERAL (src_off indexes the
+        container) or k >= 0 (the regenerated bytes of unit unit_lo + k); none is longer than span_cap
+        (0: RANGE_SPAN_BYTES)."""
+        info, sp, tl = _RangeInfo(), ctypes.c_void_p(), ctypes.c_void_p()
+        r = lib().avr_dec_plan_range(self._h, int(off), int(n), int(span_cap), ctypes.byref(info), ctypes.byref(sp),
+                                     ctypes.byref(tl))
+        if r != AVR_OK:
+            raise AvrError(r, "avr_dec_plan_range failed")
+        nu = info.unit_hi - info.unit_lo
+        spans = _take_array(sp, max(1, info.n_spans) * SPAN.itemsize).view(SPAN)[:info.n_spans].copy()
+        tails = _take_array(tl, max(1, nu) * RANGE_TAIL.itemsize).view(RANGE_TAIL)[:nu].copy()
+        return {"off": int(info.off), "len": int(info.len), "file_size": int(info.file_size),
+                "literal_bytes": int(info.literal_bytes), "unit_lo": int(info.unit_lo), "unit_hi": int(info.unit_hi),
+                "spans": spans, "tails": tails}
+
+    def range_apply(self, rng: dict, regen, unit_off, res) -> "tuple[bytes, np.ndarray]":
+        """A planned window applied on the host (avr_dec_plan_range_apply): unit unit_lo + k's regenerated
+        bytes stand at regen[unit_off[k]:], its SLICE_RESULT in res[k].  Returns (the window's bytes,
+        the per-unit statuses); raises AvrError (format error) when a status is not 0, with the
+        statuses as the exception's `status`."""
+        avrc, keep = self._keep
+        cp, cn, ckeep = _buf(avrc)
+        rp, rn, rkeep = _buf(regen)
+        spans = np.ascontiguousarray(rng["spans"], dtype=SPAN)
+        tails = np.ascontiguousarray(rng["tails"], dtype=RANGE_TAIL)
+        uo = np.ascontiguousarray(unit_off, dtype=np.uint64)
+        rs = np.ascontiguousarray(res, dtype=SLICE_RESULT)
+        nu = len(tails)
+        if len(uo) != nu or len(rs) != nu:
+            raise ValueError("DecompressPlan.range_apply: one offset and one result per selected unit")
+        out = np.zeros(max(1, rng["len"]), dtype=np.uint8)
+        st = np.zeros(max(1, nu), dtype=np.int32)
+        r = lib().avr_dec_plan_range_apply(spans.ctypes.data, len(spans), tails.ctypes.data, nu, cp, cn, rp, rn,
+                                           uo.ctypes.data, rs.ctypes.data, out.ctypes.data, rng["len"], st.ctypes.data)
+        if r != AVR_OK:
+            e = AvrError(r, "avr_dec_plan_range_apply failed")
+            e.status = st[:nu].copy()
+            raise e
+        return out[:rng["len"]].tobytes(), st[:nu]
 
     def close(self):
         if self._h:
@@ -1137,6 +1231,22 @@ class Context:
         self._check(lib().avr_pack_pieces(self._h, P(d_desc), P(d_pieces), P(d_res), n, P(d_out), P(d_packed),
                                           P(d_offsets), P(d_kept), P(d_status), self._stream(stream)), "pack_pieces")
 
+    def gather_spans(self, d_spans, n, d_src, src_len, d_dst, dst_len, d_status, stream=None):
+        """avr_gather_spans: span k (SPAN rows on the device) copies len bytes from d_src + src_off to
+        d_dst + dst_off, one workgroup per span, any alignment; d_status[k] SLICE_OVERFLOW for a span
+        outside src_len or dst_len (nothing of it read or written)."""
+        P = self._ptr
+        self._check(lib().avr_gather_spans(self._h, P(d_spans), int(n), P(d_src), int(src_len), P(d_dst), int(dst_len),
+                                           P(d_status), self._stream(stream)), "gather_spans")
+
+    def range_tails(self, d_tails, d_res, n, d_dst, dst_len, d_status, stream=None):
+        """avr_range_tails: after gather_spans on the same stream, unit k's SLICE_RESULT checked against
+        its RANGE_TAIL row (d_status[k]: the unit's status, SLICE_NO_END for a short piece or a slice
+        of the wrong length) and the last-byte rule applied at final_pos."""
+        P = self._ptr
+        self._check(lib().avr_range_tails(self._h, P(d_tails), P(d_res), int(n), P(d_dst), int(dst_len), P(d_status),
+                                          self._stream(stream)), "range_tails")
+
     # the split compress of slice batches (ABI 8); the two host steps need no context
     split_plan = staticmethod(split_plan)
     seams_build = staticmethod(seams_build)
@@ -1192,3 +1302,78 @@ class Context:
         self._check(lib().avr_synthesize_stream(self._h, ctypes.byref(sp), int(n), ctypes.byref(out),
                                                 ctypes.byref(olen)), "synthesize")
         return _take(out, olen.value)
+
+
+class Reader:
+    """An opened container that serves byte ranges of its file (avr_reader_*): pread semantics, the
+    window clamped to the file.  In the parallel models' containers (info["random_access"]) a read
+    regenerates only the slices and pieces its window touches; every other container is regenerated
+    whole at the first read and served from host memory.  The container's bytes are kept alive by the
+    reader.  A context manager; close() before the context closes."""
+
+    def __init__(self, ctx: Context, avrc):
+        self._ctx = ctx
+        p, n, self._keep = _buf(avrc)
+        self._h = ctypes.c_void_p()
+        ctx._check(lib().avr_reader_open(ctx._h, p, n, ctypes.byref(self._h)), "avr_reader_open")
+        i = _ReaderInfo()
+        ctx._check(lib().avr_reader_info(self._h, ctypes.byref(i)), "avr_reader_info")
+        self.info = {f: int(getattr(i, f)) for f, _ in _ReaderInfo._fields_ if f != "reserved"}
+        self.size = self.info["file_size"]
+
+    def read(self, off: int, n: int) -> bytes:
+        n = max(0, min(int(n), self.size - int(off))) if off < self.size else 0
+        out = np.empty(max(1, n), dtype=np.uint8)
+        got = ctypes.c_size_t()
+        self._ctx._check(lib().avr_reader_read(self._h, int(off), n, out.ctypes.data, ctypes.byref(got)),
+                         "avr_reader_read")
+        return out[:got.value].tobytes()
+
+    def read_into(self, dst, off: int, n: int) -> int:
+        """The window into device memory (avr_reader_read_device): dst a torch uint8 tensor on the
+        context's device with room for n bytes, or a device pointer (int).  Returns the bytes read."""
+        if isinstance(dst, int):
+            ptr = ctypes.c_void_p(dst)
+        else:
+            if dst.numel() * dst.element_size() < min(int(n), max(0, self.size - int(off))):
+                raise ValueError("Reader.read_into: the tensor is smaller than the window")
+            ptr = ctypes.c_void_p(dst.data_ptr())
+        got = ctypes.c_size_t()
+        self._ctx._check(lib().avr_reader_read_device(self._h, int(off), int(n), ptr, ctypes.byref(got)),
+                         "avr_reader_read_device")
+        return int(got.value)
+
+    def span(self, off: int) -> "tuple[int, int, bool]":
+        """(lo, hi, coded): the file bytes [lo, hi) of the block holding off."""
+        lo, hi, coded = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+        self._ctx._check(lib().avr_reader_span(self._h, int(off), ctypes.byref(lo), ctypes.byref(hi),
+                                               ctypes.byref(coded)), "avr_reader_span")
+        return int(lo.value), int(hi.value), bool(coded.value)
+
+    @property
+    def last(self) -> dict:
+        """What the last successful read did (avr_reader_last): units regenerated, the pieces among them,
+        regenerated / literal bytes, spans, and the read's phase times."""
+        s = _ReadStats()
+        self._ctx._check(lib().avr_reader_last(self._h, ctypes.byref(s)), "avr_reader_last")
+        d = {f: int(getattr(s, f)) for f, _ in _ReadStats._fields_ if f != "phases"}
+        d["phases"] = _phases(s.phases)
+        return d
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().avr_reader_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+

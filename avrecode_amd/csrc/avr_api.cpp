@@ -1668,6 +1668,273 @@ int avr_verify_units(avr_ctx* c, const avr_slice_desc* d_desc, const avr_slice_r
   return AVR_OK;
 }
 
+// ------------------------------------------------------------------ range reads (ABI 12)
+int avr_gather_spans(avr_ctx* c, const avr_span* d_spans, int n, const uint8_t* d_src, size_t src_len, uint8_t* d_dst,
+                     size_t dst_len, int32_t* d_status, void* stream) {
+  if (!c) return AVR_ERR_INVALID_ARGUMENT;
+  if (n <= 0) return AVR_OK;
+  if (!d_spans || !d_src || !d_dst || !d_status) return AVR_ERR_INVALID_ARGUMENT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, avr::launch_gather_spans(d_spans, n, d_src, src_len, d_dst, dst_len, d_status, (hipStream_t)stream));
+  return AVR_OK;
+}
+
+int avr_range_tails(avr_ctx* c, const avr_range_tail* d_tails, const avr_slice_result* d_res, int n, uint8_t* d_dst,
+                    size_t dst_len, int32_t* d_status, void* stream) {
+  if (!c) return AVR_ERR_INVALID_ARGUMENT;
+  if (n <= 0) return AVR_OK;
+  if (!d_tails || !d_res || !d_dst || !d_status) return AVR_ERR_INVALID_ARGUMENT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, avr::launch_range_tails(d_tails, d_res, n, d_dst, dst_len, d_status, (hipStream_t)stream));
+  return AVR_OK;
+}
+
+// One window of a random-access container (include/avrecode.h): planned on the host, then on the
+// context's stream the upload of what the window needs, the selected units regenerated -- the pieces
+// through avr_decompress_pieces_m, the whole slices through avr_decompress_slices, one launch after
+// the other on rows grouped that way -- the gather into dst (the reader's window buffer, or the
+// caller's device buffer) and the tails.  The statuses come back before any byte does.
+static int reader_window(avr_reader* r, uint64_t off, size_t len, uint8_t* out, bool device, size_t* got) {
+  avr_ctx* c = r->c;
+  const avr_dec_plan* h = r->plan;
+  const double t0 = now_s();
+  if (int e = plan_range(h, off, len, 0, &r->rp)) return fail(c, e, "avr_reader_read: the window cannot be planned");
+  const avr_range_info in = r->rp.info;
+  if (!in.len) return AVR_OK;
+  const int lo = in.unit_lo, nu = in.unit_hi - in.unit_lo, nsp = in.n_spans;
+  if (h->plan.arena_copies.size() != h->units.size()) return fail(c, AVR_ERR_FORMAT, "avr_reader_read: not a piece plan");
+  auto is_piece = [&](int u) {
+    const avr_piece& p = h->unit_pieces[u];
+    return p.seam >= 0 || p.n_mbs > 0 || p.keep != UINT32_MAX;
+  };
+  int np = 0;
+  for (int k = 0; k < nu; k++) np += is_piece(lo + k);
+  // the rows of the two launches: pieces first, then whole slices; the streams re-placed compactly
+  // (16-byte aligned, >= 16 zero bytes after each), the outputs too
+  r->descs.resize(nu);
+  r->pieces.resize(nu);
+  r->tails.resize(nu);
+  std::vector<int> row(nu);
+  uint64_t at = 0, work = 0;
+  int ip = 0, iw = np, w_pieces = 1, w_whole = 1, mh = 1;
+  for (int k = 0; k < nu; k++) {
+    avr_slice_desc d = h->units[lo + k];
+    if (h->plan.arena_copies[lo + k].len != d.payload_size)
+      return fail(c, AVR_ERR_FORMAT, "avr_reader_read: not a piece plan");
+    d.payload_offset = at;
+    at = (at + d.payload_size + 16 + 15) & ~(uint64_t)15;
+    place_output(&d, &work);
+    const bool pc = is_piece(lo + k);
+    row[k] = pc ? ip++ : iw++;
+    (pc ? w_pieces : w_whole) = std::max(pc ? w_pieces : w_whole, pc ? d.mb_width : ring_cols(d));
+    mh = std::max(mh, d.mb_height);
+    r->descs[row[k]] = d;
+    r->pieces[row[k]] = h->unit_pieces[lo + k];
+    r->tails[row[k]] = r->rp.tails[k];
+  }
+  const uint64_t upload = at + in.literal_bytes, work_base = (upload + 255) & ~(uint64_t)255;
+  const uint64_t buf_len = work_base + work + 16;
+  if (upload > r->stage_cap) {
+    if (r->stage) (void)hipHostFree(r->stage);
+    r->stage = nullptr;
+    r->stage_cap = 0;
+    const size_t cap = (size_t)((upload + 65535) & ~(uint64_t)65535);
+    HIP_TRY(c, hipHostMalloc((void**)&r->stage, cap, hipHostMallocDefault));
+    r->stage_cap = cap;
+  }
+  for (int k = 0; k < nu; k++) {
+    const avr_slice_desc& d = r->descs[row[k]];
+    const uint64_t end = (d.payload_offset + d.payload_size + 16 + 15) & ~(uint64_t)15;
+    if (d.payload_size) memcpy(r->stage + d.payload_offset, h->plan.arena_copies[lo + k].src, d.payload_size);
+    memset(r->stage + d.payload_offset + d.payload_size, 0, end - d.payload_offset - d.payload_size);
+  }
+  // the spans' sources in the read's buffer: the literals one after the other behind the streams, a
+  // unit's bytes where its output was placed
+  uint64_t lit = at;
+  for (avr_span& s : r->rp.spans) {
+    if (s.source == AVR_SPAN_LITERAL) {
+      memcpy(r->stage + lit, r->avrc + s.src_off, s.len);   // plan_range has checked it inside the container
+      s.src_off = lit;
+      lit += s.len;
+    } else {
+      s.src_off += work_base + r->descs[row[s.source]].out_offset;
+    }
+  }
+  HIP_TRY(c, r->buf.reserve(buf_len));
+  HIP_TRY(c, r->d_descs.reserve(sizeof(avr_slice_desc) * std::max(1, nu)));
+  HIP_TRY(c, r->d_res.reserve(sizeof(avr_slice_result) * std::max(1, nu)));
+  HIP_TRY(c, r->d_tails.reserve(sizeof(avr_range_tail) * std::max(1, nu)));
+  HIP_TRY(c, r->d_spans.reserve(sizeof(avr_span) * nsp));
+  HIP_TRY(c, r->d_status.reserve(sizeof(int32_t) * ((size_t)nsp + nu)));
+  if (!device) HIP_TRY(c, r->d_win.reserve(in.len));
+  uint8_t* dst = device ? out : r->d_win.as<uint8_t>();
+  uint8_t* d_in = r->buf.as<uint8_t>();
+  uint8_t* d_work = d_in + work_base;
+  avr_slice_desc* dd = r->d_descs.as<avr_slice_desc>();
+  avr_slice_result* dr = r->d_res.as<avr_slice_result>();
+  int32_t* d_st = r->d_status.as<int32_t>();
+  hipStream_t st = c->stream;
+  const double t1 = now_s();
+  HIP_TRY(c, hipEventRecord(r->ev[0], st));
+  HIP_TRY(c, hipMemcpyAsync(d_in, r->stage, upload, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(r->d_spans.p, r->rp.spans.data(), sizeof(avr_span) * nsp, hipMemcpyHostToDevice, st));
+  if (nu) {
+    HIP_TRY(c, hipMemcpyAsync(dd, r->descs.data(), sizeof(avr_slice_desc) * nu, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(r->d_tails.p, r->tails.data(), sizeof(avr_range_tail) * nu, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(dr, 0, sizeof(avr_slice_result) * nu, st));
+  }
+  HIP_TRY(c, hipEventRecord(r->ev[1], st));
+  const int model = r->info.model;
+  if (np)
+    if (int e = avr_decompress_pieces_m(c, model, dd, r->pieces.data(), np, w_pieces, mh, r->d_recs.as<uint8_t>(),
+                                        (int)(h->rec_stride ? h->recs.size() / h->rec_stride : 0), h->rec_stride, d_in,
+                                        d_work, dr, st))
+      return e;
+  if (nu > np)
+    if (int e = avr_decompress_slices(c, dd + np, nu - np, w_whole, mh, d_in, d_work, dr + np, model, st)) return e;
+  HIP_TRY(c, avr::launch_gather_spans(r->d_spans.as<avr_span>(), nsp, d_in, buf_len, dst, in.len, d_st, st));
+  HIP_TRY(c, avr::launch_range_tails(r->d_tails.as<avr_range_tail>(), dr, nu, dst, in.len, d_st + nsp, st));
+  HIP_TRY(c, hipEventRecord(r->ev[2], st));
+  r->status.assign((size_t)nsp + nu, 0);
+  r->res.assign(nu, avr_slice_result{});
+  HIP_TRY(c, hipMemcpyAsync(r->status.data(), d_st, sizeof(int32_t) * r->status.size(), hipMemcpyDeviceToHost, st));
+  if (nu) HIP_TRY(c, hipMemcpyAsync(r->res.data(), dr, sizeof(avr_slice_result) * nu, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  const double t2 = now_s();
+  for (int k = 0; k < nsp; k++)
+    if (r->status[k])
+      return fail(c, AVR_ERR_FORMAT, "avr_reader_read: span " + std::to_string(k) + " lies outside its buffers");
+  for (int k = 0; k < nu; k++)
+    if (int32_t s = r->status[nsp + row[k]])
+      return fail(c, AVR_ERR_FORMAT,
+                  "avr_reader_read: unit " + std::to_string(lo + k) + " of the container failed to decode (" +
+                      std::to_string(s) + ")");
+  if (!device) HIP_TRY(c, hipMemcpy(out, dst, in.len, hipMemcpyDeviceToHost));
+  const double t3 = now_s();
+  avr_read_stats& ls = r->last;
+  ls = avr_read_stats{};
+  ls.units = (uint64_t)nu;
+  ls.pieces = (uint64_t)np;
+  for (const avr_slice_result& x : r->res) ls.regenerated_bytes += x.out_len;
+  ls.literal_bytes = in.literal_bytes;
+  ls.spans = (uint64_t)nsp;
+  float up = 0, kn = 0;
+  HIP_TRY(c, hipEventElapsedTime(&up, r->ev[0], r->ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&kn, r->ev[1], r->ev[2]));
+  ls.phases.demux_s = t1 - t0;
+  ls.phases.upload_s = up * 1e-3;
+  ls.phases.kernel_s = kn * 1e-3;
+  ls.phases.download_s = t3 - t2;
+  ls.phases.other_s = std::max(0.0, (t3 - t0) - ls.phases.demux_s - ls.phases.upload_s - ls.phases.kernel_s -
+                                        ls.phases.download_s);
+  *got = (size_t)in.len;
+  return AVR_OK;
+}
+
+static int reader_read(avr_reader* r, uint64_t off, size_t len, uint8_t* out, bool device, size_t* got) {
+  if (!r || !got) return AVR_ERR_INVALID_ARGUMENT;
+  *got = 0;
+  avr_ctx* c = r->c;
+  if (off + len < off) return fail(c, AVR_ERR_INVALID_ARGUMENT, "avr_reader_read: off + len overflows");
+  if (!len || off >= r->info.file_size) return AVR_OK;
+  if (!out) return AVR_ERR_INVALID_ARGUMENT;
+  return guarded(c, [&]() -> int {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (r->info.random_access) {
+      const int e = reader_window(r, off, len, out, device, got);
+      if (e) (void)hipStreamSynchronize(c->stream);   // nothing of a failed read stays in flight over the reader's buffers
+      return e;
+    }
+    // no random access: the whole file once, through the whole-file call (a checked container is checked)
+    if (!r->file) {
+      uint8_t* f = nullptr;
+      size_t fl = 0;
+      if (int e = avr_decompress_file(c, r->avrc, r->n, &f, &fl)) return e;
+      r->file = f;
+      r->file_len = fl;
+      r->last = avr_read_stats{};
+      r->last.phases = c->phase;
+    }
+    if (off >= r->file_len) return AVR_OK;
+    const size_t m = (size_t)std::min<uint64_t>(len, r->file_len - off);
+    if (device) HIP_TRY(c, hipMemcpy(out, r->file + off, m, hipMemcpyHostToDevice));
+    else memcpy(out, r->file + off, m);
+    *got = m;
+    return AVR_OK;
+  });
+}
+
+int avr_reader_open(avr_ctx* c, const uint8_t* avrc, size_t n, avr_reader** out) {
+  if (!c || !avrc || !out) return AVR_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  return guarded(c, [&]() -> int {
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::unique_ptr<avr_reader> r(new avr_reader());
+    r->c = c;
+    r->avrc = avrc;
+    r->n = n;
+    if (int e = avr_dec_plan_new(&r->plan)) return fail(c, e, "avr_reader_open: no plan handle");
+    int ns = 0, nu = 0, mw = 0, mh = 0, nr = 0;
+    size_t al = 0, wl = 0, rs = 0;
+    int e = avr_dec_plan_load_pieces(r->plan, avrc, n, &ns, &nu, &al, &wl, &mw, &mh, &nr, &rs);
+    const bool pieces = e == AVR_OK;
+    // the reference and chained models chain their slices: no units, the sizes from a slice plan
+    if (e == AVR_ERR_UNSUPPORTED) e = avr_dec_plan_load(r->plan, avrc, n, &ns, &al, &wl, &mw, &mh);
+    if (e) return fail(c, e, "avr_reader_open: not a container this library reads");
+    const avr_dec_plan* h = r->plan;
+    r->info.file_size = h->block_off.back();
+    r->info.model = h->job.model;
+    r->info.random_access = pieces && !h->escapes;
+    r->info.n_blocks = (int32_t)h->job.blocks.size();
+    r->info.n_units = r->info.random_access ? nu : 0;
+    r->info.checked = h->job.has_crc;
+    if (r->info.random_access) {
+      for (auto& ev : r->ev) HIP_TRY(c, hipEventCreate(&ev));
+      HIP_TRY(c, r->d_recs.reserve(std::max<size_t>(64, h->recs.size())));
+      if (!h->recs.empty()) HIP_TRY(c, hipMemcpy(r->d_recs.p, h->recs.data(), h->recs.size(), hipMemcpyHostToDevice));
+    }
+    *out = r.release();
+    return AVR_OK;
+  });
+}
+
+int avr_reader_info(const avr_reader* r, avr_reader_info_t* info) {
+  if (!r || !info) return AVR_ERR_INVALID_ARGUMENT;
+  *info = r->info;
+  return AVR_OK;
+}
+
+int avr_reader_read(avr_reader* r, uint64_t off, size_t len, uint8_t* out, size_t* got) {
+  return reader_read(r, off, len, out, false, got);
+}
+
+int avr_reader_read_device(avr_reader* r, uint64_t off, size_t len, uint8_t* d_out, size_t* got) {
+  return reader_read(r, off, len, d_out, true, got);
+}
+
+int avr_reader_span(const avr_reader* r, uint64_t off, uint64_t* lo, uint64_t* hi, int* coded) {
+  if (!r || !lo || !hi || !coded || off >= r->info.file_size) return AVR_ERR_INVALID_ARGUMENT;
+  const avr_dec_plan* h = r->plan;
+  const size_t i = block_of_offset(h, off);
+  *lo = h->block_off[i];
+  *hi = h->block_off[i + 1];
+  *coded = h->job.blocks[i].has_cabac ? 1 : 0;
+  return AVR_OK;
+}
+
+int avr_reader_last(const avr_reader* r, avr_read_stats* out) {
+  if (!r || !out) return AVR_ERR_INVALID_ARGUMENT;
+  *out = r->last;
+  return AVR_OK;
+}
+
+void avr_reader_close(avr_reader* r) {
+  if (!r) return;
+  (void)hipSetDevice(r->c->device);
+  if (r->c->stream) (void)hipStreamSynchronize(r->c->stream);
+  delete r;   // its events, pinned buffer, plan and device buffers go with it
+}
+
 static int synthesize_stream(avr_ctx* c, const avr_synth_params* p, int n, uint8_t** out, size_t* out_len) {
   if (!c || !p || n <= 0 || !out || !out_len || p->mb_width <= 0 || p->mb_height <= 0 || p->slice_type < 0 ||
       p->slice_type > 2 || p->chroma_format_idc < 1 || p->chroma_format_idc > 3 || p->gop_length < 0 ||

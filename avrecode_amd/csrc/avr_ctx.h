@@ -92,7 +92,42 @@ struct avr_ctx : avr_host::ErrSink {
   }
 };
 
-#define HIP_TRY(c, expr)                                                                              \
+// A reader (include/avrecode.h, ABI 12): an opened container that serves byte ranges of its file.
+// Random access: the piece plan loaded once, the seam records on the device, and the buffers of a
+// read -- all its own, sized by the largest window read so far, none proportional to the file and none
+// shared with the whole-file calls.  Otherwise: the whole file, regenerated at the first read.
+struct avr_reader {
+  using DevBuf = avr_host::DevBuf;
+  avr_ctx* c = nullptr;
+  const uint8_t* avrc = nullptr;
+  size_t n = 0;
+  avr_dec_plan* plan = nullptr;
+  avr_reader_info_t info{};
+  // one device buffer per read: the selected units' streams and the window's literal bytes (the
+  // upload), then the units' output space; gather_spans' source is the whole of it
+  DevBuf buf, d_descs, d_res, d_spans, d_tails, d_status, d_recs, d_win;
+  uint8_t* stage = nullptr;   // pinned: what a read uploads
+  size_t stage_cap = 0;
+  avr_host::RangePlan rp;
+  std::vector<avr_slice_desc> descs;
+  std::vector<avr_piece> pieces;
+  std::vector<avr_range_tail> tails;
+  std::vector<avr_slice_result> res;
+  std::vector<int32_t> status;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the upload, the kernels, the downloads
+  uint8_t* file = nullptr;    // without random access: the file, after the first read (avr_free)
+  size_t file_len = 0;
+  avr_read_stats last{};
+  ~avr_reader() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (stage) (void)hipHostFree(stage);
+    if (plan) avr_dec_plan_free(plan);
+    free(file);
+  }
+};
+
+#define HIP_TRY(c, expr)                                                                             \
   do {                                                                                                \
     hipError_t _e = (expr);                                                                           \
     if (_e != hipSuccess) return avr_host::fail(c, AVR_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(_e)); \

@@ -483,3 +483,71 @@ int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>*
 }
 
 }  // namespace avr_host
+
+// ------------------------------------------------------------------ avr_plan.cpp: the plan handle
+// decompressor::run (recode.cpp:1338-1409) cut in two around the device work: load = read_packet's
+// surrogate stream parsed and matched to the container's coded blocks (decompress_setup in layout
+// mode: descs and the arena layout, no bytes copied), then the arena written where the caller wants
+// it, and the splice of the regenerated slices with the literals and the last-byte patch
+// (recode.cpp:1345-1356).  A handle keeps its scratch (the surrogate stream) for the next load.
+struct avr_dec_plan {
+  avr_host::DecJob job;
+  avr_host::Plan plan;
+  uint64_t work = 0;
+  int max_h = 1;
+  const uint8_t* avrc = nullptr;   // the caller's container (the blocks point into it)
+  size_t n = 0;
+  // a piece plan (avr_dec_plan_load_pieces): plan.descs = the coded slices (a split slice once, the
+  // splice's indexing), units = what one workgroup regenerates, in container order; plan's arena
+  // layout is the units'
+  bool pieces = false;
+  std::vector<avr_slice_desc> units;
+  std::vector<avr_piece> unit_pieces;
+  avr_host::Bytes recs;            // the seam records, rec_stride apart
+  size_t rec_stride = 0;
+  // file coordinates, from the container alone (range reads): block i stands for file bytes
+  // [block_off[i], block_off[i + 1]); a piece plan also knows block i's units, [unit_first[i],
+  // unit_first[i + 1]), and where in its slice each unit's bytes start (unit_q0)
+  std::vector<uint64_t> block_off;
+  std::vector<int> unit_first;
+  std::vector<uint32_t> unit_q0;
+  bool escapes = false;            // some block carries field 17
+  void reset() {
+    avrc = nullptr;
+    pieces = false;
+    job.blocks.clear();
+    job.desc_of_block.clear();
+    job.splits.clear();
+    job.stream.clear();   // keeps its capacity: the next stream is written over mapped pages
+    plan.descs.clear();
+    plan.arena_copies.clear();
+    plan.arena_end = 0;
+    plan.max_w = 1;
+    plan.layout_only = true;
+    units.clear();
+    unit_pieces.clear();
+    recs.clear();
+    block_off.clear();
+    unit_first.clear();
+    unit_q0.clear();
+    escapes = false;
+  }
+};
+
+namespace avr_host {
+
+// The range planner (include/avrecode.h, avr_dec_plan_range): a window of the file as the units to
+// regenerate, the copies that lay it out and the per-unit checks.  No device.
+// the best of 16 / 64 / 256 KiB for the gather launch alone over a whole-file window of a 298 MB 4K
+// stream (scripts/reader_probe.py, profiles/reader_probe.json; DESIGN §2, "Range reads")
+constexpr uint32_t kRangeSpanBytes = 16384;
+struct RangePlan {
+  avr_range_info info{};
+  std::vector<avr_span> spans;
+  std::vector<avr_range_tail> tails;
+};
+int plan_range(const avr_dec_plan* h, uint64_t off, uint64_t len, uint32_t span_cap, RangePlan* rp);
+// the block holding file byte off (off < the file's size)
+size_t block_of_offset(const avr_dec_plan* h, uint64_t off);
+
+}  // namespace avr_host

@@ -186,5 +186,14 @@ hipError_t launch_crc_spans(const uint8_t* buf, uint64_t buf_len, const uint64_t
 // what its decompress left (out_offset, res.out_len; a failed slice: its status, crc 0)
 hipError_t launch_crc_slices(const avr_slice_desc* descs, const avr_slice_result* res, int n, bool regen,
                              const uint8_t* buf, uint64_t buf_len, uint32_t* crc, int32_t* status, hipStream_t stream);
+// avr_gather_spans / avr_range_tails (avr_k_gather.hip): a window of a file laid out from copy spans
+// over one source buffer (one workgroup per span, any alignment; status[k] = 0, or AVR_SLICE_OVERFLOW
+// for a span outside src_len or dst_len: nothing of it read or written), then -- after it on the same
+// stream -- one thread per selected unit checks its result against its tail record and applies the
+// last-byte rule where the slice's final byte lies inside dst_len
+hipError_t launch_gather_spans(const avr_span* spans, int n, const uint8_t* src, uint64_t src_len, uint8_t* dst,
+                               uint64_t dst_len, int32_t* status, hipStream_t stream);
+hipError_t launch_range_tails(const avr_range_tail* tails, const avr_slice_result* res, int n, uint8_t* dst,
+                              uint64_t dst_len, int32_t* status, hipStream_t stream);
 
 }  // namespace avr

@@ -179,45 +179,25 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
 }  // namespace avr_host
 
 // ------------------------------------------------------------------ sharded decompress plans
-// decompressor::run (recode.cpp:1338-1409) cut in two around the device work: load = read_packet's
-// surrogate stream parsed and matched to the container's coded blocks (decompress_setup in layout
-// mode: descs and the arena layout, no bytes copied), then the arena written where the caller wants
-// it, and the splice of the regenerated slices with the literals and the last-byte patch
-// (recode.cpp:1345-1356).  A handle keeps its scratch (the surrogate stream) for the next load.
-struct avr_dec_plan {
-  DecJob job;
-  Plan plan;
-  uint64_t work = 0;
-  int max_h = 1;
-  const uint8_t* avrc = nullptr;   // the caller's container (the blocks point into it)
-  size_t n = 0;
-  // a piece plan (avr_dec_plan_load_pieces): plan.descs = the coded slices (a split slice once, the
-  // splice's indexing), units = what one workgroup regenerates, in container order; plan's arena
-  // layout is the units'
-  bool pieces = false;
-  std::vector<avr_slice_desc> units;
-  std::vector<avr_piece> unit_pieces;
-  Bytes recs;                      // the seam records, rec_stride apart
-  size_t rec_stride = 0;
-  void reset() {
-    avrc = nullptr;
-    pieces = false;
-    job.blocks.clear();
-    job.desc_of_block.clear();
-    job.splits.clear();
-    job.stream.clear();   // keeps its capacity: the next stream is written over mapped pages
-    plan.descs.clear();
-    plan.arena_copies.clear();
-    plan.arena_end = 0;
-    plan.max_w = 1;
-    plan.layout_only = true;
-    units.clear();
-    unit_pieces.clear();
-    recs.clear();
-  }
-};
+// (struct avr_dec_plan: avr_host.h -- the reader of avr_api.cpp works on one too)
 
 namespace {
+
+// File coordinates from the container alone: block i stands for file bytes [block_off[i],
+// block_off[i + 1]) -- a literal for its length, a coded block for size (+ escapes) bytes, a
+// skip_coded block for none (decompress_setup has checked every size).
+void map_blocks(avr_dec_plan* h) {
+  const std::vector<avr::PbBlock>& bl = h->job.blocks;
+  h->block_off.assign(bl.size() + 1, 0);
+  uint64_t at = 0;
+  for (size_t i = 0; i < bl.size(); i++) {
+    h->block_off[i] = at;
+    if (bl[i].has_literal) at += bl[i].literal_len;
+    else if (bl[i].has_cabac) at += (uint64_t)bl[i].size + bl[i].escapes;
+    h->escapes |= bl[i].has_escapes;
+  }
+  h->block_off[bl.size()] = at;
+}
 
 // splice_job's output laid out: the literal and regenerated-slice copies, the last-byte patches
 // (position, byte) and the total length.  An escaped block (field 17) is one more copy job: its
@@ -286,7 +266,206 @@ void write_splice(const std::vector<avr::PbCopy>& copies, const std::vector<std:
 
 }  // namespace
 
+// ------------------------------------------------------------------ range reads: the planner
+namespace avr_host {
+
+size_t block_of_offset(const avr_dec_plan* h, uint64_t off) {
+  // the last block that starts at or before off and stands for at least one byte
+  const auto it = std::upper_bound(h->block_off.begin(), h->block_off.end(), off);
+  return (size_t)(it - h->block_off.begin()) - 1;
+}
+
+// One window [off, off + len) of the file (include/avrecode.h, avr_dec_plan_range).  The blocks it
+// touches in file order: a literal gives spans out of the container, a coded block the units whose
+// share [q0, q1) of its slice the window reaches, spans out of their regenerated bytes and -- for
+// every unit from the first selected to the last -- a tail.  Runs on bytes the caller does not
+// control: everything read from the plan is checked against the block it belongs to before it is
+// emitted.
+int plan_range(const avr_dec_plan* h, uint64_t off, uint64_t len, uint32_t span_cap, RangePlan* rp) {
+  if (!h || !h->avrc || !h->pieces || !rp || off + len < off) return AVR_ERR_INVALID_ARGUMENT;
+  if (!span_cap) span_cap = kRangeSpanBytes;
+  if (span_cap < 16 || span_cap > (1u << 30)) return AVR_ERR_INVALID_ARGUMENT;
+  if (h->escapes) return AVR_ERR_UNSUPPORTED;   // an escaped block's bytes are not a crop of its regenerated bytes
+  const std::vector<avr::PbBlock>& bl = h->job.blocks;
+  const size_t nb = bl.size(), nu = h->units.size();
+  if (h->block_off.size() != nb + 1 || h->unit_first.size() != nb + 1 || h->unit_q0.size() != nu ||
+      h->unit_pieces.size() != nu)
+    return AVR_ERR_INVALID_ARGUMENT;
+  const uint64_t file_size = h->block_off[nb];
+  rp->spans.clear();
+  rp->tails.clear();
+  rp->info = avr_range_info{};
+  rp->info.file_size = file_size;
+  const uint64_t w0 = std::min(off, file_size), w1 = w0 + std::min(len, file_size - w0);
+  rp->info.off = w0;
+  rp->info.len = w1 - w0;
+  if (w0 == w1) return AVR_OK;
+  int ulo = -1, uhi = -1;
+  // (source, src_off) + [a, b) of the file -> spans of at most span_cap bytes
+  auto emit = [&](int32_t source, uint64_t src_off, uint64_t a, uint64_t b) {
+    while (a < b) {
+      const uint32_t n = (uint32_t)std::min<uint64_t>(span_cap, b - a);
+      rp->spans.push_back(avr_span{src_off, a - w0, n, source});
+      src_off += n;
+      a += n;
+    }
+  };
+  // unit sources are written as plan indices first and rebased to unit_lo at the end
+  for (size_t i = block_of_offset(h, w0); i < nb && h->block_off[i] < w1; i++) {
+    const avr::PbBlock& b = bl[i];
+    const uint64_t b0 = h->block_off[i], b1 = h->block_off[i + 1];
+    const uint64_t a0 = std::max(b0, w0), a1 = std::min(b1, w1);
+    if (a0 >= a1) continue;   // a block of no bytes (skip_coded, an empty literal)
+    if (b.has_literal) {
+      if (b1 - b0 != b.literal_len || b.literal < h->avrc || (size_t)(b.literal - h->avrc) > h->n ||
+          b.literal_len > h->n - (size_t)(b.literal - h->avrc))
+        return AVR_ERR_FORMAT;
+      emit(AVR_SPAN_LITERAL, (uint64_t)(b.literal - h->avrc) + (a0 - b0), a0, a1);
+      rp->info.literal_bytes += a1 - a0;
+      continue;
+    }
+    const int u0 = h->unit_first[i], u1 = h->unit_first[i + 1];
+    // a coded block that no slice claimed ("Not all blocks were decoded.", recode.cpp:1354)
+    if (!b.has_cabac || u0 < 0 || u1 <= u0 || (size_t)u1 > nu || b.size <= 0 || (uint64_t)b.size != b1 - b0)
+      return AVR_ERR_FORMAT;
+    const uint32_t size = (uint32_t)b.size;
+    for (int u = u0; u < u1; u++) {
+      const bool last = u + 1 == u1;
+      const uint32_t q0 = h->unit_q0[u], q1 = last ? size : h->unit_q0[u + 1];
+      const avr_piece& pc = h->unit_pieces[u];
+      // the cuts ascend inside the slice, and keep is this unit's share of it
+      if (q0 > q1 || q1 > size || (u == u0 && q0 != 0) || (last ? pc.keep != UINT32_MAX : pc.keep != q1 - q0))
+        return AVR_ERR_FORMAT;
+      const uint64_t s0 = std::max(b0 + q0, a0), s1 = std::min(b0 + q1, a1);
+      if (s0 >= s1) continue;
+      if (ulo < 0) ulo = u;
+      uhi = u + 1;
+      emit(u, s0 - (b0 + q0), s0, s1);
+    }
+  }
+  if (ulo >= 0) {
+    rp->tails.reserve((size_t)(uhi - ulo));
+    // the tails of [ulo, uhi): the blocks these units belong to, walked once more
+    size_t i = block_of_offset(h, w0);
+    for (int u = ulo; u < uhi; u++) {
+      while (i < nb && h->unit_first[i + 1] <= u) i++;
+      if (i >= nb) return AVR_ERR_FORMAT;
+      const avr::PbBlock& b = bl[i];
+      const bool last = u + 1 == h->unit_first[i + 1];
+      avr_range_tail t{};
+      t.size = (uint32_t)b.size;
+      t.final_pos = AVR_RANGE_NO_POS;
+      if (!last) {
+        t.keep = h->unit_pieces[u].keep;
+      } else {
+        t.keep = UINT32_MAX;
+        t.q_last = h->unit_q0[u];
+        t.has_rule = b.has_parity && b.has_last_byte && !b.last_byte.empty();
+        t.length_parity = b.length_parity ? 1 : 0;
+        t.last_byte = t.has_rule ? (uint8_t)b.last_byte[0] : 0;
+        const uint64_t fin = h->block_off[i] + (uint64_t)b.size - 1;
+        if (fin >= w0 && fin < w1) t.final_pos = fin - w0;
+      }
+      rp->tails.push_back(t);
+    }
+    for (avr_span& s : rp->spans)
+      if (s.source >= 0) s.source -= ulo;
+  }
+  // what was emitted tiles the window: in order, without gap or overlap
+  uint64_t at = 0;
+  for (const avr_span& s : rp->spans) {
+    if (s.dst_off != at || !s.len || s.len > span_cap) return AVR_ERR_FORMAT;
+    at += s.len;
+  }
+  if (at != w1 - w0 || rp->spans.size() > (size_t)INT32_MAX) return AVR_ERR_FORMAT;
+  rp->info.unit_lo = std::max(ulo, 0);
+  rp->info.unit_hi = std::max(uhi, 0);
+  rp->info.n_spans = (int32_t)rp->spans.size();
+  return AVR_OK;
+}
+
+}  // namespace avr_host
+
 extern "C" {
+
+int avr_dec_plan_file_size(const avr_dec_plan* h, uint64_t* size) {
+  if (!h || !h->avrc || !size || h->block_off.empty()) return AVR_ERR_INVALID_ARGUMENT;
+  *size = h->block_off.back();
+  return AVR_OK;
+}
+
+int avr_dec_plan_range(const avr_dec_plan* h, uint64_t off, uint64_t len, uint32_t span_cap, avr_range_info* info,
+                       avr_span** spans, avr_range_tail** tails) {
+  if (!h || !info || !spans || !tails) return AVR_ERR_INVALID_ARGUMENT;
+  *spans = nullptr;
+  *tails = nullptr;
+  return guarded(nullptr, [&]() -> int {
+    RangePlan rp;
+    if (int r = plan_range(h, off, len, span_cap, &rp)) return r;
+    avr_span* s = (avr_span*)malloc(sizeof(avr_span) * std::max<size_t>(1, rp.spans.size()));
+    avr_range_tail* t = (avr_range_tail*)malloc(sizeof(avr_range_tail) * std::max<size_t>(1, rp.tails.size()));
+    if (!s || !t) {
+      free(s);
+      free(t);
+      return AVR_ERR_OUT_OF_MEMORY;
+    }
+    if (!rp.spans.empty()) memcpy(s, rp.spans.data(), sizeof(avr_span) * rp.spans.size());
+    if (!rp.tails.empty()) memcpy(t, rp.tails.data(), sizeof(avr_range_tail) * rp.tails.size());
+    *spans = s;
+    *tails = t;
+    *info = rp.info;
+    return AVR_OK;
+  });
+}
+
+// What gather_spans_kernel and range_tails_kernel (avr_k_gather.hip) do, on host buffers: the CPU
+// tests' reference for the two, and what tests/native/range_check.cpp drives under sanitizers.
+int avr_dec_plan_range_apply(const avr_span* spans, int n_spans, const avr_range_tail* tails, int n_units,
+                             const uint8_t* avrc, size_t avrc_len, const uint8_t* regen, size_t regen_len,
+                             const uint64_t* unit_off, const avr_slice_result* res, uint8_t* out, size_t out_len,
+                             int32_t* status) {
+  if (n_spans < 0 || n_units < 0 || (n_spans && (!spans || !out)) || (n_units && (!tails || !unit_off || !res || !status)))
+    return AVR_ERR_INVALID_ARGUMENT;
+  // every span inside its source and the window, every final byte inside the window: before any write
+  for (int k = 0; k < n_spans; k++) {
+    const avr_span& s = spans[k];
+    if (s.dst_off > out_len || s.len > out_len - s.dst_off) return AVR_ERR_INVALID_ARGUMENT;
+    if (s.source == AVR_SPAN_LITERAL) {
+      if (!avrc || s.src_off > avrc_len || s.len > avrc_len - s.src_off) return AVR_ERR_INVALID_ARGUMENT;
+    } else {
+      if (s.source < 0 || s.source >= n_units || !regen) return AVR_ERR_INVALID_ARGUMENT;
+      const uint64_t base = unit_off[s.source];
+      if (base > regen_len || s.src_off > regen_len - base || s.len > regen_len - base - s.src_off)
+        return AVR_ERR_INVALID_ARGUMENT;
+    }
+  }
+  for (int k = 0; k < n_units; k++)
+    if (tails[k].final_pos != AVR_RANGE_NO_POS && tails[k].final_pos >= out_len) return AVR_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < n_spans; k++) {
+    const avr_span& s = spans[k];
+    const uint8_t* src = s.source == AVR_SPAN_LITERAL ? avrc + s.src_off : regen + unit_off[s.source] + s.src_off;
+    if (s.len) memcpy(out + s.dst_off, src, s.len);
+  }
+  bool failed = false;
+  for (int k = 0; k < n_units; k++) {
+    const avr_range_tail& t = tails[k];
+    const avr_slice_result& r = res[k];
+    int32_t st = r.status;
+    if (!st) {
+      if (t.keep != UINT32_MAX) {
+        if (r.out_len < t.keep) st = AVR_SLICE_NO_END;
+      } else {
+        const uint64_t T = (uint64_t)t.q_last + r.out_len;
+        const bool append = t.has_rule && (uint32_t)(T & 1) != (uint32_t)(t.length_parity & 1);
+        if (T + (append ? 1 : 0) != t.size) st = AVR_SLICE_NO_END;
+        else if (t.has_rule && t.final_pos != AVR_RANGE_NO_POS) out[t.final_pos] = t.last_byte;
+      }
+    }
+    status[k] = st;
+    failed |= st != 0;
+  }
+  return failed ? AVR_ERR_FORMAT : AVR_OK;
+}
 
 int avr_dec_plan_new(avr_dec_plan** out) {
   if (!out) return AVR_ERR_INVALID_ARGUMENT;
@@ -311,6 +490,7 @@ int avr_dec_plan_load(avr_dec_plan* h, const uint8_t* avrc, size_t n, int* n_sli
       place_output(&d, &w);
       mh = std::max(mh, d.mb_height);
     }
+    map_blocks(h);
     h->avrc = avrc;
     h->n = n;
     h->work = w;
@@ -355,9 +535,11 @@ int avr_dec_plan_load_pieces(avr_dec_plan* h, const uint8_t* avrc, size_t n, int
       h->units.push_back(d);
       h->unit_pieces.push_back(p);
     };
+    h->unit_first.assign(j.blocks.size() + 1, 0);
     for (size_t i = 0; i < j.blocks.size(); i++) {
       const avr::PbBlock& b = j.blocks[i];
       const int k = j.desc_of_block[i];
+      h->unit_first[i] = (int)h->units.size();
       if (!b.has_cabac || k == -1) continue;
       const int s = (int)slices.size();
       const size_t u0 = h->units.size();
@@ -365,6 +547,7 @@ int avr_dec_plan_load_pieces(avr_dec_plan* h, const uint8_t* avrc, size_t n, int
       if (k >= 0) {
         sd = h->plan.descs[k];
         unit(sd, b.cabac, b.cabac_len, avr_piece{-1, 0, s, UINT32_MAX});
+        h->unit_q0.push_back(0);
       } else {
         const SplitBlock& x = j.splits[-2 - k];
         sd = sp.plan.descs[x.first];
@@ -378,6 +561,7 @@ int avr_dec_plan_load_pieces(avr_dec_plan* h, const uint8_t* avrc, size_t n, int
           // the plan's records say where their piece's bytes start in the slice (the kernels do not read it)
           if (pc.seam >= 0) ((avr::SeamRec*)(sp.recs.data() + (size_t)pc.seam * sp.stride))->q = x.q[p - 1];
           unit(pd, b.cabac + off, pd.payload_size, avr_piece{pc.seam, pc.n_mbs, s, keep});
+          h->unit_q0.push_back(p ? x.q[p - 1] : 0u);
           off += pd.payload_size;
         }
       }
@@ -386,6 +570,8 @@ int avr_dec_plan_load_pieces(avr_dec_plan* h, const uint8_t* avrc, size_t n, int
       j.desc_of_block[i] = s;
       slices.push_back(sd);
     }
+    h->unit_first[j.blocks.size()] = (int)h->units.size();
+    map_blocks(h);
     j.splits.clear();
     h->plan.descs = std::move(slices);
     h->plan.arena_copies = std::move(copies);

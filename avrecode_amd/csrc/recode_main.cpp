@@ -1,4 +1,7 @@
 // recode CLI (recode.cpp:1627-1659): recode [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] <input> [output]
+//                                    recode read <in.avrc> <offset> <length> [output]
+//   read  a byte range of the file a container restores (avr_reader_*): only the slices and pieces the
+//         range touches are regenerated where the container allows it; the range is clamped to the file.
 //   -p    parallel model (fresh model per slice; slices independent) on the reference's
 //         arithmetic_code<uint64_t, uint8_t>; default = reference model.
 //   -p32  parallel model on the optional 32-bit P32 coder (avrecode-amd:P32 containers).
@@ -9,6 +12,7 @@
 //         (avr_set_split_p32; avrecode-amd:P32S / P32SE containers).
 //   -k    compress and roundtrip, any model: a checked container -- the file's CRC-32 in its Metadata
 //         (avr_set_checksums); decompress checks the field wherever it finds it.
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,12 +45,68 @@ static void print_bill(const char* title, const uint64_t* b) {
   }
 }
 
+// a non-negative decimal number and nothing else
+static bool parse_u64(const char* s, uint64_t* v) {
+  if (!*s || *s < '0' || *s > '9') return false;
+  char* end = nullptr;
+  errno = 0;
+  *v = strtoull(s, &end, 10);
+  return errno == 0 && *end == 0;
+}
+
+// recode read <in.avrc> <offset> <length> [output]
+static int read_range(int argc, char** argv) {
+  uint64_t off = 0, len = 0;
+  if (argc < 5 || argc > 6 || !parse_u64(argv[3], &off) || !parse_u64(argv[4], &len) || off + len < off) {
+    std::cerr << "Usage: " << argv[0] << " read <in.avrc> <offset> <length> [output]" << std::endl;
+    return 1;
+  }
+  std::vector<uint8_t> in;
+  if (!read_file(argv[2], &in)) {
+    std::cerr << "Failed to open file: " << argv[2] << std::endl;
+    return 1;
+  }
+  avr_ctx* ctx = nullptr;
+  if (avr_create(0, &ctx) != AVR_OK) {
+    std::cerr << "No usable MI355X / HIP device" << std::endl;
+    return 1;
+  }
+  avr_reader* rd = nullptr;
+  avr_reader_info_t info;
+  int r = avr_reader_open(ctx, in.data(), in.size(), &rd);
+  if (r == AVR_OK) r = avr_reader_info(rd, &info);
+  std::vector<uint8_t> out;
+  size_t got = 0;
+  if (r == AVR_OK) {
+    const uint64_t o = off < info.file_size ? off : info.file_size;
+    out.resize((size_t)(len < info.file_size - o ? len : info.file_size - o));
+    r = avr_reader_read(rd, off, out.size(), out.data(), &got);
+  }
+  if (r != AVR_OK) {
+    std::cerr << "Exception: " << avr_last_error(ctx) << " (" << r << ")" << std::endl;
+    avr_reader_close(rd);
+    avr_destroy(ctx);
+    return 1;
+  }
+  if (argc == 6) {
+    std::ofstream f(argv[5], std::ios::binary);
+    f.write((const char*)out.data(), (std::streamsize)got);
+  } else {
+    fwrite(out.data(), 1, got, stdout);
+  }
+  avr_reader_close(rd);
+  avr_destroy(ctx);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::cerr << "Usage: " << argv[0] << " [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] <input> [output]" << std::endl;
+    std::cerr << "Usage: " << argv[0] << " [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] <input> [output]\n"
+              << "       " << argv[0] << " read <in.avrc> <offset> <length> [output]" << std::endl;
     return 1;
   }
   std::string cmd = argv[1];
+  if (cmd == "read") return read_range(argc, argv);
   int a = 2, model = AVR_MODEL_REFERENCE;
   bool escaped = false, split32 = false, checks = false;
   for (; a < argc; a++) {   // the model, -e, -s and -k, in any order

@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define AVRECODE_ABI_VERSION 11 /* 11: checked containers, opt-in (avr_set_checksums, Metadata field 16, AVR_ERR_CHECKSUM,
+#define AVRECODE_ABI_VERSION 12 /* 12: range reads (avr_reader_*, avr_dec_plan_file_size, avr_dec_plan_range(_apply),
+                                 *    avr_gather_spans, avr_range_tails);
+                                 * 11: checked containers, opt-in (avr_set_checksums, Metadata field 16, AVR_ERR_CHECKSUM,
                                  *    avr_crc_spans, avr_crc32(_combine), avr_assemble_container_args, avr_dec_plan_splice_crc);
                                  * 10: the long-slice split on the P32 coder, opt-in (avr_set_split_p32, the "P32S" / "P32SE"
                                  *    tags, avr_compress_split_slices_m, avr_decompress_pieces_m, AVR_ASSEMBLE_SPLIT32);
@@ -691,6 +693,145 @@ int avr_stage_pieces(avr_ctx* ctx, avr_slice_desc* d_desc, const uint64_t* d_src
 int avr_verify_units(avr_ctx* ctx, const avr_slice_desc* d_desc, const avr_slice_result* d_res_c, int n,
                      const uint32_t* d_first, int n_units, const uint8_t* d_in, const uint8_t* d_packed, const uint64_t* d_offsets,
                      const uint32_t* d_kept, const int32_t* d_unit_status, int32_t* d_verdict, void* stream);
+
+/* ------------------------------------------------------------------ range reads (ABI 12)
+ * An opened container serves byte ranges of its file.  In the parallel models' containers every coded
+ * slice -- and every piece of a cut slice -- is independent, so a window of the file needs only the
+ * units whose bytes it touches.  No reference counterpart (decompressor::run regenerates the whole
+ * file, recode.cpp:1312-1357).
+ *
+ * File coordinates come from the container alone: a literal block stands for its length, a coded block
+ * for `size` bytes, a skip_coded block for none; the prefix sum over the blocks places every block and
+ * gives the file's size.  Inside a cut block piece i covers slice bytes [q[i-1], q[i]) (q[-1] = 0, the
+ * last piece to `size`).
+ *
+ * avr_dec_plan_file_size: the size of the file a loaded plan (either load) restores.
+ * avr_dec_plan_range (a piece plan, avr_dec_plan_load_pieces; host only): the window [off, off + len)
+ * clamped to the file, as
+ *   - info: the clamped window, the units [unit_lo, unit_hi) whose bytes it touches (units of blocks
+ *     that only border it are not selected; an empty window selects none), the counts;
+ *   - *spans (n_spans; malloc'd, avr_free): the copies that lay the window out, in window order and
+ *     without gap or overlap.  source = AVR_SPAN_LITERAL: src_off indexes the container's bytes;
+ *     source = k >= 0: src_off indexes the regenerated bytes of unit unit_lo + k.  No span is longer
+ *     than span_cap bytes (0: the library's 16384; otherwise 16 .. 2^30), so one long slice spreads
+ *     over many workgroups of avr_gather_spans;
+ *   - *tails (unit_hi - unit_lo; malloc'd): what must hold of each selected unit's result, and for the
+ *     unit that ends a slice the last-byte rule (recode.cpp:1345-1356).  A piece that is not its
+ *     slice's last (keep != UINT32_MAX) must have regenerated at least keep bytes.  A last piece or a
+ *     whole slice must make the slice's regenerated total T = q_last + out_len restore exactly `size`
+ *     bytes: with the rule (has_rule) T = size when T's parity is length_parity (the final byte is
+ *     replaced by last_byte) or T = size - 1 when it differs (last_byte is appended); without it
+ *     T = size.  final_pos = where the slice's final byte stands in the window, AVR_RANGE_NO_POS when
+ *     it lies outside.  The unit holding a slice's final byte is always its last unit, also when that
+ *     byte is the appended one: the rule is decided by the regenerated length, so that unit is
+ *     decoded (its span then copies one byte of slack from the unit's output space, which the tail
+ *     overwrites).
+ * This length check is stricter than the whole-file splice, which keeps the reference's rule and never
+ * compares a regenerated length with `size`: a range read's coordinates are the container's sizes, so
+ * a touched slice whose length contradicts its block fails the read (AVR_SLICE_NO_END in its status,
+ * AVR_ERR_FORMAT from the call).
+ * AVR_ERR_UNSUPPORTED for a container with escaped blocks (Block field 17: such a block's file bytes
+ * are not a crop of its regenerated bytes), AVR_ERR_FORMAT for a touched coded block without a unit
+ * or cuts that do not ascend inside `size`, AVR_ERR_INVALID_ARGUMENT for a plan that is not a piece
+ * plan, off + len overflowing or span_cap out of range.  Every index and length emitted is checked.
+ * avr_dec_plan_range_apply (host only): the spans and tails applied to host buffers -- what
+ * avr_gather_spans and avr_range_tails do on the device.  Unit unit_lo + k's regenerated bytes stand
+ * at regen + unit_off[k], its result in res[k]; avrc = the container (literal spans).  status[k]
+ * (n_units) = the unit's own status when non-zero, AVR_SLICE_NO_END for a short piece or a slice of
+ * the wrong length, else 0.  AVR_OK when every status is 0, else AVR_ERR_FORMAT;
+ * AVR_ERR_INVALID_ARGUMENT, before anything is written, when a span or a final_pos does not lie
+ * inside its buffers.  Nothing is written outside out[0, out_len). */
+enum { AVR_SPAN_LITERAL = -1 };
+#define AVR_RANGE_NO_POS UINT64_MAX
+typedef struct {
+  uint64_t src_off;   /* in the container's bytes (literal) or the source unit's regenerated bytes;
+                       * avr_gather_spans: in d_src */
+  uint64_t dst_off;   /* in the window */
+  uint32_t len;
+  int32_t source;     /* AVR_SPAN_LITERAL, or the unit's index among the selected ones (avr_gather_spans ignores it) */
+} avr_span;
+typedef struct {
+  uint32_t keep;            /* a piece that is not its slice's last: the bytes it must have regenerated; else UINT32_MAX */
+  uint32_t q_last;          /* a last piece / whole slice: the slice's bytes before this unit */
+  uint32_t size;            /* the block's size */
+  uint8_t has_rule, length_parity, last_byte, reserved;
+  uint64_t final_pos;       /* window position of the slice's final byte; AVR_RANGE_NO_POS */
+} avr_range_tail;
+typedef struct {
+  uint64_t off, len;        /* the window, clamped to the file */
+  uint64_t file_size, literal_bytes;
+  int32_t unit_lo, unit_hi, n_spans, reserved;
+} avr_range_info;
+int avr_dec_plan_file_size(const avr_dec_plan* plan, uint64_t* size);
+int avr_dec_plan_range(const avr_dec_plan* plan, uint64_t off, uint64_t len, uint32_t span_cap, avr_range_info* info,
+                       avr_span** spans, avr_range_tail** tails);
+int avr_dec_plan_range_apply(const avr_span* spans, int n_spans, const avr_range_tail* tails, int n_units,
+                             const uint8_t* avrc, size_t avrc_len, const uint8_t* regen, size_t regen_len,
+                             const uint64_t* unit_off, const avr_slice_result* res, uint8_t* out, size_t out_len,
+                             int32_t* status);
+/* The two device steps (all pointers device pointers, `stream` a hipStream_t, nothing synchronised;
+ * n <= 0 launches nothing).
+ * avr_gather_spans: one workgroup per span copies d_spans[k].len bytes from d_src + src_off to
+ * d_dst + dst_off, any alignment on either side.  d_status[k] = 0, or AVR_SLICE_OVERFLOW for a span
+ * that does not lie inside src_len or dst_len (checked on the device; nothing of it is read or
+ * written).  Spans of one launch must not overlap in the destination (the kernel's memory safety does
+ * not rely on it).
+ * avr_range_tails: after the gather on the same stream, one thread per selected unit reads d_res[k],
+ * applies d_tails[k] (above) and writes d_status[k]; for the unit that ends a slice, when the rule
+ * replaces or appends and final_pos is inside dst_len, it stores last_byte at d_dst + final_pos
+ * (AVR_SLICE_OVERFLOW for a final_pos outside). */
+int avr_gather_spans(avr_ctx* ctx, const avr_span* d_spans, int n, const uint8_t* d_src, size_t src_len, uint8_t* d_dst,
+                     size_t dst_len, int32_t* d_status, void* stream);
+int avr_range_tails(avr_ctx* ctx, const avr_range_tail* d_tails, const avr_slice_result* d_res, int n, uint8_t* d_dst,
+                    size_t dst_len, int32_t* d_status, void* stream);
+
+/* The reader: pread on an opened container.  avrc must stay valid and unchanged until avr_reader_close;
+ * one reader belongs to one context (and its host thread); it owns its device buffers, reuses them
+ * across reads and shares none with the whole-file calls, so other calls on the context may come
+ * between two reads.  Both reads synchronise before they return.
+ * Random-access containers (info.random_access = 1): "avrecode-amd:P64" with or without seams,
+ * "P32" and "P32S".  open loads the piece plan once and uploads the seam records once; nothing
+ * proportional to the file is reserved.  A read plans its window (avr_dec_plan_range), writes the
+ * selected units' streams -- re-placed compactly, 16-byte aligned, >= 16 zero bytes after each -- and
+ * the window's literal bytes into one pinned staging buffer, uploads it, regenerates the units on the
+ * context's stream (pieces through avr_decompress_pieces_m's path, whole slices -- field and MBAFF
+ * ones included -- through avr_decompress_slices', one launch after the other), gathers the window
+ * (avr_gather_spans), runs the tails (avr_range_tails), downloads the statuses and only then the
+ * bytes.  A selected unit with a non-zero status fails the read with AVR_ERR_FORMAT
+ * (avr_last_error on the context); `out` is then untouched (d_out: unspecified).
+ * Everything else (info.random_access = 0: reference and chained models, every "E" tag -- an escaped
+ * block's bytes are not a crop of its regenerated bytes): the first read regenerates the whole file
+ * once through avr_decompress_file (so a checked container is checked: AVR_ERR_CHECKSUM), the reader
+ * keeps it in host memory and serves every read from there.
+ * Checked containers: a partial read cannot verify a file CRC.  info.checked says that field 16 is
+ * present; random-access reads are guarded by the per-unit statuses and the strict length check
+ * (above), not by field 16.
+ * pread semantics: the window is clamped to the file; *got = 0 with AVR_OK at or past the end and for
+ * len = 0 (nothing is launched); off + len overflowing is AVR_ERR_INVALID_ARGUMENT.
+ * avr_reader_span: [*lo, *hi) = the file bytes of the block holding off, *coded = 1 for a coded block
+ * (a caller that chunks on these boundaries never regenerates a boundary slice twice);
+ * AVR_ERR_INVALID_ARGUMENT at or past the end.
+ * avr_reader_last: what the last successful read did. */
+typedef struct avr_reader avr_reader;
+typedef struct {
+  uint64_t file_size;
+  int32_t model;           /* AVR_MODEL_* */
+  int32_t random_access;
+  int32_t n_blocks, n_units;   /* n_units: 0 without random access */
+  int32_t checked, reserved;
+} avr_reader_info_t;
+typedef struct {
+  uint64_t units, pieces;      /* units regenerated; those among them that are pieces of cut slices */
+  uint64_t regenerated_bytes, literal_bytes, spans;
+  avr_phase_times phases;      /* of the read: demux_s = planning and staging */
+} avr_read_stats;
+int avr_reader_open(avr_ctx* ctx, const uint8_t* avrc, size_t n, avr_reader** out);
+int avr_reader_info(const avr_reader* r, avr_reader_info_t* info);
+int avr_reader_read(avr_reader* r, uint64_t off, size_t len, uint8_t* out, size_t* got);
+int avr_reader_read_device(avr_reader* r, uint64_t off, size_t len, uint8_t* d_out, size_t* got);
+int avr_reader_span(const avr_reader* r, uint64_t off, uint64_t* lo, uint64_t* hi, int* coded);
+int avr_reader_last(const avr_reader* r, avr_read_stats* out);
+void avr_reader_close(avr_reader* r);
 
 /* Container codec check (host only): parse a Recoded protobuf (recode.proto:1-19) with the
  * library's own wire codec -- the one avr_decompress_file uses -- and return (a) its fields as JSON,
