@@ -242,6 +242,15 @@ typedef struct {
 /* 1024 CABAC context bytes (FFmpeg's sl->cabac_state).  Returns 0 on success (end_of_slice   */
 /* reached at a legal MB), <0 on a syntax error / unsupported syntax / overrun.               */
 int avr_walk_slice(const avr_slice_hdr_t *h, const avr_hooks_t *hooks, int picture_id);
+/* What the walker is reading when it calls a cabac hook (the author answers bins by these): the
+ * syntax element, the bin's index in it (the binary part of an exp-Golomb suffix: 100), for SE_REF the
+ * largest legal value, the macroblocks finished, and at SE_EOS whether the picture's last one is. */
+enum {
+  SE_SKIP = 1, SE_MBTYPE, SE_SUBMBTYPE, SE_T8X8, SE_PREVINTRA, SE_REMINTRA, SE_CHROMAPRED, SE_REF,
+  SE_MVD_PREFIX, SE_MVD_SUFFIX, SE_CBP, SE_QPDELTA, SE_CBF, SE_SIG, SE_LAST, SE_LEVEL_PREFIX,
+  SE_LEVEL_SUFFIX, SE_SIGN, SE_EOS, SE_PCM_FLAG, SE_FIELD
+};
+extern int avr_walk_se, avr_walk_se_bin, avr_walk_se_limit, avr_walk_mbs_done, avr_walk_last_mb;
 /* One piece of a split slice (avr_seam_t): the walk from start_mb (a row start) for n_mbs
  * macroblocks (0: to end_of_slice), the CABAC contexts, the upper row and last_dqp_nz from the
  * seam (edge == NULL: the slice's own start).  Returns 1 when it stopped after n_mbs. */
@@ -363,6 +372,54 @@ int avr_decompress_piece(const avr_slice_hdr_t *h, int picture_id, const uint8_t
                          int n_mbs, obuf_t *out);
 /* every split slice of a file (split_bytes) decompressed piece by piece and compared (oracle_recode.c) */
 int avr_check_pieces(const uint8_t *file, size_t n, size_t split_bytes, int *n_split, int *n_pieces);
+
+/* ------------------------------------------------------------------------------------------ */
+/* The author (oracle_author.c): H.264 streams written by this library for the tests.  It writes  */
+/* SPS, PPS and slice headers itself (ITU-T H.264 7.3.2.1.1, 7.3.2.2, 7.3.3) and fills each slice */
+/* by running avr_walk_slice with hooks that ANSWER every bin from a seeded policy and feed it to   */
+/* the CABAC re-encoder: a syntactically valid slice whose statistics the caller chooses, without   */
+/* the caps of the device generator (avr_synthesize_stream).  Same parameters, same bytes.          */
+enum { AVR_AUTHOR_LEVELS = 0, AVR_AUTHOR_MOTION, AVR_AUTHOR_SPARSE, AVR_AUTHOR_MIXED, AVR_AUTHOR_FORCED };
+enum { AVR_FORCE_LEVEL = 0, AVR_FORCE_MVD, AVR_FORCE_QPDELTA, AVR_FORCE_REF };
+#define AVR_AUTHOR_MAX_SLICES 256
+#define AVR_AUTHOR_MAX_FORCED 8
+typedef struct {
+  int32_t slice, element, nth, length;   /* the nth (0-based) such element of that slice gets this length */
+} avr_author_force_t;
+typedef struct {
+  int32_t mb_width, mb_height;           /* frame size in macroblocks (height even unless progressive) */
+  int32_t chroma_format_idc, transform_8x8_mode;
+  int32_t structure;                     /* 0 progressive, 1 PAFF top field first, 2 MBAFF, 3 PAFF bottom first */
+  int32_t num_ref_idx;                   /* both lists, 1..32 */
+  int32_t pictures, slices_per_picture;
+  int32_t with_i;                        /* 1: pictures cycle I, P, B; 0: one I picture, then P, B, P, ... */
+  int32_t profile;                       /* AVR_AUTHOR_* */
+  int32_t kmax_level, kmax_mvd;          /* longest unary prefix of a level / mvd escape's suffix drawn */
+  int32_t n_qp, qp[8], n_idc, idc[4];    /* slice_qp / cabac_init_idc values, cycled per slice */
+  int32_t n_forced;
+  avr_author_force_t forced[AVR_AUTHOR_MAX_FORCED];
+  uint64_t seed;
+} avr_author_params_t;
+typedef struct {
+  int32_t slice_type, slice_qp, cabac_init_idc, first_mb, structure;   /* as avr_slice_hdr_t; structure:
+                                           0 frame, 1 top field, 2 bottom field, 3 MBAFF frame */
+  int32_t refused;                       /* the walk stopped at a bound: flushed and padded */
+  uint32_t payload_bytes, bins;
+} avr_author_slice_t;
+typedef struct {
+  uint32_t slices, refused_slices, mbs, skipped_mbs, payload_bytes, emulation_bytes;
+  uint64_t bins;
+  uint32_t level_escapes, level_len[32];   /* by the suffix's unary prefix length, 0..31 */
+  uint32_t mvd_escapes, mvd_k[32];         /* by k, the suffix's exp-Golomb order reached, 3..25 */
+  uint32_t qp_delta_len[104];              /* by unary length, 0..103 */
+  uint32_t ref_idx[33];                    /* by value, 0..32 */
+  uint32_t idc_used[2][3];                 /* [P, B][cabac_init_idc] slices */
+  uint32_t qp_used[52];
+  avr_author_slice_t slice[AVR_AUTHOR_MAX_SLICES];
+} avr_author_census_t;
+/* 0 and *out (malloc'd Annex-B stream); <0: bad parameters, a header that does not parse back to
+ * where the author put slice_data(), or a walk that failed where none was forced */
+int avr_author_stream(const avr_author_params_t *p, uint8_t **out, size_t *len, avr_author_census_t *census);
 
 /* protobuf wire codec for recode.proto */
 typedef struct {

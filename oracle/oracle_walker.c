@@ -24,12 +24,6 @@
 
 int avr_walk_se, avr_walk_se_bin, avr_walk_se_limit, avr_walk_mbs_done, avr_walk_last_mb;
 
-enum {
-  SE_SKIP = 1, SE_MBTYPE, SE_SUBMBTYPE, SE_T8X8, SE_PREVINTRA, SE_REMINTRA, SE_CHROMAPRED, SE_REF,
-  SE_MVD_PREFIX, SE_MVD_SUFFIX, SE_CBP, SE_QPDELTA, SE_CBF, SE_SIG, SE_LAST, SE_LEVEL_PREFIX,
-  SE_LEVEL_SUFFIX, SE_SIGN, SE_EOS, SE_PCM_FLAG, SE_FIELD
-};
-
 /* scan8 (recode.cpp:263-277 == FFmpeg h264dec.h scan8) */
 static const uint8_t scan8[51] = {
   4 + 1 * 8,  5 + 1 * 8,  4 + 2 * 8,  5 + 2 * 8,  6 + 1 * 8,  7 + 1 * 8,  6 + 2 * 8,  7 + 2 * 8,
