@@ -27,6 +27,7 @@ __all__ = [
     "seams_of_container", "SPLIT_SLOT", "SplitPlan", "split_plan", "seams_build", "escape_payload",
     "ASSEMBLE_ESCAPED", "ASSEMBLE_SPLIT32", "ASSEMBLE_CRC", "ERR_CHECKSUM", "crc32", "crc32_combine",
     "file_crc_of_container", "Reader", "SPAN", "RANGE_TAIL", "SPAN_LITERAL", "RANGE_NO_POS", "RANGE_SPAN_BYTES",
+    "ASSEMBLE_UNIT_CRC", "UNIT_CHECK", "SLICE_CHECKSUM", "unit_checks_apply",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,6 +44,7 @@ CHAIN_SLICES = 16
 ASSEMBLE_ESCAPED = 1   # avr_assemble_container_opts' flag: the second search of Context.recode_escaped
 ASSEMBLE_SPLIT32 = 2   # and: seams fields for MODEL_PARALLEL32, under the "P32S" / "P32SE" tags (Context.split_p32)
 ASSEMBLE_CRC = 4       # and: a checked container, the file's CRC-32 in Metadata field 16 (Context.checksums)
+ASSEMBLE_UNIT_CRC = 16  # and: unit checksums, a CRC-32 per slice / piece in Block field 18 (Context.unit_checksums)
 ERR_CHECKSUM = -7      # AVR_ERR_CHECKSUM: the container decoded, and its file is not the file it was made from
 SPLIT_BYTES_DEFAULT = 98304   # the parallel model's long-slice split (Context.split_bytes), unless AVR_SPLIT_BYTES
 MODEL_NAMES = {MODEL_REFERENCE: "R", MODEL_PARALLEL: "P", MODEL_PARALLEL32: "P32", MODEL_CHAINED: "C"}
@@ -77,6 +79,8 @@ EXPORTED_SYMBOLS = (
     "avr_dec_plan_file_size", "avr_dec_plan_range", "avr_dec_plan_range_apply", "avr_gather_spans", "avr_range_tails",
     "avr_reader_open", "avr_reader_info", "avr_reader_read", "avr_reader_read_device", "avr_reader_span",
     "avr_reader_last", "avr_reader_close",
+    "avr_set_unit_checksums", "avr_get_unit_checksums", "avr_check_units", "avr_unit_checks_apply",
+    "avr_dec_plan_unit_crcs",
 )
 
 # avr_slice_desc / avr_slice_result (include/avrecode.h), C layout
@@ -100,11 +104,14 @@ KEEP_ALL = 0xFFFFFFFF    # avr_piece.keep of a last piece or a whole slice
 SLICE_NO_END = -9        # AVR_SLICE_NO_END
 SLICE_CODER = -10        # AVR_SLICE_CODER
 SLICE_OVERFLOW = -12     # AVR_SLICE_OVERFLOW
+SLICE_CHECKSUM = -22     # AVR_SLICE_CHECKSUM: a unit's regenerated bytes miss its CRC (Block field 18)
 # avr_split_slot (include/avrecode.h): a slice's cut records in a split compress batch; (-1, 0): none
 # avr_span / avr_range_tail (range reads, ABI 12)
 SPAN = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("len", "<u4"), ("source", "<i4")], align=True)
 RANGE_TAIL = np.dtype([("keep", "<u4"), ("q_last", "<u4"), ("size", "<u4"), ("has_rule", "u1"), ("length_parity", "u1"),
                        ("last_byte", "u1"), ("reserved", "u1"), ("final_pos", "<u8")], align=True)
+# avr_unit_check (unit checksums, ABI 13): where a unit's regenerated bytes start, its CRC, whether it has one
+UNIT_CHECK = np.dtype([("src_off", "<u8"), ("crc", "<u4"), ("have", "<u4")], align=True)
 SPAN_LITERAL = -1               # avr_span.source of a literal: src_off indexes the container
 RANGE_NO_POS = 0xFFFFFFFFFFFFFFFF   # avr_range_tail.final_pos: the slice's final byte lies outside the window
 RANGE_SPAN_BYTES = 16384        # the planner's default span cap
@@ -152,7 +159,7 @@ class _RangeInfo(ctypes.Structure):   # avr_range_info
 class _ReaderInfo(ctypes.Structure):   # avr_reader_info_t
     _fields_ = [("file_size", ctypes.c_uint64), ("model", ctypes.c_int32), ("random_access", ctypes.c_int32),
                 ("n_blocks", ctypes.c_int32), ("n_units", ctypes.c_int32), ("checked", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("unit_checked", ctypes.c_int32)]
 
 
 class _ReadStats(ctypes.Structure):   # avr_read_stats
@@ -317,6 +324,11 @@ def lib() -> ctypes.CDLL:
     L.avr_reader_last.argtypes = [vp, ctypes.POINTER(_ReadStats)]
     L.avr_reader_close.argtypes = [vp]
     L.avr_reader_close.restype = None
+    L.avr_set_unit_checksums.argtypes = [vp, i32]
+    L.avr_get_unit_checksums.argtypes = [vp]
+    L.avr_check_units.argtypes = [vp, vp, vp, vp, i32, vp, sz, vp, vp]
+    L.avr_unit_checks_apply.argtypes = [vp, vp, vp, i32, vp, sz, vp]
+    L.avr_dec_plan_unit_crcs.argtypes = [vp, i32, i32, vp]
     for name in EXPORTED_SYMBOLS:   # fails here, not at first use, when the build is stale
         getattr(L, name)
     _lib = L
@@ -609,6 +621,16 @@ class DecompressPlan:
             raise e
         return out[:rng["len"]].tobytes(), st[:nu]
 
+    def unit_crcs(self, unit_lo: int, unit_hi: int) -> np.ndarray:
+        """UNIT_CHECK[unit_hi - unit_lo] of a piece plan's units (avr_dec_plan_unit_crcs): crc / have from
+        their blocks' unit checksums (Block field 18; have = 0 without the field), src_off left 0 for
+        the caller."""
+        out = np.zeros(max(1, unit_hi - unit_lo), dtype=UNIT_CHECK)
+        r = lib().avr_dec_plan_unit_crcs(self._h, int(unit_lo), int(unit_hi), out.ctypes.data)
+        if r != AVR_OK:
+            raise AvrError(r, "avr_dec_plan_unit_crcs failed")
+        return out[:max(0, unit_hi - unit_lo)]
+
     def close(self):
         if self._h:
             lib().avr_dec_plan_free(self._h)
@@ -619,6 +641,25 @@ class DecompressPlan:
             self.close()
         except Exception:
             pass
+
+
+def unit_checks_apply(tails, checks, res, src, status=None) -> "tuple[int, np.ndarray]":
+    """avr_check_units on host buffers (avr_unit_checks_apply): unit k's share of its slice at
+    src[checks[k].src_off:], its SLICE_RESULT in res[k], its RANGE_TAIL in tails[k].  status: the units'
+    statuses so far (default all 0).  Returns (the call's return code -- 0, ERR_CHECKSUM when it set a
+    SLICE_CHECKSUM, format error when it set a SLICE_OVERFLOW -- and the statuses).  Host only."""
+    tl = np.ascontiguousarray(tails, dtype=RANGE_TAIL)
+    ck = np.ascontiguousarray(checks, dtype=UNIT_CHECK)
+    rs = np.ascontiguousarray(res, dtype=SLICE_RESULT)
+    n = len(tl)
+    if len(ck) != n or len(rs) != n:
+        raise ValueError("unit_checks_apply: one check and one result per tail")
+    st = np.zeros(max(1, n), dtype=np.int32)
+    if status is not None:
+        st[:n] = np.asarray(status, dtype=np.int32)
+    sp, sn, keep = _buf(src)
+    r = lib().avr_unit_checks_apply(tl.ctypes.data, ck.ctypes.data, rs.ctypes.data, n, sp, sn, st.ctypes.data)
+    return int(r), st[:n]
 
 
 def crc32(data, crc: int = 0) -> int:
@@ -732,7 +773,7 @@ def seams_build(descs, arena, res, slots, cuts, piece_end, recs, rec_stride: int
 def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, lens: np.ndarray,
                        model: int = MODEL_PARALLEL, ps: "ParsedStream | None" = None, as_array: bool = False,
                        out: "np.ndarray | None" = None, seams=None, escaped: bool = False, split32: bool = False,
-                       crcs=None, checksums: bool = False):
+                       crcs=None, checksums: bool = False, unit_checksums: bool = False):
     """Recoded container from per-slice outputs gathered from the ranks (avr_assemble_container; with ps =
     parse_stream(data) already in hand, avr_assemble_container_parsed: no second parse).  recoded:
     bytes or a uint8 array.  model: the model / coder the outputs were made with (PARALLEL, PARALLEL32,
@@ -752,22 +793,26 @@ def assemble_container(data, status: np.ndarray, recoded, offsets: np.ndarray, l
     checksums (ASSEMBLE_CRC; any model, not with out): a checked container, what ctx.compress writes
     with Context.checksums on (avr_assemble_container_args); crcs: the CRC-32 of every slice's payload
     as the ranks' devices computed them (read for coded slices; trusted), else the assembly computes
-    them on host threads.  Host only."""
+    them on host threads.
+    unit_checksums (ASSEMBLE_UNIT_CRC; the parallel models, not with out): Block field 18 on every coded
+    block, what ctx.compress writes with Context.unit_checksums on; the assembly computes the values on
+    host threads from the payloads and the seams' cuts.  Host only."""
     L = lib()
-    flags = (ASSEMBLE_ESCAPED if escaped else 0) | (ASSEMBLE_SPLIT32 if split32 else 0)
+    flags = (ASSEMBLE_ESCAPED if escaped else 0) | (ASSEMBLE_SPLIT32 if split32 else 0) | \
+        (ASSEMBLE_UNIT_CRC if unit_checksums else 0)
     if (flags or checksums) and out is not None:
-        raise ValueError("assemble_container: escaped / split32 / checksums cannot be combined with out")
+        raise ValueError("assemble_container: escaped / split32 / checksums / unit_checksums cannot be combined with out")
     p, n, keep = _buf(data)
     st = np.ascontiguousarray(status, dtype=np.int32)
     of = np.ascontiguousarray(offsets, dtype=np.uint64)
     ln = np.ascontiguousarray(lens, dtype=np.uint32)
     rp, rn, keep2 = _buf(recoded)
     res, olen = ctypes.c_void_p(), ctypes.c_size_t()
-    if checksums:
+    if checksums or unit_checksums:
         a = _AssembleArgs()
         a.size, a.file, a.n, a.model, a.n_slices = ctypes.sizeof(_AssembleArgs), p, n, model, len(st)
         a.status, a.recoded, a.recoded_len, a.offsets, a.lens = st.ctypes.data, rp, rn, of.ctypes.data, ln.ctypes.data
-        a.flags = flags | ASSEMBLE_CRC
+        a.flags = flags | (ASSEMBLE_CRC if checksums else 0)
         if len(of) != len(st) or len(ln) != len(st):
             raise ValueError("assemble_container: status / offsets / lens need one entry per slice")
         if ps is not None:
@@ -1059,6 +1104,30 @@ class Context:
     def checksums(self, on: bool):
         self._check(lib().avr_set_checksums(self._h, 1 if on else 0), "avr_set_checksums")
 
+    @property
+    def unit_checksums(self) -> bool:
+        """Unit checksums (avr_set_unit_checksums; default: AVR_UNIT_CHECKSUMS, else off): compress and
+        roundtrip of the parallel models write one CRC-32 per unit -- a whole coded slice, or each piece
+        of a cut one -- into Block field 18 (7 bytes per uncut block), from CRCs the device computes
+        over the payloads.  Reading needs no option: a Reader checks the units a read touches
+        (AvrError ERR_CHECKSUM naming the unit; reads that avoid it succeed), every whole-file
+        decompress each block."""
+        return bool(lib().avr_get_unit_checksums(self._h))
+
+    @unit_checksums.setter
+    def unit_checksums(self, on: bool):
+        self._check(lib().avr_set_unit_checksums(self._h, 1 if on else 0), "avr_set_unit_checksums")
+
+    def check_units(self, d_tails, d_checks, d_res, n, d_src, src_len, d_status, stream=None):
+        """avr_check_units: after range_tails on the same stream, unit k's share of its slice (RANGE_TAIL
+        and SLICE_RESULT rows) at d_src + d_checks[k].src_off (UNIT_CHECK rows) CRC'd by one workgroup,
+        the last-byte rule applied to the value, and compared with d_checks[k].crc: d_status[k] becomes
+        SLICE_CHECKSUM on a mismatch, SLICE_OVERFLOW for a span outside src_len; units with a non-zero
+        status or have = 0 are left alone."""
+        P = self._ptr
+        self._check(lib().avr_check_units(self._h, P(d_tails), P(d_checks), P(d_res), int(n), P(d_src), int(src_len),
+                                          P(d_status), self._stream(stream)), "check_units")
+
     def crc_spans(self, d_buf, buf_len, d_off, d_len, n, d_crc, d_status, stream=None):
         """d_crc[k] = the CRC-32 of d_buf[d_off[k] : d_off[k] + d_len[k]] (avr_crc_spans: one workgroup
         per span, device tensors, nothing synchronised); d_status[k] = SLICE_OVERFLOW for a span outside
@@ -1318,7 +1387,7 @@ class Reader:
         ctx._check(lib().avr_reader_open(ctx._h, p, n, ctypes.byref(self._h)), "avr_reader_open")
         i = _ReaderInfo()
         ctx._check(lib().avr_reader_info(self._h, ctypes.byref(i)), "avr_reader_info")
-        self.info = {f: int(getattr(i, f)) for f, _ in _ReaderInfo._fields_ if f != "reserved"}
+        self.info = {f: int(getattr(i, f)) for f, _ in _ReaderInfo._fields_}
         self.size = self.info["file_size"]
 
     def read(self, off: int, n: int) -> bytes:

@@ -336,6 +336,7 @@ struct SplitOut {
   std::vector<uint8_t> recoded, seams;   // seams empty: no cut
   avr_slice_result bill{};
   uint32_t crc = 0;   // SplitJob::crc: the payload's CRC-32
+  std::vector<uint32_t> unit_crcs;   // SplitJob::unit_crc: one per unit (Block field 18), the payload's own when uncut
 };
 struct SplitJob {
   std::vector<const avr::SliceInfo*> sl;
@@ -349,6 +350,7 @@ struct SplitJob {
   int max_w = 1;
   uint32_t coder = 0;   // coder_flag(model): the walk's and the verify launch's coder
   bool crc = false;     // a checked container: the payloads' CRCs too, over the uploaded arena
+  bool unit_crc = false;   // unit checksums (implies crc): the cut slices' units too, once the cuts are known
   EventPair ev;   // around the split compress kernel
 };
 
@@ -495,6 +497,49 @@ int split_finish(avr_ctx* c, SplitJob* j, bool verify, std::vector<SplitOut>* ou
     if (so.status) continue;
     so.recoded.assign(out1.begin() + j->d[k].out_offset, out1.begin() + j->d[k].out_offset + r1[k].out_len);
     so.seams.swap(ss[k].field);
+  }
+  // 2b) unit checksums: the units of the cut slices are known now -- one avr_crc_spans launch over the
+  //     payload arena, which still lies in sp_in (an uncut slice's one unit is its payload)
+  if (j->unit_crc) {
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+    for (int k = 0; k < n; k++) {
+      if ((*out)[k].status || ss[k].q.empty()) continue;
+      const uint32_t size = j->d[k].payload_size;
+      for (size_t u = 0; u <= ss[k].q.size(); u++) {
+        const uint32_t lo = u ? ss[k].q[u - 1] : 0u, hi = u < ss[k].q.size() ? ss[k].q[u] : size;
+        if (lo > hi || hi > size) return fail(c, AVR_ERR_DEVICE, "split: cuts that do not ascend inside the slice");
+        off.push_back(j->d[k].payload_offset + lo);
+        len.push_back(hi - lo);
+      }
+    }
+    const size_t N = off.size();
+    std::vector<uint32_t> got(2 * N);   // the values, then the statuses
+    if (N) {
+      if (N > (size_t)INT32_MAX) return fail(c, AVR_ERR_INVALID_ARGUMENT, "split: too many units");
+      HIP_TRY(c, c->sp_ucrc.reserve(20 * N));
+      uint64_t* d_off = c->sp_ucrc.as<uint64_t>();
+      uint32_t* d_len = (uint32_t*)(d_off + N);
+      uint32_t* d_crc = d_len + N;
+      HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), 8 * N, hipMemcpyHostToDevice, st));
+      HIP_TRY(c, hipMemcpyAsync(d_len, len.data(), 4 * N, hipMemcpyHostToDevice, st));
+      HIP_TRY(c, avr::launch_crc_spans(c->sp_in.as<uint8_t>(), j->arena.size(), d_off, d_len, (int)N, d_crc,
+                                       (int32_t*)(d_crc + N), st));
+      HIP_TRY(c, hipMemcpyAsync(got.data(), d_crc, 8 * N, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+    }
+    size_t at = 0;
+    for (int k = 0; k < n; k++) {
+      SplitOut& so = (*out)[k];
+      if (so.status) continue;
+      if (ss[k].q.empty()) {
+        so.unit_crcs.assign(1, so.crc);
+        continue;
+      }
+      for (size_t u = 0; u <= ss[k].q.size(); u++, at++)   // a span inside the arena is never refused
+        so.unit_crcs.push_back(got[N + at] == 0 ? got[at]
+                                                : avr_crc32(0, j->arena.data() + off[at], len[at]));
+    }
   }
   // 3) verify: the pieces decompressed from the records as a container gives them, spliced, compared
   Plan vp;
@@ -649,7 +694,11 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   // a checked container (avr_set_checksums): the candidates' payload CRCs from the device, where the
   // uploads put them; the reference models' pass re-plans, and its payloads are CRC'd by emit_container
   const bool checks = c->checksums;
-  sj.crc = checks;
+  // unit checksums (avr_set_unit_checksums): the parallel models' coded blocks carry their units' CRCs
+  // (Block field 18) -- an uncut slice's is that same payload CRC, a cut slice's units follow its cuts
+  const bool units = c->unit_checksums && parallel_model(model);
+  sj.crc = checks || units;
+  sj.unit_crc = units;
   SliceCrcs crcs_dev;
   if (parallel_model(model)) plan_candidates(pf, st, split_bytes, &plan, &sj.sl, &sj.d, &route);
   // 2) launch the split job's first pass on the split stream, then the batch beside it; collect
@@ -658,7 +707,8 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   pc.mark_demux();
   const uint32_t bill_flag = bills ? avr::kFlagBill : 0u;
   if (int r = split_begin(c, &sj, split_bytes, bill_flag)) return r;
-  if (int r = run_plan(c, 0, false, plan, &res, &outb, verify, bill_flag | coder_flag(model), checks ? &crcs_dev : nullptr)) {
+  if (int r = run_plan(c, 0, false, plan, &res, &outb, verify, bill_flag | coder_flag(model),
+                       checks || units ? &crcs_dev : nullptr)) {
     (void)hipStreamSynchronize(c->split_stream);   // its first pass still reads sj's buffers
     return r;
   }
@@ -692,6 +742,8 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
   for (int f = 0; f < nf; f++) seams_of[f].assign(pf[f].slices.size(), {nullptr, 0});
   std::vector<std::vector<uint32_t>> crc_of(nf);
   for (int f = 0; f < nf && checks && parallel_model(model); f++) crc_of[f].assign(pf[f].slices.size(), 0);
+  std::vector<std::vector<std::vector<uint32_t>>> ucrc_of(nf);
+  for (int f = 0; f < nf && units; f++) ucrc_of[f].resize(pf[f].slices.size());
   if (reference_model(model)) {
     if (int r = reference_pass(c, nf, in, in_len, model, pf, bills, st, ok, found, recoded)) return r;
   } else {
@@ -704,12 +756,16 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
           recoded[f][i].swap(x.recoded);
           seams_of[f][i] = {x.seams.data(), x.seams.size()};
           if (checks) crc_of[f][i] = x.crc;
+          if (units) ucrc_of[f][i] = x.unit_crcs;
           if (bills) add_bill(&(*bills)[f], x.bill);
           continue;
         }
-        if (checks)
-          crc_of[f][i] = crcs_dev.have(r.index) ? crcs_dev.crc[r.index]
-                                                : avr_crc32(0, pf[f].slices[i].payload(), pf[f].slices[i].size);
+        if (checks || units) {
+          const uint32_t crc = crcs_dev.have(r.index) ? crcs_dev.crc[r.index]
+                                                      : avr_crc32(0, pf[f].slices[i].payload(), pf[f].slices[i].size);
+          if (checks) crc_of[f][i] = crc;
+          if (units) ucrc_of[f][i].assign(1, crc);
+        }
         recoded[f][i].assign(outb.begin() + plan.descs[r.index].out_offset,
                              outb.begin() + plan.descs[r.index].out_offset + res[r.index].out_len);
         if (bills) add_bill(&(*bills)[f], res[r.index]);
@@ -723,7 +779,8 @@ int compress_files(avr_ctx* c, int nf, const uint8_t* const* in, const size_t* i
     for (size_t i = 0; i < pf[f].slices.size(); i++) blobs[i] = {recoded[f][i].data(), recoded[f][i].size()};
     st[f] = emit_container(in[f], in_len[f], views_of(pf[f]), found[f], blobs, model, &out[f], &out_len[f], nullptr, 0,
                            &seams_of[f], escaped ? &escapes[f] : nullptr,
-                           FileCrcArg{checks, crc_of[f].empty() ? nullptr : crc_of[f].data()});
+                           FileCrcArg{checks, crc_of[f].empty() ? nullptr : crc_of[f].data()},
+                           UnitCrcArg{units, units ? &ucrc_of[f] : nullptr});
   });
   for (int f = 0; f < nf; f++) {
     if (status) status[f] = st[f];
@@ -1160,6 +1217,7 @@ int avr_create(int device, avr_ctx** out) {
   if (const char* e = getenv("AVR_RECODE_ESCAPED")) c->recode_escaped = strtol(e, nullptr, 10) != 0;
   if (const char* e = getenv("AVR_SPLIT_P32")) c->split_p32 = strtol(e, nullptr, 10) != 0;
   if (const char* e = getenv("AVR_CHECKSUMS")) c->checksums = strtol(e, nullptr, 10) != 0;
+  if (const char* e = getenv("AVR_UNIT_CHECKSUMS")) c->unit_checksums = strtol(e, nullptr, 10) != 0;
   if (const char* e = getenv("AVR_FIELD_LANE"); !e || strcmp(e, "0") != 0) {
     if (hipStreamCreateWithFlags(&c->fld_stream, hipStreamNonBlocking) != hipSuccess) return AVR_ERR_DEVICE;
     for (auto& ev : c->fld_ev)
@@ -1214,6 +1272,13 @@ int avr_set_checksums(avr_ctx* c, int on) {
   return AVR_OK;
 }
 int avr_get_checksums(const avr_ctx* c) { return c && c->checksums; }
+
+int avr_set_unit_checksums(avr_ctx* c, int on) {
+  if (!c) return AVR_ERR_INVALID_ARGUMENT;
+  c->unit_checksums = on != 0;
+  return AVR_OK;
+}
+int avr_get_unit_checksums(const avr_ctx* c) { return c && c->unit_checksums; }
 
 void avr_free(void* p) { free(p); }
 
@@ -1689,6 +1754,16 @@ int avr_range_tails(avr_ctx* c, const avr_range_tail* d_tails, const avr_slice_r
   return AVR_OK;
 }
 
+int avr_check_units(avr_ctx* c, const avr_range_tail* d_tails, const avr_unit_check* d_checks, const avr_slice_result* d_res,
+                    int n, const uint8_t* d_src, size_t src_len, int32_t* d_status, void* stream) {
+  if (!c) return AVR_ERR_INVALID_ARGUMENT;
+  if (n <= 0) return AVR_OK;
+  if (!d_tails || !d_checks || !d_res || !d_src || !d_status) return AVR_ERR_INVALID_ARGUMENT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, avr::launch_check_units(d_tails, d_checks, d_res, n, d_src, src_len, d_status, (hipStream_t)stream));
+  return AVR_OK;
+}
+
 // One window of a random-access container (include/avrecode.h): planned on the host, then on the
 // context's stream the upload of what the window needs, the selected units regenerated -- the pieces
 // through avr_decompress_pieces_m, the whole slices through avr_decompress_slices, one launch after
@@ -1731,6 +1806,14 @@ static int reader_window(avr_reader* r, uint64_t off, size_t len, uint8_t* out, 
     r->descs[row[k]] = d;
     r->pieces[row[k]] = h->unit_pieces[lo + k];
     r->tails[row[k]] = r->rp.tails[k];
+  }
+  // the selected units' checksums (Block field 18), where their blocks carry them
+  bool any_check = false;
+  if (nu && !h->job.block_checked.empty()) {
+    r->rp_checks.resize(nu);
+    if (int e = avr_dec_plan_unit_crcs(h, lo, lo + nu, r->rp_checks.data()))
+      return fail(c, e, "avr_reader_read: the units' checksums cannot be read");
+    for (int k = 0; k < nu; k++) any_check |= r->rp_checks[k].have != 0;
   }
   const uint64_t upload = at + in.literal_bytes, work_base = (upload + 255) & ~(uint64_t)255;
   const uint64_t buf_len = work_base + work + 16;
@@ -1794,6 +1877,17 @@ static int reader_window(avr_reader* r, uint64_t off, size_t len, uint8_t* out, 
     if (int e = avr_decompress_slices(c, dd + np, nu - np, w_whole, mh, d_in, d_work, dr + np, model, st)) return e;
   HIP_TRY(c, avr::launch_gather_spans(r->d_spans.as<avr_span>(), nsp, d_in, buf_len, dst, in.len, d_st, st));
   HIP_TRY(c, avr::launch_range_tails(r->d_tails.as<avr_range_tail>(), dr, nu, dst, in.len, d_st + nsp, st));
+  if (any_check) {   // each unit's share of its slice where it was regenerated, against the container's value
+    r->checks.resize(nu);
+    for (int k = 0; k < nu; k++) {
+      r->checks[row[k]] = r->rp_checks[k];
+      r->checks[row[k]].src_off = work_base + r->descs[row[k]].out_offset;
+    }
+    HIP_TRY(c, r->d_checks.reserve(sizeof(avr_unit_check) * nu));
+    HIP_TRY(c, hipMemcpyAsync(r->d_checks.p, r->checks.data(), sizeof(avr_unit_check) * nu, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, avr::launch_check_units(r->d_tails.as<avr_range_tail>(), r->d_checks.as<avr_unit_check>(), dr, nu, d_in,
+                                       buf_len, d_st + nsp, st));
+  }
   HIP_TRY(c, hipEventRecord(r->ev[2], st));
   r->status.assign((size_t)nsp + nu, 0);
   r->res.assign(nu, avr_slice_result{});
@@ -1805,10 +1899,15 @@ static int reader_window(avr_reader* r, uint64_t off, size_t len, uint8_t* out, 
     if (r->status[k])
       return fail(c, AVR_ERR_FORMAT, "avr_reader_read: span " + std::to_string(k) + " lies outside its buffers");
   for (int k = 0; k < nu; k++)
-    if (int32_t s = r->status[nsp + row[k]])
+    if (int32_t s = r->status[nsp + row[k]]) {
+      if (s == AVR_SLICE_CHECKSUM)
+        return fail(c, AVR_ERR_CHECKSUM,
+                    "avr_reader_read: unit " + std::to_string(lo + k) +
+                        " of the container regenerated bytes that are not the ones its checksum was made from (CRC-32)");
       return fail(c, AVR_ERR_FORMAT,
                   "avr_reader_read: unit " + std::to_string(lo + k) + " of the container failed to decode (" +
                       std::to_string(s) + ")");
+    }
   if (!device) HIP_TRY(c, hipMemcpy(out, dst, in.len, hipMemcpyDeviceToHost));
   const double t3 = now_s();
   avr_read_stats& ls = r->last;
@@ -1888,6 +1987,12 @@ int avr_reader_open(avr_ctx* c, const uint8_t* avrc, size_t n, avr_reader** out)
     r->info.n_blocks = (int32_t)h->job.blocks.size();
     r->info.n_units = r->info.random_access ? nu : 0;
     r->info.checked = h->job.has_crc;
+    {   // every coded block carries unit checksums (Block field 18)
+      bool coded = false, all = true;
+      for (size_t i = 0; i < h->job.blocks.size(); i++)
+        if (h->job.blocks[i].has_cabac) coded = true, all = all && h->job.unit_checked(i);
+      r->info.unit_checked = coded && all;
+    }
     if (r->info.random_access) {
       for (auto& ev : r->ev) HIP_TRY(c, hipEventCreate(&ev));
       HIP_TRY(c, r->d_recs.reserve(std::max<size_t>(64, h->recs.size())));

@@ -160,10 +160,10 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
              const uint8_t* recoded, size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, uint8_t** out,
              size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0, const SeamsArg& sa = SeamsArg(),
              uint32_t flags = 0, const uint32_t* crcs = nullptr) {
-  // the escaped second chance is the parallel models' own format, the opt-in split the P32 coder's;
-  // the file's CRC is any model's
-  if ((flags & ~(uint32_t)(AVR_ASSEMBLE_ESCAPED | AVR_ASSEMBLE_SPLIT32 | AVR_ASSEMBLE_CRC)) ||
-      ((flags & AVR_ASSEMBLE_ESCAPED) && !parallel_model(model)) ||
+  // the escaped second chance and the unit checksums are the parallel models' own format, the opt-in
+  // split the P32 coder's; the file's CRC is any model's
+  if ((flags & ~(uint32_t)(AVR_ASSEMBLE_ESCAPED | AVR_ASSEMBLE_SPLIT32 | AVR_ASSEMBLE_CRC | AVR_ASSEMBLE_UNIT_CRC)) ||
+      ((flags & (AVR_ASSEMBLE_ESCAPED | AVR_ASSEMBLE_UNIT_CRC)) && !parallel_model(model)) ||
       ((flags & AVR_ASSEMBLE_SPLIT32) && model != AVR_MODEL_PARALLEL32))
     return AVR_ERR_INVALID_ARGUMENT;
   const bool seams_ok = model == AVR_MODEL_PARALLEL || (flags & AVR_ASSEMBLE_SPLIT32);
@@ -190,7 +190,8 @@ int assemble(const uint8_t* file, size_t n, int model, const std::vector<SliceVi
   const std::vector<const uint8_t*> found = segment(file, n, sv, ok, esc ? &escapes : nullptr);
   const double t1 = now_s();
   const int r = emit_container(file, n, sv, found, blobs, model, out, out_len, dst, cap, sa.p ? &fields : nullptr,
-                               esc ? &escapes : nullptr, FileCrcArg{(flags & AVR_ASSEMBLE_CRC) != 0, crcs});
+                               esc ? &escapes : nullptr, FileCrcArg{(flags & AVR_ASSEMBLE_CRC) != 0, crcs},
+                               UnitCrcArg{(flags & AVR_ASSEMBLE_UNIT_CRC) != 0, nullptr});
   if (getenv("AVR_ASM_TIMING")) fprintf(stderr, "assemble: segment %.3f s, emit %.3f s\n", t1 - t0, now_s() - t1);
   return r;
 }
@@ -331,6 +332,48 @@ std::vector<const uint8_t*> segment(const uint8_t* in, size_t n, const ParsedFil
   return segment(in, n, views_of(pf), ok, escapes);
 }
 
+namespace {
+// The unit values of every coded slice from its payload, on host threads: unit u of slice i covers
+// payload bytes [q[u - 1], q[u]) -- q from the slice's seams field, none for an uncut slice -- the last
+// to the payload's size.  AVR_ERR_INVALID_ARGUMENT for a seams field whose cuts cannot be read or do
+// not ascend inside the payload.
+int host_unit_crcs(const std::vector<SliceView>& sv, const std::vector<const uint8_t*>& found,
+                   const std::vector<std::pair<const uint8_t*, size_t>>* seams, std::vector<std::vector<uint32_t>>* out) {
+  struct Job {
+    size_t slice, unit;
+    const uint8_t* p;
+    size_t len;
+  };
+  std::vector<Job> jobs;
+  uint64_t bytes = 0;
+  out->assign(sv.size(), {});
+  std::vector<uint32_t> q;
+  for (size_t i = 0; i < sv.size(); i++) {
+    if (!found[i]) continue;
+    q.clear();
+    if (seams && (*seams)[i].second && !seams_cut_q((*seams)[i].first, (*seams)[i].second, &q)) return AVR_ERR_INVALID_ARGUMENT;
+    (*out)[i].assign(q.size() + 1, 0);
+    for (size_t u = 0; u <= q.size(); u++) {
+      const size_t lo = u ? q[u - 1] : 0, hi = u < q.size() ? q[u] : sv[i].size;
+      if (lo > hi || hi > sv[i].size) return AVR_ERR_INVALID_ARGUMENT;
+      jobs.push_back({i, u, sv[i].payload + lo, hi - lo});
+    }
+    bytes += sv[i].size;
+  }
+  const unsigned T = bytes < ((uint64_t)64 << 20) ? 1u : bulk_threads();
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (size_t k; (k = next.fetch_add(1)) < jobs.size();)
+      (*out)[jobs[k].slice][jobs[k].unit] = avr_crc32(0, jobs[k].p, jobs[k].len);
+  };
+  std::vector<std::thread> th;
+  for (unsigned t = 1; t < T; t++) th.emplace_back(work);
+  work();
+  for (auto& x : th) x.join();
+  return AVR_OK;
+}
+}  // namespace
+
 // compressor::run's block stream (recode.cpp:1115-1125, 1275-1297) as a Recoded protobuf, written
 // once: the blocks' headers in order, their bytes by parallel_copies, into the caller's buffer dst
 // (cap bytes; too small: AVR_ERR_INVALID_ARGUMENT with *out_len = the size needed) or, without one,
@@ -339,7 +382,13 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
                    const std::vector<std::pair<const uint8_t*, size_t>>& recoded, int model, uint8_t** out,
                    size_t* out_len, uint8_t* dst, size_t cap,
                    const std::vector<std::pair<const uint8_t*, size_t>>* seams, const std::vector<uint32_t>* escapes,
-                   const FileCrcArg& crc) {
+                   const FileCrcArg& crc, const UnitCrcArg& units) {
+  // unit checksums (Block field 18): per coded slice one value per unit, brought or computed here
+  std::vector<std::vector<uint32_t>> own_units;
+  if (units.on && !units.values) {
+    if (int r = host_unit_crcs(sv, found, seams, &own_units)) return r;
+  }
+  const std::vector<std::vector<uint32_t>>* unit_values = units.on ? (units.values ? units.values : &own_units) : nullptr;
   bool any_escapes = false, any_seams = false;
   std::vector<avr::PbBlock> blocks;
   blocks.reserve(2 * sv.size() + 1);
@@ -375,6 +424,11 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
       b.cabac_len = recoded[i].second;
       if (seams && (*seams)[i].second)
         b.has_seams = any_seams = true, b.seams = (*seams)[i].first, b.seams_len = (*seams)[i].second;
+      if (unit_values && i < unit_values->size() && !(*unit_values)[i].empty()) {
+        b.has_unit_crcs = true;
+        for (uint32_t v : (*unit_values)[i])
+          for (int k = 0; k < 4; k++) b.unit_crcs.push_back((char)(uint8_t)(v >> (8 * k)));
+      }
     } else {
       b.has_skip = true;
       b.skip_coded = true;
@@ -624,6 +678,14 @@ int avr_container_describe(const uint8_t* in, size_t n, char** json, uint8_t** r
     if (b.has_last_byte) add("\"last_byte\": \"" + hex((const uint8_t*)b.last_byte.data(), b.last_byte.size()) + "\"");
     if (b.has_seams) add("\"seams\": \"" + hex(b.seams, b.seams_len) + "\"");
     if (b.has_escapes) add("\"escapes\": " + std::to_string(b.escapes));
+    if (b.has_unit_crcs) {   // one value per unit: the cut block's count from its seams
+      std::vector<uint32_t> q;
+      if (b.has_seams && !seams_cut_q(b.seams, b.seams_len, &q)) return AVR_ERR_FORMAT;
+      if (b.unit_crcs.size() != 4 * (q.size() + 1)) return AVR_ERR_FORMAT;
+      std::string v;
+      for (size_t u = 0; u <= q.size(); u++) v += (u ? ", " : "") + std::to_string(b.unit_crc(u));
+      add("\"unit_crcs\": [" + v + "]");
+    }
     j += (i ? ", {" : "{") + e + "}";
     avr::pb_put_block(&o, b);
   }

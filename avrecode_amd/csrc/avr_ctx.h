@@ -59,6 +59,8 @@ struct avr_ctx : avr_host::ErrSink {
   bool recode_escaped = false;   // avr_set_recode_escaped / AVR_RECODE_ESCAPED (Block field 17)
   bool checksums = false;        // avr_set_checksums / AVR_CHECKSUMS (Metadata field 16: the file's CRC-32)
   DevBuf crc, sp_crc;            // per-slice CRCs, then their statuses: run_plan's batch, the split job's slices
+  bool unit_checksums = false;   // avr_set_unit_checksums / AVR_UNIT_CHECKSUMS (Block field 18: a CRC-32 per unit)
+  DevBuf sp_ucrc;                // the cut slices' unit spans (offsets, lengths), then their CRCs and statuses
   // avr_decompress_pieces: the batch's PieceCtl array, host (alive while its upload is in flight) and device
   std::vector<avr::PieceCtl> pc_host;
   DevBuf pc_ctl;
@@ -105,7 +107,8 @@ struct avr_reader {
   avr_reader_info_t info{};
   // one device buffer per read: the selected units' streams and the window's literal bytes (the
   // upload), then the units' output space; gather_spans' source is the whole of it
-  DevBuf buf, d_descs, d_res, d_spans, d_tails, d_status, d_recs, d_win;
+  DevBuf buf, d_descs, d_res, d_spans, d_tails, d_status, d_recs, d_win, d_checks;
+  std::vector<avr_unit_check> rp_checks, checks;   // a read's unit checks (Block field 18): in plan order, in launch-row order
   uint8_t* stage = nullptr;   // pinned: what a read uploads
   size_t stage_cap = 0;
   avr_host::RangePlan rp;

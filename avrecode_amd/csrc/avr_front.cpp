@@ -724,6 +724,7 @@ void pb_put_block(std::vector<uint8_t>* o, const PbBlock& b) {
   if (b.has_last_byte) bytes_field(&m, 6, (const uint8_t*)b.last_byte.data(), b.last_byte.size());
   if (b.has_seams) bytes_field(&m, 16, b.seams, b.seams_len);
   if (b.has_escapes) varint(&m, 17 << 3), varint(&m, b.escapes);
+  if (b.has_unit_crcs) bytes_field(&m, 18, (const uint8_t*)b.unit_crcs.data(), b.unit_crcs.size());
   bytes_field(o, 2, m.data(), m.size());
 }
 
@@ -744,6 +745,7 @@ size_t block_inner_size(const PbBlock& b) {
   if (b.has_last_byte) m += bytes_field_size(6, b.last_byte.size());
   if (b.has_seams) m += bytes_field_size(16, b.seams_len);
   if (b.has_escapes) m += varint_size(17 << 3) + varint_size(b.escapes);
+  if (b.has_unit_crcs) m += bytes_field_size(18, b.unit_crcs.size());
   return m;
 }
 size_t put_varint(uint8_t* o, size_t at, uint64_t v) {
@@ -777,6 +779,7 @@ size_t pb_write_block(uint8_t* o, size_t at, const PbBlock& b, std::vector<PbCop
   if (b.has_last_byte) at = put_bytes(o, at, 6, (const uint8_t*)b.last_byte.data(), b.last_byte.size(), nullptr);
   if (b.has_seams) at = put_bytes(o, at, 16, b.seams, b.seams_len, copies);
   if (b.has_escapes) at = put_varint(o, at, 17 << 3), at = put_varint(o, at, b.escapes);
+  if (b.has_unit_crcs) at = put_bytes(o, at, 18, (const uint8_t*)b.unit_crcs.data(), b.unit_crcs.size(), nullptr);
   return at;
 }
 
@@ -867,7 +870,12 @@ bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::st
       uint64_t t2, v;
       if (!rd_varint(&q, qe, &t2)) return false;
       const int f2 = (int)(t2 >> 3), w2 = (int)(t2 & 7);
-      if (w2 == 0 && (f2 == 1 || f2 == 3 || f2 == 5 || f2 == 17)) {
+      if (f2 == 18) {   // the unit CRCs: once, a length-delimited field of whole values
+        if (w2 != 2 || b.has_unit_crcs || !rd_varint(&q, qe, &v) || (uint64_t)(qe - q) < v || v == 0 || v % 4) return false;
+        b.has_unit_crcs = true;
+        b.unit_crcs.assign((const char*)q, v);
+        q += v;
+      } else if (w2 == 0 && (f2 == 1 || f2 == 3 || f2 == 5 || f2 == 17)) {
         if (!rd_varint(&q, qe, &v)) return false;
         if (f2 == 1) b.has_size = true, b.size = (int64_t)v;
         if (f2 == 3) b.has_skip = true, b.skip_coded = v != 0;
@@ -884,6 +892,7 @@ bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::st
         return false;
       }
     }
+    if (b.has_unit_crcs && (!b.has_cabac || (!b.has_seams && b.unit_crcs.size() != 4))) return false;
     blocks->push_back(b);
   }
   if (file_crc) *file_crc = fc;

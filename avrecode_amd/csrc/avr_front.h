@@ -121,6 +121,15 @@ struct PbBlock {
   // their meaning on the unescaped payload.  Only under the "E" tags below.
   bool has_escapes = false;
   uint64_t escapes = 0;
+  // field 18, this library's own: one little-endian CRC-32 per unit of a coded block (the whole slice,
+  // or each piece of a cut one) over the unit's share of the unescaped payload (include/avrecode.h,
+  // avr_set_unit_checksums).  Additive: a reader that does not know it skips it.
+  bool has_unit_crcs = false;
+  std::string unit_crcs;   // 4 bytes per unit
+  uint32_t unit_crc(size_t i) const {
+    const uint8_t* p = (const uint8_t*)unit_crcs.data() + 4 * i;
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+  }
 };
 void pb_put_block(std::vector<uint8_t>* o, const PbBlock& b);
 // The same bytes written into a buffer sized beforehand: pb_block_size(b) bytes at o + at (returns
@@ -144,7 +153,10 @@ struct PbFileCrc {
 };
 // Metadata with the version (null: none, the reference model's) and then the file's CRC
 void pb_put_metadata(std::vector<uint8_t>* o, const std::string* version, uint32_t file_crc);
-// false also for a second Metadata field 16, or one that is not a fixed32
+// false also for a second Metadata field 16, or one that is not a fixed32, and for a Block field 18
+// that occurs twice, has another wire type, stands on a block without cabac or whose length is not a
+// positive multiple of 4 (exactly 4 on a block without field 16; a cut block's count is checked where
+// its seams are decoded)
 bool pb_parse(const uint8_t* in, size_t n, std::vector<PbBlock>* blocks, std::string* version,
               bool* has_metadata = nullptr, PbFileCrc* file_crc = nullptr);
 // Recoded.Metadata.version only (empty without Metadata); false for bytes that are not a Recoded

@@ -434,13 +434,15 @@ int avr_hooks_compress_begin(avr_ctx* c, const uint8_t* file, size_t n, int mode
   uint8_t* avrc = nullptr;
   size_t avrc_len = 0;
   // a session's container never carries Block field 17: the callbacks serve the slices the plain
-  // segmentation codes; nor the file's CRC (Metadata field 16)
-  const int esc = avr_get_recode_escaped(c), chk = avr_get_checksums(c);
+  // segmentation codes; nor the file's CRC (Metadata field 16), nor unit checksums (Block field 18)
+  const int esc = avr_get_recode_escaped(c), chk = avr_get_checksums(c), uck = avr_get_unit_checksums(c);
   avr_set_recode_escaped(c, 0);
   avr_set_checksums(c, 0);
+  avr_set_unit_checksums(c, 0);
   const int cr = avr_compress_file(c, file, n, model, &avrc, &avrc_len);
   avr_set_recode_escaped(c, esc);
   avr_set_checksums(c, chk);
+  avr_set_unit_checksums(c, uck);
   if (cr) return cr;
   hs->result.assign(avrc, avrc + avrc_len);
   free(avrc);
@@ -798,11 +800,13 @@ int avr_hooks_end(avr_hooks_session* hs, uint8_t** out, size_t* out_len) {
                                     &avrc, &avrc_len);
             }))
           return r;
-      } else {   // as at avr_hooks_compress_begin: a session's container carries no file CRC
-        const int chk = avr_get_checksums(hs->c);
+      } else {   // as at avr_hooks_compress_begin: a session's container carries no file CRC and no unit checksums
+        const int chk = avr_get_checksums(hs->c), uck = avr_get_unit_checksums(hs->c);
         avr_set_checksums(hs->c, 0);
+        avr_set_unit_checksums(hs->c, 0);
         const int r = avr_compress_file(hs->c, hs->original.data(), hs->original.size(), hs->model, &avrc, &avrc_len);
         avr_set_checksums(hs->c, chk);
+        avr_set_unit_checksums(hs->c, uck);
         if (r) return r;
       }
       hs->result.assign(avrc, avrc + avrc_len);

@@ -143,7 +143,7 @@ constexpr size_t kCrcChunk = (size_t)4 << 20;   // a long item's share of one ho
 
 }  // namespace
 
-uint32_t fold_file_crc(std::vector<CrcItem>* items) {
+void resolve_crc_items(std::vector<CrcItem>* items) {
   // the bytes nobody has CRC'd yet, in chunks, on host threads when they are many
   struct Job {
     size_t item;
@@ -172,16 +172,27 @@ uint32_t fold_file_crc(std::vector<CrcItem>* items) {
   for (CrcItem& it : *items)
     if (!it.known) it.crc = 0;
   for (const Job& j : jobs) (*items)[j.item].crc = avr_crc32_combine((*items)[j.item].crc, j.crc, j.len);
-  // the last-byte rule on each value, then the blocks in file order
+  // the last-byte rule on each value
   const z_crc_t* byte_table = get_crc_table();
-  uint32_t crc = 0;
   for (CrcItem& it : *items) {
-    uint64_t len = it.len;
-    if (it.rule == LastByte::kAppend) it.crc = avr_crc32(it.crc, &it.last_byte, 1), len++;
+    if (it.rule == LastByte::kAppend) it.crc = avr_crc32(it.crc, &it.last_byte, 1), it.len++;
     else if (it.rule == LastByte::kReplace) it.crc ^= (uint32_t)byte_table[it.regen_last ^ it.last_byte];
-    crc = avr_crc32_combine(crc, it.crc, len);
+    it.known = true;
+    it.rule = LastByte::kKeep;
   }
+}
+
+// the blocks in file order
+uint32_t combine_crc_items(const std::vector<CrcItem>& items) {
+  uint32_t crc = 0;
+  for (const CrcItem& it : items)
+    if (it.in_file) crc = avr_crc32_combine(crc, it.crc, it.len);
   return crc;
+}
+
+uint32_t fold_file_crc(std::vector<CrcItem>* items) {
+  resolve_crc_items(items);
+  return combine_crc_items(*items);
 }
 
 }  // namespace avr_host

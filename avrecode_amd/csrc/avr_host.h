@@ -279,6 +279,14 @@ struct FileCrcArg {
   bool on = false;
   const uint32_t* crcs = nullptr;
 };
+// Unit checksums (Block field 18, include/avrecode.h, avr_set_unit_checksums): write the field on
+// every coded block -- slice i's values from (*values)[i] where the caller brings them (a device
+// computed them over the payload arena; empty: none for that slice) or from the payload on host
+// threads, a cut block's units read from its seams field.
+struct UnitCrcArg {
+  bool on = false;
+  const std::vector<std::vector<uint32_t>>* values = nullptr;
+};
 bool recodable_candidate(const avr::SliceInfo& s);
 std::vector<SliceView> views_of(const ParsedFile& pf);
 // escapes (the parallel models' opt-in second chance, AVR_ASSEMBLE_ESCAPED): a slice the search
@@ -293,7 +301,8 @@ int emit_container(const uint8_t* in, size_t n, const std::vector<SliceView>& sv
                    const std::vector<std::pair<const uint8_t*, size_t>>& recoded, int model, uint8_t** out,
                    size_t* out_len, uint8_t* dst = nullptr, size_t cap = 0,
                    const std::vector<std::pair<const uint8_t*, size_t>>* seams = nullptr,
-                   const std::vector<uint32_t>* escapes = nullptr, const FileCrcArg& crc = FileCrcArg());
+                   const std::vector<uint32_t>* escapes = nullptr, const FileCrcArg& crc = FileCrcArg(),
+                   const UnitCrcArg& units = UnitCrcArg());
 
 // ------------------------------------------------------------------ avr_seams.cpp: the seams codec
 struct SeamCe {
@@ -310,6 +319,7 @@ bool seam_encoder(const uint8_t* pay, size_t n, uint64_t bitpos, uint32_t offset
 bool seams_encode(const std::vector<const avr::SeamRec*>& recs, const std::vector<SeamCe>& ce, const avr_slice_desc& d,
                   const std::vector<uint32_t>& piece_len, std::vector<uint8_t>* out);
 bool seams_decode(const uint8_t* p, size_t n, const avr_slice_desc& d, size_t rec_stride, SeamsDecoded* sd);
+bool seams_cut_q(const uint8_t* p, size_t n, std::vector<uint32_t>* q);   // the cuts' q only, no descriptor needed
 bool splice_pieces(const avr_slice_desc* d, const avr_slice_result* r, const uint8_t* out, const std::vector<uint32_t>& q,
                    std::vector<uint8_t>* o);
 void last_byte_patch(std::vector<uint8_t>* o, const uint8_t* payload, size_t size);
@@ -377,6 +387,12 @@ struct DecJob {
   std::vector<SplitBlock> splits;
   bool has_crc = false;              // Recoded.Metadata field 16: the file's CRC-32 (a checked container)
   uint32_t file_crc = 0;
+  // Block field 18 (unit checksums): per block, whether it carries the field and its unit values
+  // combined in order -- the CRC-32 of the slice's payload, which every splice compares with the
+  // patched CRC of the slice's regenerated bytes.  Empty: no block has the field.
+  std::vector<char> block_checked;
+  std::vector<uint32_t> block_crc;
+  bool unit_checked(size_t i) const { return i < block_checked.size() && block_checked[i]; }
 };
 
 // sp: where the pieces of split blocks go (nullptr: such a container is refused -- the sharded and
@@ -418,7 +434,13 @@ struct CrcItem {
   bool known = false;
   LastByte rule = LastByte::kKeep;
   uint8_t last_byte = 0, regen_last = 0;   // the block's last_byte; kReplace: the regenerated last byte
+  bool in_file = true;   // false: a value of its own beside the file's fold (an escaped block's unescaped bytes)
 };
+// The two steps of the fold.  resolve: every item's crc and len made final -- the bytes nobody has
+// CRC'd yet on host threads, then the last-byte rule on the value (rule becomes kKeep).  combine: the
+// in_file items of a resolved list, in order.  fold_file_crc = both.
+void resolve_crc_items(std::vector<CrcItem>* items);
+uint32_t combine_crc_items(const std::vector<CrcItem>& items);
 uint32_t fold_file_crc(std::vector<CrcItem>* items);
 // a coded block's item: its len regenerated bytes at p (read for kReplace's one byte, and for the CRC
 // unless the caller brings it)
@@ -442,11 +464,15 @@ inline CrcItem crc_item_of_slice(const avr::PbBlock& b, const uint8_t* p, size_t
 // A checked container (j.has_crc) is checked here: crc_of(route, &crc) gives the CRC of those len
 // bytes where a device computed it (false: from the bytes, on host threads), and a file whose fold
 // is not the container's value is AVR_ERR_CHECKSUM.
+// So is every block with unit checksums (Block field 18, j.block_crc): its values combined against the
+// patched CRC of the slice's regenerated, unescaped bytes -- the same crc_of values or bytes -- with or
+// without the file's field; AVR_ERR_CHECKSUM names the block.
 template <class Slice, class Crc>
 int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>* o, Crc&& crc_of) {
   o->reserve(j.stream.size());
   std::vector<CrcItem> items;
-  if (j.has_crc) items.reserve(j.blocks.size());
+  std::vector<std::pair<size_t, size_t>> unit_checks;   // (item, block): blocks with field 18
+  if (j.has_crc || !j.block_checked.empty()) items.reserve(j.blocks.size());
   for (size_t i = 0; i < j.blocks.size(); i++) {
     const avr::PbBlock& b = j.blocks[i];
     if (b.has_literal) {
@@ -460,7 +486,8 @@ int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>*
     const uint8_t* p = nullptr;
     size_t len = 0;
     if (int stt = slice(route_of_block(k), &p, &len))
-      return fail(c, AVR_ERR_FORMAT, "slice " + std::to_string(k) + " failed to decode (" + std::to_string(stt) + ")");
+      return fail(c, AVR_ERR_FORMAT, "block " + std::to_string(i) + ": slice " + std::to_string(k) + " failed to decode (" +
+                                         std::to_string(stt) + ")");
     const size_t o0 = o->size();
     o->insert(o->end(), p, p + len);
     patch_last_byte(b, len, o);
@@ -471,13 +498,21 @@ int splice_job(ErrSink* c, const DecJob& j, Slice&& slice, std::vector<uint8_t>*
       o->resize(o0);
       o->insert(o->end(), e.begin(), e.end());
       if (j.has_crc) items.push_back(CrcItem{nullptr, e.size(), avr_crc32(0, e.data(), e.size()), true});
-    } else if (j.has_crc) {
+    }
+    if ((j.has_crc && !b.has_escapes) || j.unit_checked(i)) {   // the unescaped bytes' patched CRC
       uint32_t crc = 0;
       const bool have = crc_of(route_of_block(k), &crc);
+      if (j.unit_checked(i)) unit_checks.push_back({items.size(), i});
       items.push_back(crc_item_of_slice(b, p, len, have ? &crc : nullptr));
+      items.back().in_file = j.has_crc && !b.has_escapes;
     }
   }
-  if (j.has_crc && fold_file_crc(&items) != j.file_crc)
+  resolve_crc_items(&items);
+  for (const auto& uc : unit_checks)
+    if (items[uc.first].crc != j.block_crc[uc.second])
+      return fail(c, AVR_ERR_CHECKSUM, "block " + std::to_string(uc.second) +
+                                           ": the regenerated slice is not the one its unit checksums were made from (CRC-32)");
+  if (j.has_crc && combine_crc_items(items) != j.file_crc)
     return fail(c, AVR_ERR_CHECKSUM, "the container decoded to a file that is not the file it was made from (CRC-32)");
   return AVR_OK;
 }

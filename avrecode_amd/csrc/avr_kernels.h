@@ -195,5 +195,11 @@ hipError_t launch_gather_spans(const avr_span* spans, int n, const uint8_t* src,
                                uint64_t dst_len, int32_t* status, hipStream_t stream);
 hipError_t launch_range_tails(const avr_range_tail* tails, const avr_slice_result* res, int n, uint8_t* dst,
                               uint64_t dst_len, int32_t* status, hipStream_t stream);
+// avr_check_units (avr_k_check.hip): after the tails on the same stream, one workgroup per selected
+// unit whose status is still 0 and whose check has a value: the CRC-32 of its share of the slice in
+// src, the last-byte rule applied to the value, against checks[k].crc -- AVR_SLICE_CHECKSUM on a
+// mismatch, AVR_SLICE_OVERFLOW (nothing read) for a span outside src_len
+hipError_t launch_check_units(const avr_range_tail* tails, const avr_unit_check* checks, const avr_slice_result* res,
+                              int n, const uint8_t* src, uint64_t src_len, int32_t* status, hipStream_t stream);
 
 }  // namespace avr

@@ -12,6 +12,28 @@ using namespace avr_host;
 
 namespace avr_host {
 
+namespace {
+// Block field 18 of block i taken into the job: one value per unit -- the cuts' q say where the units
+// end, the last at `size` -- combined in order into the CRC-32 of the slice's payload.  False: not one
+// value per unit.
+bool take_unit_crcs(DecJob* j, size_t i, const std::vector<uint32_t>& q) {
+  const avr::PbBlock& b = j->blocks[i];
+  if (b.unit_crcs.size() != 4 * (q.size() + 1)) return false;
+  if (j->block_checked.empty()) {
+    j->block_checked.assign(j->blocks.size(), 0);
+    j->block_crc.assign(j->blocks.size(), 0);
+  }
+  uint32_t crc = 0;
+  for (size_t u = 0; u <= q.size(); u++) {
+    const uint64_t lo = u ? q[u - 1] : 0, hi = u < q.size() ? q[u] : (uint64_t)b.size;
+    crc = avr_crc32_combine(crc, b.unit_crc(u), hi - lo);
+  }
+  j->block_checked[i] = 1;
+  j->block_crc[i] = crc;
+  return true;
+}
+}  // namespace
+
 int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* plan, SplitPlan* sp) {
   const bool tm = getenv("AVR_ASM_TIMING") != nullptr;
   double t0 = now_s();
@@ -20,6 +42,8 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
   if (!avr::pb_parse(in, n, &j->blocks, &version, nullptr, &fc)) return fail(c, AVR_ERR_FORMAT, "not a Recoded protobuf");
   j->has_crc = fc.present;
   j->file_crc = fc.value;
+  j->block_checked.clear();
+  j->block_crc.clear();
   j->model = avr::model_of_version(version);
   // another avrecode-amd container format (the round-2 "avrecode-amd:P", ...) would be read as a
   // reference-model container and fail late: refuse it here
@@ -52,6 +76,8 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
       if (b.has_escapes && (b.escapes == 0 || b.escapes > (uint64_t)b.size / 2 + 1))
         return fail(c, AVR_ERR_FORMAT, "Invalid escapes count in coded block: " + std::to_string(b.escapes));
       total += (size_t)b.size + (size_t)b.escapes;
+      // an uncut block's one unit is the slice (a cut block's values wait for its seams, below)
+      if (b.has_unit_crcs && !b.has_seams) take_unit_crcs(j, (size_t)(&b - j->blocks.data()), {});
     } else if (!b.skip_coded) {
       return fail(c, AVR_ERR_FORMAT, "Unknown input block type");
     }
@@ -117,6 +143,8 @@ int decompress_setup(ErrSink* c, const uint8_t* in, size_t n, DecJob* j, Plan* p
       for (uint32_t l : sd.piece_len) tot += l;
       if (tot != b.cabac_len || sd.q.back() >= (uint64_t)b.size || sd.first_mb[0] <= (uint32_t)d.first_mb)
         return fail(c, AVR_ERR_FORMAT, "Invalid seams field in coded block.");
+      if (b.has_unit_crcs && !take_unit_crcs(j, next_coded, sd.q))
+        return fail(c, AVR_ERR_FORMAT, "unit checksums (block field 18): not one value per piece");
       SplitBlock x;
       x.block = (int)next_coded;
       x.first = (int)sp->plan.descs.size();
@@ -205,7 +233,9 @@ void map_blocks(avr_dec_plan* h) {
 // until the copies are done.
 // A checked container (job.has_crc) is checked here, before anything is written: the fold of the
 // blocks' CRCs (fold_file_crc) -- the slices' from crcs, or without them from regen on host threads --
-// against the container's value, AVR_ERR_CHECKSUM when they differ.
+// against the container's value, AVR_ERR_CHECKSUM when they differ.  So is every block with unit
+// checksums (field 18): its values combined (job.block_crc) against the patched CRC of its slice's
+// regenerated bytes, from the same crcs or bytes, with or without the file's field.
 int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* regen, size_t regen_len,
                   const uint64_t* offsets, const uint32_t* lens, std::vector<avr::PbCopy>* copies,
                   std::vector<std::pair<size_t, uint8_t>>* patches, std::vector<std::vector<uint8_t>>* side,
@@ -219,7 +249,14 @@ int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* r
       return AVR_ERR_INVALID_ARGUMENT;
   copies->reserve(j.blocks.size());
   std::vector<CrcItem> items;
-  if (j.has_crc) items.reserve(j.blocks.size());
+  std::vector<std::pair<size_t, size_t>> unit_checks;   // (item, block): blocks with field 18
+  if (j.has_crc || !j.block_checked.empty()) items.reserve(j.blocks.size());
+  // the patched CRC of a coded block's regenerated (unescaped) bytes: the file's item, a unit check's, or both
+  auto slice_item = [&](size_t i, int k, bool in_file) {
+    if (j.unit_checked(i)) unit_checks.push_back({items.size(), i});
+    items.push_back(crc_item_of_slice(j.blocks[i], regen + offsets[k], lens[k], crcs ? &crcs[k] : nullptr));
+    items.back().in_file = in_file;
+  };
   size_t at = 0;
   for (size_t i = 0; i < j.blocks.size(); i++) {
     const avr::PbBlock& b = j.blocks[i];
@@ -242,18 +279,22 @@ int splice_layout(const avr_dec_plan* h, const int32_t* status, const uint8_t* r
       side->push_back(std::move(e));
       copies->push_back({at, side->back().data(), side->back().size()});
       if (j.has_crc) items.push_back(CrcItem{side->back().data(), side->back().size()});
+      if (j.unit_checked(i)) slice_item(i, k, false);
       at += side->back().size();
       continue;
     }
     if (len) copies->push_back({at, regen + offsets[k], len});
-    if (j.has_crc) items.push_back(crc_item_of_slice(b, regen + offsets[k], len, crcs ? &crcs[k] : nullptr));
+    if (j.has_crc || j.unit_checked(i)) slice_item(i, k, j.has_crc);
     const LastByte rule = last_byte_rule(b, len);
     const size_t m = len + (rule == LastByte::kAppend);
     if (rule != LastByte::kKeep) patches->push_back({at + m - 1, (uint8_t)b.last_byte[0]});
     at += m;
   }
   *total = at;
-  if (j.has_crc && fold_file_crc(&items) != j.file_crc) return AVR_ERR_CHECKSUM;
+  resolve_crc_items(&items);
+  for (const auto& uc : unit_checks)
+    if (items[uc.first].crc != j.block_crc[uc.second]) return AVR_ERR_CHECKSUM;
+  if (j.has_crc && combine_crc_items(items) != j.file_crc) return AVR_ERR_CHECKSUM;
   return AVR_OK;
 }
 
@@ -465,6 +506,66 @@ int avr_dec_plan_range_apply(const avr_span* spans, int n_spans, const avr_range
     failed |= st != 0;
   }
   return failed ? AVR_ERR_FORMAT : AVR_OK;
+}
+
+// What check_units_kernel (avr_k_check.hip) does, on host buffers: the CPU tests' reference for it, and
+// what tests/native/unit_check.cpp drives under sanitizers.  The last-byte rule goes onto the value
+// with fold_file_crc's arithmetic (avr_host.cpp).
+int avr_unit_checks_apply(const avr_range_tail* tails, const avr_unit_check* checks, const avr_slice_result* res, int n,
+                          const uint8_t* src, size_t src_len, int32_t* status) {
+  if (n < 0 || (n && (!tails || !checks || !res || !status))) return AVR_ERR_INVALID_ARGUMENT;
+  bool mismatch = false, outside = false;
+  for (int k = 0; k < n; k++) {
+    const avr_range_tail& t = tails[k];
+    const avr_unit_check& ck = checks[k];
+    if (status[k] != 0 || res[k].status != 0 || !ck.have) continue;
+    const uint32_t out_len = res[k].out_len;
+    uint32_t len = out_len;
+    LastByte rule = LastByte::kKeep;
+    if (t.keep != UINT32_MAX) {
+      len = t.keep;   // a piece that is not its slice's last: its share, even when it regenerated more
+    } else if (t.has_rule) {
+      const uint64_t T = (uint64_t)t.q_last + out_len;
+      rule = (uint32_t)(T & 1) != (uint32_t)(t.length_parity & 1) ? LastByte::kAppend
+             : len                                                ? LastByte::kReplace
+                                                                  : LastByte::kKeep;
+    }
+    if (ck.src_off > src_len || len > src_len - ck.src_off || (len && !src)) {
+      status[k] = AVR_SLICE_OVERFLOW;
+      outside = true;
+      continue;
+    }
+    uint32_t crc = len ? avr_crc32(0, src + ck.src_off, len) : 0;
+    if (rule == LastByte::kAppend) {
+      crc = avr_crc32(crc, &t.last_byte, 1);
+    } else if (rule == LastByte::kReplace) {
+      uint32_t e = (uint32_t)(src[ck.src_off + len - 1] ^ t.last_byte);   // the raw byte table's entry
+      for (int i = 0; i < 8; i++) e = (e >> 1) ^ (0xEDB88320u & (0u - (e & 1)));
+      crc ^= e;
+    }
+    if (crc != ck.crc) {
+      status[k] = AVR_SLICE_CHECKSUM;
+      mismatch = true;
+    }
+  }
+  return mismatch ? AVR_ERR_CHECKSUM : outside ? AVR_ERR_FORMAT : AVR_OK;
+}
+
+int avr_dec_plan_unit_crcs(const avr_dec_plan* h, int unit_lo, int unit_hi, avr_unit_check* out) {
+  if (!h || !h->avrc || !h->pieces || unit_lo < 0 || unit_hi < unit_lo || (size_t)unit_hi > h->units.size() ||
+      (unit_hi > unit_lo && !out) || h->unit_first.size() != h->job.blocks.size() + 1)
+    return AVR_ERR_INVALID_ARGUMENT;
+  const std::vector<avr::PbBlock>& bl = h->job.blocks;
+  size_t i = 0;
+  for (int u = unit_lo; u < unit_hi; u++) {
+    while (i < bl.size() && h->unit_first[i + 1] <= u) i++;
+    if (i >= bl.size()) return AVR_ERR_FORMAT;
+    const size_t at = (size_t)(u - h->unit_first[i]);
+    const bool have = h->job.unit_checked(i) && 4 * (at + 1) <= bl[i].unit_crcs.size();
+    out[u - unit_lo].crc = have ? bl[i].unit_crc(at) : 0u;
+    out[u - unit_lo].have = have ? 1u : 0u;
+  }
+  return AVR_OK;
 }
 
 int avr_dec_plan_new(avr_dec_plan** out) {

@@ -149,6 +149,28 @@ bool seams_decode(const uint8_t* p, size_t n, const avr_slice_desc& d, size_t re
   return true;
 }
 
+// The cuts' q alone (piece i covers slice bytes [q[i - 1], q[i])), for the callers that need a cut
+// block's units and hold no descriptor: the container writer's unit CRCs and avr_container_describe.
+// The layout's own checks only; the states are seams_decode's business.
+bool seams_cut_q(const uint8_t* p, size_t n, std::vector<uint32_t>* q) {
+  q->clear();
+  if (n < 4) return false;
+  const uint32_t rl = get_le32(p);
+  if (rl < 12 || rl > (1u << 30)) return false;
+  std::vector<uint8_t> raw(rl);
+  uLongf got = rl;
+  if (uncompress(raw.data(), &got, p + 4, n - 4) != Z_OK || got != rl || get_le32(raw.data()) != 2) return false;
+  const uint32_t k = get_le32(raw.data() + 4), w = get_le32(raw.data() + 8);
+  const size_t per = 32 + 1024 + (size_t)avr::kEdgeBytes * w;
+  if (k == 0 || k > 65536 || w > (uint32_t)avr::kMringCols || 12 + 4 * ((size_t)k + 1) + per * k != rl) return false;
+  const uint8_t* r = raw.data() + 12 + 4 * ((size_t)k + 1);
+  for (uint32_t i = 0; i < k; i++, r += per) {
+    q->push_back(get_le32(r + 4));
+    if (i && (*q)[i] <= (*q)[i - 1]) return false;
+  }
+  return true;
+}
+
 // the regenerated bytes of a split slice from its q.size() + 1 pieces, units d[i] / r[i] of a pieces
 // launch that wrote `out`: piece i's bytes up to cut i's q (the cut's first byte), the last piece
 // whole; false if a piece failed or came out short

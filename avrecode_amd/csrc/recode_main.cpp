@@ -1,7 +1,8 @@
-// recode CLI (recode.cpp:1627-1659): recode [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] <input> [output]
+// recode CLI (recode.cpp:1627-1659): recode [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] [-u] <input> [output]
 //                                    recode read <in.avrc> <offset> <length> [output]
 //   read  a byte range of the file a container restores (avr_reader_*): only the slices and pieces the
 //         range touches are regenerated where the container allows it; the range is clamped to the file.
+//         A unit whose bytes miss its checksum (-u) fails the read: the error names it, the exit status is 1.
 //   -p    parallel model (fresh model per slice; slices independent) on the reference's
 //         arithmetic_code<uint64_t, uint8_t>; default = reference model.
 //   -p32  parallel model on the optional 32-bit P32 coder (avrecode-amd:P32 containers).
@@ -12,6 +13,9 @@
 //         (avr_set_split_p32; avrecode-amd:P32S / P32SE containers).
 //   -k    compress and roundtrip, any model: a checked container -- the file's CRC-32 in its Metadata
 //         (avr_set_checksums); decompress checks the field wherever it finds it.
+//   -u    with -p / -p32, compress and roundtrip: unit checksums -- a CRC-32 per slice and per piece of a
+//         cut slice in the container (avr_set_unit_checksums); decompress and read check them wherever
+//         they find them.
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -101,21 +105,22 @@ static int read_range(int argc, char** argv) {
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::cerr << "Usage: " << argv[0] << " [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] <input> [output]\n"
+    std::cerr << "Usage: " << argv[0] << " [compress|decompress|roundtrip] [-p|-p32|-c] [-e] [-s] [-k] [-u] <input> [output]\n"
               << "       " << argv[0] << " read <in.avrc> <offset> <length> [output]" << std::endl;
     return 1;
   }
   std::string cmd = argv[1];
   if (cmd == "read") return read_range(argc, argv);
   int a = 2, model = AVR_MODEL_REFERENCE;
-  bool escaped = false, split32 = false, checks = false;
-  for (; a < argc; a++) {   // the model, -e, -s and -k, in any order
+  bool escaped = false, split32 = false, checks = false, units = false;
+  for (; a < argc; a++) {   // the model, -e, -s, -k and -u, in any order
     if (!strcmp(argv[a], "-p")) model = AVR_MODEL_PARALLEL;
     else if (!strcmp(argv[a], "-p32")) model = AVR_MODEL_PARALLEL32;
     else if (!strcmp(argv[a], "-c")) model = AVR_MODEL_CHAINED;
     else if (!strcmp(argv[a], "-e")) escaped = true;
     else if (!strcmp(argv[a], "-s")) split32 = true;
     else if (!strcmp(argv[a], "-k")) checks = true;
+    else if (!strcmp(argv[a], "-u")) units = true;
     else break;
   }
   if (escaped && ((model != AVR_MODEL_PARALLEL && model != AVR_MODEL_PARALLEL32) || cmd == "decompress")) {
@@ -124,6 +129,10 @@ int main(int argc, char** argv) {
   }
   if (split32 && (model != AVR_MODEL_PARALLEL32 || cmd == "decompress")) {
     std::cerr << "-s goes with compress or roundtrip and -p32" << std::endl;
+    return 1;
+  }
+  if (units && ((model != AVR_MODEL_PARALLEL && model != AVR_MODEL_PARALLEL32) || cmd == "decompress")) {
+    std::cerr << "-u goes with compress or roundtrip and -p or -p32" << std::endl;
     return 1;
   }
   if (a >= argc) return 1;
@@ -142,6 +151,7 @@ int main(int argc, char** argv) {
   if (escaped) avr_set_recode_escaped(ctx, 1);
   if (split32) avr_set_split_p32(ctx, 1);
   if (checks) avr_set_checksums(ctx, 1);
+  if (units) avr_set_unit_checksums(ctx, 1);
   uint8_t* out = nullptr;
   size_t out_len = 0;
   int r;

@@ -394,7 +394,8 @@ def compress_range(ctx, part: ParsedStream, device=None, model: int = MODEL_PARA
 
 def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = None,
                      model: int = MODEL_PARALLEL, split_bytes: int | None = None, run_range=None,
-                     escaped: bool = False, split_p32: bool = False, checksums: bool = False) -> bytes | None:
+                     escaped: bool = False, split_p32: bool = False, checksums: bool = False,
+                     unit_checksums: bool = False) -> bytes | None:
     """PARALLEL-model compress of one file across all ranks; the container is returned on rank 0.
 
     Every rank parses the file (host), takes its contiguous slice range (partition), runs it on its
@@ -424,6 +425,10 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     literals' into the file's CRC (avr_assemble_container_args, ASSEMBLE_CRC): byte-identical to
     ctx.compress(data, model) with ctx.checksums on.  A device step that returns no sixth value has
     them computed from the payloads on the host.
+    unit_checksums (pass ctx.unit_checksums): rank 0 assembles with ASSEMBLE_UNIT_CRC -- Block field 18
+    on every coded block, the unit values computed there on host threads from the payloads and the
+    seams' cuts (the ranks' work does not change; values brought from their devices are not taken
+    yet) -- byte-identical to ctx.compress(data, model) with ctx.unit_checksums on.
     run_range(part) -> compress_range's tuple replaces the device step (CPU tests)."""
     import torch
     import torch.distributed as dist
@@ -463,9 +468,10 @@ def sharded_compress(ctx, data: bytes, device=None, ps: ParsedStream | None = No
     if gs is not None:
         _, sblob, soffs, slens = gs
         return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, seams=(sblob, soffs, slens),
-                                  escaped=escaped, split32=split32, checksums=checksums, crcs=gc)
+                                  escaped=escaped, split32=split32, checksums=checksums, crcs=gc,
+                                  unit_checksums=unit_checksums)
     return assemble_container(data, st, blob, offs, lens, model=model, ps=ps, escaped=escaped, checksums=checksums,
-                              crcs=gc)
+                              crcs=gc, unit_checksums=unit_checksums)
 
 
 def _gather_device(ctx, device):

@@ -32,7 +32,10 @@
 extern "C" {
 #endif
 
-#define AVRECODE_ABI_VERSION 12 /* 12: range reads (avr_reader_*, avr_dec_plan_file_size, avr_dec_plan_range(_apply),
+#define AVRECODE_ABI_VERSION 13 /* 13: unit checksums, opt-in (avr_set_unit_checksums, Block field 18, AVR_SLICE_CHECKSUM,
+                                 *    avr_check_units, avr_unit_checks_apply, avr_dec_plan_unit_crcs, AVR_ASSEMBLE_UNIT_CRC,
+                                 *    avr_reader_info_t.unit_checked);
+                                 * 12: range reads (avr_reader_*, avr_dec_plan_file_size, avr_dec_plan_range(_apply),
                                  *    avr_gather_spans, avr_range_tails);
                                  * 11: checked containers, opt-in (avr_set_checksums, Metadata field 16, AVR_ERR_CHECKSUM,
                                  *    avr_crc_spans, avr_crc32(_combine), avr_assemble_container_args, avr_dec_plan_splice_crc);
@@ -190,6 +193,39 @@ uint32_t avr_crc32_combine(uint32_t a, uint32_t b, uint64_t len_b);
 int avr_crc_spans(avr_ctx* ctx, const uint8_t* d_buf, size_t buf_len, const uint64_t* d_off, const uint32_t* d_len,
                   int n, uint32_t* d_crc, int32_t* d_status, void* stream);
 
+/* Unit checksums: a CRC-32 per unit in the container, an option of the parallel models, off by default
+ * (with it off every container is byte for byte what it was).  A unit is what one workgroup
+ * regenerates: a whole coded slice, or one piece of a cut slice.  The file CRC above guards whole-file
+ * calls only -- a range read (avr_reader_*) regenerates a few units and cannot fold a file's value --
+ * and a flipped bit in Block.cabac can regenerate a slice of the right length with wrong bytes, which
+ * neither the unit statuses nor the reader's length check see.  With the option on,
+ * avr_compress_file(s) and avr_roundtrip_file(s) of AVR_MODEL_PARALLEL / AVR_MODEL_PARALLEL32 write
+ * Block field 18 ("unit_crcs", wire type 2) on every coded block: 4 m bytes, one little-endian CRC-32
+ * (zlib's) per unit in unit order, m = 1 for an uncut block, the number of pieces for one with field
+ * 16.  Unit i covers slice bytes [q[i-1], q[i]) (q[-1] = 0, the last unit to `size`: the range
+ * planner's coordinates) of the slice's payload, in the unescaped domain (also on a block with field
+ * 17), as the file holds them after the last-byte rule; the values combined in order
+ * (avr_crc32_combine with the unit lengths) are the payload's CRC.  7 bytes per uncut block,
+ * 4 m + 3 for a cut one (m <= 31; 4 m + 4 beyond).  No tag changes: the field is additive and a reader
+ * from before it (the reference's included) skips it.  The reference and chained models ignore the
+ * option (their bytes are pinned), and hooks compress sessions never write the field.
+ * The values come from the device, where the payloads lie: an uncut slice's from the per-slice payload
+ * CRC pass of the checked containers, a cut slice's from one avr_crc_spans launch over the payload
+ * arena once the cuts are known; a value the device refused is computed on the host.
+ * Reading needs no option.  AVR_ERR_FORMAT for the field on a block without cabac, a second one,
+ * another wire type, or a length that is not 4 x the block's unit count.  The field may stand on some
+ * coded blocks and not on others: a block without it is unchecked.  Every path that regenerates a
+ * unit checks it: a range read the units it touched (avr_check_units: AVR_ERR_CHECKSUM names the
+ * unit, reads that avoid it still succeed), every whole-file path (avr_decompress_file(s),
+ * avr_splice_container, avr_dec_plan_splice(_crc)) each block -- its values combined against the
+ * patched CRC of the slice's regenerated bytes, from device values where the caller has them, with or
+ * without Metadata field 16 (both present: both checked) -- AVR_ERR_CHECKSUM naming the block.
+ * Not covered: hooks sessions ignore the field (either direction); a sharded decompress checks only
+ * through rank 0's splice; the reference and chained models; a non-random-access reader checks through
+ * its whole-file call.  Default: the environment's AVR_UNIT_CHECKSUMS (non-zero: on), else 0. */
+int avr_set_unit_checksums(avr_ctx* ctx, int on);
+int avr_get_unit_checksums(const avr_ctx* ctx);
+
 /* ------------------------------------------------------------------ whole files (host memory) */
 /* in: an MP4 (avcC) or Annex-B H.264 file.  *out: serialized Recoded protobuf (recode.proto). */
 int avr_compress_file(avr_ctx* ctx, const uint8_t* in, size_t n, int model, uint8_t** out, size_t* out_len);
@@ -297,7 +333,8 @@ enum {
   AVR_SLICE_NO_STOP = -11,        /* compress: a CABAC re-encode would not restore the payload (last-byte rule) */
   AVR_SLICE_OVERFLOW = -12,       /* output past out_capacity */
   AVR_SLICE_MBAFF_RING = -20,     /* MBAFF slice launched with max_mb_width < 3 * mb_width + 7 */
-  AVR_SLICE_NO_ROUNDTRIP = -21    /* file calls: the device roundtrip check did not regenerate the payload */
+  AVR_SLICE_NO_ROUNDTRIP = -21,   /* file calls: the device roundtrip check did not regenerate the payload */
+  AVR_SLICE_CHECKSUM = -22        /* avr_check_units: the unit's regenerated bytes are not the ones its CRC was made from */
 };
 
 typedef struct {
@@ -636,8 +673,11 @@ int avr_assemble_container_seams_parsed(const uint8_t* file, size_t n, int model
  * flag with any other model.
  * AVR_ASSEMBLE_CRC: a checked container (avr_set_checksums), for every assemblable model: the file's
  * CRC-32 is folded from the literals and the coded slices' payload CRCs, which the assembly computes
- * on host threads -- or takes from avr_assemble_container_args' crcs. */
-enum { AVR_ASSEMBLE_ESCAPED = 1, AVR_ASSEMBLE_SPLIT32 = 2, AVR_ASSEMBLE_CRC = 4 };
+ * on host threads -- or takes from avr_assemble_container_args' crcs.
+ * AVR_ASSEMBLE_UNIT_CRC: unit checksums (avr_set_unit_checksums), the parallel models only
+ * (AVR_ERR_INVALID_ARGUMENT otherwise): Block field 18 on every coded block, the values computed here on
+ * host threads from the payloads and the seams' q.  (Bit 8 is not a flag.) */
+enum { AVR_ASSEMBLE_ESCAPED = 1, AVR_ASSEMBLE_SPLIT32 = 2, AVR_ASSEMBLE_CRC = 4, AVR_ASSEMBLE_UNIT_CRC = 16 };
 int avr_assemble_container_opts(const uint8_t* file, size_t n, int model, const avr_slice_desc* descs, int n_slices,
                                 const uint8_t* arena, size_t arena_len, const int32_t* status, const uint8_t* recoded,
                                 size_t recoded_len, const uint64_t* offsets, const uint32_t* lens, const uint8_t* seams,
@@ -784,6 +824,32 @@ int avr_gather_spans(avr_ctx* ctx, const avr_span* d_spans, int n, const uint8_t
                      size_t dst_len, int32_t* d_status, void* stream);
 int avr_range_tails(avr_ctx* ctx, const avr_range_tail* d_tails, const avr_slice_result* d_res, int n, uint8_t* d_dst,
                     size_t dst_len, int32_t* d_status, void* stream);
+/* The unit check of a range read (ABI 13, avr_set_unit_checksums): after avr_range_tails on the same
+ * stream, one workgroup of 256 threads per selected unit k.  Nothing happens when d_status[k] != 0,
+ * d_res[k].status != 0 or d_checks[k].have == 0 (the status stays).  Otherwise the CRC-32 of the unit's
+ * share of its slice -- d_tails[k].keep bytes of a piece that is not its slice's last (even when it
+ * regenerated more), d_res[k].out_len bytes of a last piece or whole slice, at d_src + src_off -- with
+ * the last-byte rule applied to the value, decided as avr_range_tails decides it from
+ * T = q_last + out_len (replace: the raw byte table's entry for the difference of the two last bytes;
+ * append: last_byte through the register, out_len = 0 included; else nothing), is compared with
+ * d_checks[k].crc: d_status[k] = AVR_SLICE_CHECKSUM on a mismatch, AVR_SLICE_OVERFLOW for a span that
+ * does not lie inside src_len (nothing of it is read).  All pointers are device pointers; nothing is
+ * synchronised; n <= 0 launches nothing.
+ * avr_dec_plan_unit_crcs (host only, a piece plan): crc / have of the units [unit_lo, unit_hi) from
+ * their blocks' field 18 (have = 0 for a unit of a block without it); src_off is the caller's.
+ * avr_unit_checks_apply (host only): avr_check_units on host buffers.  AVR_ERR_CHECKSUM when it set an
+ * AVR_SLICE_CHECKSUM, else AVR_ERR_FORMAT when it set an AVR_SLICE_OVERFLOW, else AVR_OK. */
+typedef struct {
+  uint64_t src_off;   /* where the unit's regenerated bytes start in d_src */
+  uint32_t crc;       /* the unit's value of Block field 18 */
+  uint32_t have;      /* 0: the unit's block carries no field; nothing is checked */
+} avr_unit_check;
+int avr_check_units(avr_ctx* ctx, const avr_range_tail* d_tails, const avr_unit_check* d_checks,
+                    const avr_slice_result* d_res, int n, const uint8_t* d_src, size_t src_len, int32_t* d_status,
+                    void* stream);
+int avr_dec_plan_unit_crcs(const avr_dec_plan* plan, int unit_lo, int unit_hi, avr_unit_check* out);
+int avr_unit_checks_apply(const avr_range_tail* tails, const avr_unit_check* checks, const avr_slice_result* res, int n,
+                          const uint8_t* src, size_t src_len, int32_t* status);
 
 /* The reader: pread on an opened container.  avrc must stay valid and unchanged until avr_reader_close;
  * one reader belongs to one context (and its host thread); it owns its device buffers, reuses them
@@ -796,16 +862,20 @@ int avr_range_tails(avr_ctx* ctx, const avr_range_tail* d_tails, const avr_slice
  * the window's literal bytes into one pinned staging buffer, uploads it, regenerates the units on the
  * context's stream (pieces through avr_decompress_pieces_m's path, whole slices -- field and MBAFF
  * ones included -- through avr_decompress_slices', one launch after the other), gathers the window
- * (avr_gather_spans), runs the tails (avr_range_tails), downloads the statuses and only then the
- * bytes.  A selected unit with a non-zero status fails the read with AVR_ERR_FORMAT
- * (avr_last_error on the context); `out` is then untouched (d_out: unspecified).
+ * (avr_gather_spans), runs the tails (avr_range_tails) and -- when a selected unit's block carries
+ * unit checksums (Block field 18) -- the unit checks (avr_check_units), downloads the statuses and only
+ * then the bytes.  A selected unit with a non-zero status fails the read with AVR_ERR_FORMAT, one whose
+ * bytes miss its checksum (AVR_SLICE_CHECKSUM) with AVR_ERR_CHECKSUM (avr_last_error on the context
+ * names the unit); `out` is then untouched (d_out: unspecified).  A read that touches no block with the
+ * field launches nothing more and its avr_read_stats are what they were.
  * Everything else (info.random_access = 0: reference and chained models, every "E" tag -- an escaped
  * block's bytes are not a crop of its regenerated bytes): the first read regenerates the whole file
  * once through avr_decompress_file (so a checked container is checked: AVR_ERR_CHECKSUM), the reader
  * keeps it in host memory and serves every read from there.
  * Checked containers: a partial read cannot verify a file CRC.  info.checked says that field 16 is
  * present; random-access reads are guarded by the per-unit statuses and the strict length check
- * (above), not by field 16.
+ * (above), not by field 16 -- and by the unit checksums where the container has them:
+ * info.unit_checked = 1 when every coded block carries Block field 18.
  * pread semantics: the window is clamped to the file; *got = 0 with AVR_OK at or past the end and for
  * len = 0 (nothing is launched); off + len overflowing is AVR_ERR_INVALID_ARGUMENT.
  * avr_reader_span: [*lo, *hi) = the file bytes of the block holding off, *coded = 1 for a coded block
@@ -818,7 +888,7 @@ typedef struct {
   int32_t model;           /* AVR_MODEL_* */
   int32_t random_access;
   int32_t n_blocks, n_units;   /* n_units: 0 without random access */
-  int32_t checked, reserved;
+  int32_t checked, unit_checked;
 } avr_reader_info_t;
 typedef struct {
   uint64_t units, pieces;      /* units regenerated; those among them that are pieces of cut slices */
@@ -836,7 +906,8 @@ void avr_reader_close(avr_reader* r);
 /* Container codec check (host only): parse a Recoded protobuf (recode.proto:1-19) with the
  * library's own wire codec -- the one avr_decompress_file uses -- and return (a) its fields as JSON,
  * {"version": null | hex, "blocks": [{"size": int, "literal": hex, "skip_coded": bool, "cabac": hex,
- * "length_parity": bool, "last_byte": hex, "seams": hex, "escapes": int}, ...]} with only the fields present -- and
+ * "length_parity": bool, "last_byte": hex, "seams": hex, "escapes": int, "unit_crcs": [int, ...]}, ...]} with only the
+ * fields present (AVR_ERR_FORMAT for a malformed Block field 18, avr_set_unit_checksums) -- and
  * "file_crc": int after "version" when the Metadata holds field 16 -- and (b) the message
  * re-serialised by the library's writer (the one avr_compress_file uses; Metadata.version and field 16 only).
  * Both buffers are malloc'd (avr_free).  AVR_ERR_FORMAT when the bytes are not a Recoded message. */
